@@ -3,15 +3,19 @@
 (training_loop.py:369-391: noise -> ScoreUNet fwd -> MSE -> bwd -> grad all-reduce -> AdamW -> EMA) on the
 default configs/sda_unet.yml network, synthetic (B, F*w, 128, 128) fields, bf16 compute, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1 without a launcher: this process (which never touches a GPU) starts N rank processes itself -- what
         fabric.launch() does for the reference (train.py:93-100) -- and relays rank 0's JSON line;
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
         the ranks are the launcher's: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment.
 
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given (dump_outputs() below) and
+prints the line: the headline and its contract keys, `roofline` and `cpu_baseline` null.  Everything else it can measure runs only
+with --full, which adds the legs below to the same run.
+
 Rank 0 prints ONE compact JSON line (< 6 KB: the headline, `roofline`, `cpu_baseline` and a few scalars -- compact_line() below;
-tests/test_bench_launcher.py bounds its size) and writes everything else (`by_kernel`, the deep variant, the module-API legs, the
-sampler legs) to gpurun_out/bench_extras.json, named in the line's `extras_file`.  `roofline` is measured live (HIP events on the launch stream around every launch of the
+tests/test_bench_launcher.py bounds its size) and, with --full, writes everything else (`by_kernel`, the deep variant, the module-API
+legs, the sampler legs) to the extras file (extras_path()), named in the line's `extras_file`.  `roofline` is measured live (HIP events on the launch stream around every launch of the
 dominant kernel inside the timed region); `by_kernel` comes from extra steps AFTER the timed region in which every implicit-GEMM
 launch is bracketed by events and the two backward streams are serialised (each kernel alone on the chip); `cpu_baseline` is the
 CPU oracle (oracle/, a plain-PyTorch restatement of the same step) timed on this box's host cores, rank 0 at N=1 only.
@@ -53,6 +57,11 @@ def parse():
                    help="internal: run only the module_api legs (bench.py starts itself with this for a fresh process) and print their JSON")
     p.add_argument("--light-extras", action="store_true",
                    help="only the extras every rank of a multi-GPU job runs (vendor GEMM, by_kernel, sampler legs incl. the member-sharded one)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: roofline, vendor GEMM, by_kernel, sampler legs, deep variant, module API, "
+                        "CPU baseline (the options above narrow this set); without it a run does only the headline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed (loss, parameters, EMA) as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -341,18 +350,43 @@ def compact_line(full: dict, extras_file=None) -> str:
     return text
 
 
-def emit(json_fd, full: dict):
-    """Everything to the extras file (and nothing of it to stdout); the compact line, alone and last, to the saved stdout descriptor."""
-    path = extras_path()
-    try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(full, f, indent=1)
-        shown = os.path.relpath(path, REPO)
-    except OSError as e:
-        sys.stderr.write(f"bench.py: could not write {path}: {e}\n")
-        shown = None
+def emit(json_fd, full: dict, write_extras: bool = True):
+    """Everything to the extras file if `write_extras` (and nothing of it to stdout); the compact line, alone and last, to the saved
+    stdout descriptor."""
+    shown = None
+    if write_extras:
+        path = extras_path()
+        try:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(full, f, indent=1)
+            shown = os.path.relpath(path, REPO)
+        except OSError as e:
+            sys.stderr.write(f"bench.py: could not write {path}: {e}\n")
     os.write(json_fd, (compact_line(full, shown) + "\n").encode())
+
+
+DUMP_SAMPLE = 1 << 22  # entries written per flat buffer by dump_outputs(): 16 MB each in float32
+
+
+def dump_outputs(path: str, loss: torch.Tensor, trainer) -> None:
+    """What a caller of the timed path holds after its last step: the loss Trainer.step returned (`loss`), and the parameters
+    (`params`) and EMA weights (`ema`) it updated, as float32 <path>/<name>.npy.  The flat buffers (72 M entries for the default
+    network) are sampled at DUMP_SAMPLE positions drawn from a generator seeded 0 and sorted, the same positions in every run of the
+    same configuration; a buffer no larger than that is written whole."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = trainer.eng.flat
+    n = flat.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values.to(flat.device)
+    arrays = dict(loss=loss.detach().reshape(1), params=flat, ema=trainer.ema_flats[0])
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if idx is not None and t.numel() == n:
+            t = t[idx]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 # ----------------------------------------------------------------------------------------------------------------- one rank
@@ -394,8 +428,9 @@ def run_rank(a):
     ds = SyntheticWindowDataset(n_frames=1024 + w - 1, n_vars=a.vars, height=a.size, width=a.size, window=w, seed=0)
     feed = DeviceWindowFeed(ds, dev, rank=rank, num_replicas=world, seed=0)
 
-    timer = LaunchTimer(ops, trainer.eng, trainer.dt, a.batch)
-    timer.install()
+    timer = LaunchTimer(ops, trainer.eng, trainer.dt, a.batch) if a.full else None  # roofline and by_kernel: --full only
+    if timer is not None:
+        timer.install()
 
     def one_step():
         return trainer.step(feed.next_batch(a.batch, lazy=True))  # the windows are read in place by the input conversion
@@ -403,11 +438,13 @@ def run_rank(a):
     for _ in range(a.warmup):
         one_step()
     torch.cuda.synchronize()
-    timer.index_layers()
+    if timer is not None:
+        timer.index_layers()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.mode = "dominant"
+    if timer is not None:
+        timer.mode = "dominant"
     # the host enqueues ~330 launches per step one step ahead of the device; a generation-2 garbage collection in the middle of that (tens of
     # thousands of live tensor / ctypes objects) shows as one 50-ms step in twenty: collect now, not inside the timed region
     import gc
@@ -425,7 +462,8 @@ def run_rank(a):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    timer.mode = "off"
+    if timer is not None:
+        timer.mode = "off"
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -433,6 +471,8 @@ def run_rank(a):
     loss_val = float(loss)
     windows = a.batch * world * a.steps
     value = windows / elapsed
+    if a.dump_outputs and rank == 0:  # before any leg below takes another step
+        dump_outputs(a.dump_outputs, loss, trainer)
 
     out = None
     if rank == 0:
@@ -442,11 +482,11 @@ def run_rank(a):
         # roofline is priced on the FORWARD launches (bias / SiLU pair / residual / LayerNorm-emission epilogues); the average over every
         # launch of the same layers, input gradients included (LayerNorm-backward epilogues), is reported beside it -- it is what
         # `rocprofv3 --stats` averages.
-        dom_f = timer.summarise(lambda rec, kind: kind == "fwd", steps=a.steps)
-        dom_a = timer.summarise(steps=a.steps)
+        dom_f = timer.summarise(lambda rec, kind: kind == "fwd", steps=a.steps) if timer is not None else None
         gf_fwd = GFLOP_FWD.get(C, 116.0) if a.size == 128 else None
         roof = None
         if dom_f:
+            dom_a = timer.summarise(steps=a.steps)
             (kname, kf), = list(dom_f.items())[:1]
             ka = list(dom_a.values())
             all_ms = sum(v["ms_per_step"] for v in ka)
@@ -477,7 +517,7 @@ def run_rank(a):
             out["model_tflops_per_gpu"] = round(tf / world, 1)
             out["mfma_frac_whole_step"] = round(tf / world / MFMA_PEAK_TFLOPS, 4)
 
-    extras = not a.no_extras
+    extras = a.full and not a.no_extras
     # ---- what a plain dense GEMM of the vendor library reaches on THIS chip in THIS run (outside the headline region): the clock the
     # power governor holds under matrix load caps every bf16 kernel well below the 2.5 PFLOP/s spec peak `roofline.frac` is priced at
     def vendor_gemm():
@@ -595,11 +635,11 @@ def run_rank(a):
         out["sampler_configs3"] = _leg(out, "sampler_configs3", lambda: sampler_configs3(dev, a.precision if a.precision != "fp32" else "bf16"))
 
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = _leg(out, "cpu_baseline", lambda: cpu_baseline(C, a.size, DEFAULT_CFG))
         else:
             out["cpu_baseline"] = None
-        emit(json_fd, out)
+        emit(json_fd, out, write_extras=a.full)
     if dist.is_initialized():
         dist.destroy_process_group()
 

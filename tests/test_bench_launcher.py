@@ -232,3 +232,53 @@ def test_a_failing_extra_leg_is_reported_and_the_record_survives(capsys):
     full["deep_variant"] = None
     d = json.loads(bench.compact_line(full, "x.json"))
     assert d["extra_legs_failed"] == ["deep_variant"] and d["value"] == full["value"] and d["roofline"]["frac"]
+
+
+def test_a_plain_run_writes_no_extras_file(tmp_path, monkeypatch):
+    import json
+    full = _fake_full_result()
+    monkeypatch.setenv("C2W_BENCH_EXTRAS", str(tmp_path / "extras.json"))
+    rd, wr = os.pipe()
+    bench.emit(wr, full, write_extras=False)
+    os.close(wr)
+    data = os.read(rd, 65536)
+    os.close(rd)
+    assert data.count(b"\n") == 1 and json.loads(data)["extras_file"] is None
+    assert not (tmp_path / "extras.json").exists()
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_in_float32_within_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs: the loss, the flat parameters and the EMA; a buffer larger than DUMP_SAMPLE is sampled at the same fixed positions
+    in every run (the parameters' and the EMA's sample are the same entries)."""
+    import types
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    n = 5000
+    flat = torch.arange(n, dtype=torch.float32)
+    trainer = types.SimpleNamespace(eng=types.SimpleNamespace(flat=flat), ema_flats=[flat * 2])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(0.25), trainer)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["ema.npy", "loss.npy", "params.npy"]
+    arrs = {nm: np.load(tmp_path / "a" / nm) for nm in names}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    assert arrs["loss.npy"].tolist() == [0.25]
+    p = arrs["params.npy"]
+    assert p.shape == (1000,) and np.all(np.diff(p) >= 0) and np.array_equal(arrs["ema.npy"], 2 * p)
+    assert all(np.array_equal(arrs[nm], np.load(tmp_path / "b" / nm)) for nm in names)
+    small = types.SimpleNamespace(eng=types.SimpleNamespace(flat=flat[:500]), ema_flats=[flat[:500]])
+    bench.dump_outputs(str(tmp_path / "c"), torch.tensor(1.0), small)
+    assert np.array_equal(np.load(tmp_path / "c" / "params.npy"), flat[:500].numpy())  # written whole
+    # the real bound: two sampled flat buffers and the loss stay under 64 MB
+    monkeypatch.undo()
+    assert (2 * bench.DUMP_SAMPLE + 1) * 4 < 64 << 20
+
+
+def test_full_and_dump_outputs_options(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"

@@ -199,7 +199,7 @@ def test_bench_multi_rank_extras_run_through_the_communicator(tmp_path):
     env = dict(os.environ, C2W_FORCE_DIST="1", C2W_BENCH_EXTRAS=str(extras))
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "8",
-                          "--no-cpu-baseline", "--sample-steps", "1", "--kernel-steps", "1", "--light-extras"],
+                          "--no-cpu-baseline", "--sample-steps", "1", "--kernel-steps", "1", "--light-extras", "--full"],
                          capture_output=True, text=True, env=env, timeout=1200)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

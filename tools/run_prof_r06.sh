@@ -20,7 +20,7 @@ for args in "" "--ddp" "--ddp --bucket-view"; do
   tag=$(echo "plain$args" | tr -d ' -')
   python3 tools/bench_module_api.py --legs bf16_autocast --steps 20 --warmup 4 $args > $O/mapi_$tag.json 2> $O/mapi_$tag.err
 done
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/final_bench_line.json 2> $O/final_bench.err
+timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/final_bench_line.json 2> $O/final_bench.err
 cp gpurun_out/bench_extras.json $O/final_bench_extras.json
 tail -c 600 $O/final_bench_line.json
 ls $O

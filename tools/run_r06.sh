@@ -493,7 +493,7 @@ mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -rxX -p no:cacheprovider > $O/gpu_tests_full.txt 2>&1; tail -4 $O/gpu_tests_full.txt > $O/gpu_tests_tail.txt; tail -1 $O/gpu_tests_tail.txt
 C2W_WGRAD_STREAM=1 timeout 1500 python -m pytest tests -m gpu -q -rxX -p no:cacheprovider > $O/gpu_tests_two_streams_full.txt 2>&1; tail -4 $O/gpu_tests_two_streams_full.txt > $O/gpu_tests_tail_two_streams.txt; tail -1 $O/gpu_tests_tail_two_streams.txt
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-timeout 1500 python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 400 $O/bench_line.json
+timeout 1500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 400 $O/bench_line.json
 }
 
 st=${1:?stage}; shift
