@@ -1,0 +1,559 @@
+"""Float64 references of the conv, weight-gradient, LayerNorm and reduction kernels, each with an element-wise error bound.
+
+Every function takes the kernel's own (storage-typed) operands, computes the exact operation in torch.float64 with torch's own ops on
+the operands' device (F.conv2d, F.conv_transpose2d, F.interpolate, F.unfold, einsum; chunked by image) and returns V(ref, bound): two
+float64 tensors of the output's shape.  A correct kernel satisfies |got - ref| <= bound element by element (assert_within).  This module
+never calls climate2weather_amd.ops or tests/emu_ops.py.
+
+Error model (u32 = 2^-24; u_T = 2^-8 bf16, 2^-11 fp16, 2^-24 fp32).  A value is carried as V(v, e): v its exact fp64 value, e a bound
+on how far the kernel's fp32 / storage-typed value may be from v.  The kernels' arithmetic is restated operation by operation:
+
+  * fp32 add / sub / mul (_add, _mul):   e = e_a + e_b (+ |a| e_b + |b| e_a + e_a e_b for a product) + u32 (|v| + e)
+  * rounding to the storage type (_rnd): e += u_T (|v| + e) + floor_T; floor = 2^-25 for fp16 (half the subnormal spacing: results
+    below 2^-14 keep fewer bits), 0 otherwise.  The conversions are v_cvt_pk_*_f32, round to nearest even (common.h:26-40).
+  * transcendentals (_silu, _dsilu, _rsqrt): the propagated error times the function's largest slope (|silu'| <= 1.0998,
+    |silu''| <= 0.5, rsqrt: 0.5 s^-1.5 e_s at s - e_s), plus K_ULP = 4 fp32 ulps of the magnitude of the result's terms
+    (exp / rcp / rsq are 1-ulp instructions; silu = a * sigmoid(a) and dsilu = sg + h (1 - sg) add one rounding each).
+  * an fp32 sum of N terms t_i done as a chain of at most L dependent additions (_sum):
+        e = C_ACC u32 (sqrt(N) sqrt(sum t_i^2) + sqrt(L) |sum t_i|)  +  (propagated errors of the terms)
+    The first term is the rounding model for zero-mean terms (partial sums grow like sqrt(k)).  The second is the chain of
+    same-sign partial sums: with positive terms (loss sums, sum of squares) every partial sum is close to the total, and a chain of L
+    additions (per-thread loop + wave tree + one atomicAdd per wave or workgroup onto one address; pointwise.hip:375/581/653,
+    sampler.hip:80, conv_patch3.hip:375) rounds L times at that size.  L is taken from the kernels' launch geometry (_loss_chain);
+    where it is not, L = N.  sum t_i^2 is the same fp64 op on squared operands (conv(x^2, w^2), dW(x^2, dy^2)).  C_ACC = 8.
+    Propagated errors of the terms add up worst case inside a row (they share the row's statistics), and in quadrature
+    (C_ACC sqrt(sum e_i^2)) across pixels, where they come from independent roundings (the modulation gradients dm).
+  * conv K-sums: N = L = taps * Cin (kvalid when given); the bias is added in fp32 (conv_epilogue.h:46).
+
+Roundings counted from conv_epilogue.h: the accumulator (+ bias, + SiLU) is rounded to T into the LDS tile (:53 / :91; fp32 tiles keep
+fp32, :51); the multiplier (plain or dSiLU of it, :537/:540) and the residual (:547) are applied in fp32 to that rounded value and the
+sum is rounded again (:549); the SiLU pair takes silu / silu' of that stored value and rounds each (:551-562); the second output is
+silu of the stored value (:578-583); pool2 adds the four stored values in fp32 ((g00 + g01) + g10) + g11 and rounds (:469-491); the
+fused LayerNorm forward reads the stored sum (:429-436) and runs ln_fwd_kernel's arithmetic (two-pass variance, :438-455); the fused
+LayerNorm backward reads the conv tile as stored (:256), restates ln_bwd_kernel's arithmetic (:258-283) and rounds y once (:293);
+dm receives the fp32 rows before the residual (:283, :362).  LayerNorm (pointwise.hip:24-72, 80-195): u = x + m, mean, c = u - mean,
+q = sum c^2, rs = 1/sqrt(q/den + eps), out = c rs -- the statistics' errors propagate through these same rules, so (x - mean) * rstd
+carries the error of the mean in c and the error of q in rs.
+
+Bench-size cases: the reference is computed for every image and every reduction in full (no subset); the GPU tier's budget note is in
+tests/test_gpu_fp64_bounds.py.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+U32 = 2.0 ** -24
+UT = {torch.float32: 2.0 ** -24, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
+FLOOR = {torch.float32: 0.0, torch.bfloat16: 0.0, torch.float16: 2.0 ** -25}
+C_ACC = 8.0
+K_ULP = 4.0
+SILU_SLOPE, DSILU_SLOPE = 1.0998, 0.5
+CONV_1X1, CONV_S1, CONV_S2, CONV_UP, CONV_TS2 = 0, 1, 2, 3, 4  # include/c2w_hip.h
+ACT_NONE, ACT_SILU, ACT_SILU_PAIR = 0, 1, 2
+MUL_PLAIN, MUL_DSILU = 0, 1
+STORAGE = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}  # the library's dtype codes
+D = torch.float64
+CHUNK_ELEMS = 1 << 26  # doubles per image chunk of an im2col / conv intermediate
+
+
+class V:
+    """an fp64 value and the bound on the kernel's distance from it"""
+    __slots__ = ("v", "e")
+
+    def __init__(self, v, e=None):
+        self.v = v
+        self.e = torch.zeros_like(v) if e is None else e
+
+    def __iter__(self):
+        return iter((self.v, self.e))
+
+    def view(self, *shape):
+        return V(self.v.reshape(*shape), self.e.reshape(*shape))
+
+
+def exact(t):
+    return V(t.to(D))
+
+
+def _T(dtype):
+    return STORAGE[dtype] if isinstance(dtype, int) else dtype
+
+
+def _v(a):
+    return a if isinstance(a, V) else V(torch.as_tensor(a, dtype=D))
+
+
+def _add(a, b, sign=1.0):
+    a, b = _v(a), _v(b)
+    v = a.v + sign * b.v
+    e = a.e + b.e
+    return V(v, e + U32 * (v.abs() + e))
+
+
+def _sub(a, b):
+    return _add(a, b, -1.0)
+
+
+def _mul(a, b):
+    a, b = _v(a), _v(b)
+    v = a.v * b.v
+    e = a.v.abs() * b.e + b.v.abs() * a.e + a.e * b.e
+    return V(v, e + U32 * (v.abs() + e))
+
+
+def _scale(a, c):
+    """a times an fp32 constant that is itself one rounding away from c (1/C, 1/den)"""
+    v = a.v * c
+    e = a.e * abs(c) + 2 * U32 * (v.abs() + a.e * abs(c))
+    return V(v, e)
+
+
+def _rnd(a, dtype):
+    T = _T(dtype)
+    return V(a.v, a.e + UT[T] * (a.v.abs() + a.e) + FLOOR[T])
+
+
+def _sigmoid(x):
+    return torch.sigmoid(x)
+
+
+def _silu(a):
+    s = _sigmoid(a.v)
+    v = a.v * s
+    return V(v, SILU_SLOPE * a.e + K_ULP * U32 * v.abs())
+
+
+def _dsilu(a):
+    s = _sigmoid(a.v)
+    h = a.v * s
+    v = s + h * (1 - s)
+    return V(v, DSILU_SLOPE * a.e + K_ULP * U32 * (s + h.abs()))
+
+
+def _rsqrt(a):
+    v = a.v.rsqrt()
+    lo = (a.v - a.e).clamp_min(a.v * 1e-3)
+    return V(v, 0.5 * a.e * lo.pow(-1.5) + K_ULP * U32 * v)
+
+
+def _acc(total, sumsq, n, chain):
+    return C_ACC * U32 * (math.sqrt(n) * sumsq.clamp_min(0).sqrt() + math.sqrt(chain) * total.abs())
+
+
+def _sum(a, dim, chain=None, indep=False):
+    """fp32 sum of a V along dim; indep: the terms' propagated errors are independent roundings (added in quadrature)"""
+    n = a.v.shape[dim]
+    s = a.v.sum(dim)
+    sq = (a.v * a.v).sum(dim)
+    pe = C_ACC * (a.e * a.e).sum(dim).sqrt() if indep else a.e.sum(dim)
+    if indep:
+        pe = torch.minimum(pe, a.e.sum(dim))
+    return V(s, _acc(s, sq, n, n if chain is None else chain) + pe)
+
+
+# ---------------------------------------------------------------------------------------------------------------- convolution
+
+def _rows(t, n, ld):
+    return t.reshape(-1)[: n * ld].view(n, ld)
+
+
+def _chunks(B, per_image):
+    step = max(1, CHUNK_ELEMS // max(per_image, 1))
+    return [(b0, min(B, b0 + step)) for b0 in range(0, B, step)]
+
+
+def _core(X, W4, g):
+    """X (b, Cin, Hin, Win) fp64, W4 (rows, Cin, 3, 3) or (rows, Cin) fp64 -> (b, rows, Hout, Wout)"""
+    mode = g["mode"]
+    if mode == CONV_1X1:
+        return torch.einsum("bchw,oc->bohw", X, W4)
+    if mode == CONV_S1:
+        return F.conv2d(X, W4, padding=1)
+    if mode == CONV_S2:
+        return F.conv2d(X, W4, stride=2, padding=1)
+    if mode == CONV_UP:
+        return F.conv2d(F.interpolate(X, scale_factor=2.0, mode="nearest"), W4, padding=1)
+    if mode == CONV_TS2:
+        op = (g["Hout"] - (2 * g["Hin"] - 1), g["Wout"] - (2 * g["Win"] - 1))
+        return F.conv_transpose2d(X, W4.permute(1, 0, 2, 3), stride=2, padding=1, output_padding=op)
+    raise ValueError(mode)
+
+
+def _weights(w, g):
+    taps = 1 if g["mode"] == CONV_1X1 else 9
+    rows = min(g["wrows"], g["Cout"])
+    Wt = w.reshape(-1)[: g["wrows"] * taps * g["Cin"]].view(g["wrows"], taps, g["Cin"])[:rows].to(D)
+    return Wt[:, 0] if taps == 1 else Wt.view(rows, 3, 3, -1).permute(0, 3, 1, 2)
+
+
+def conv_sum(x, w, g, bias=None, kvalid=0, images=None):
+    """The fp32 accumulator of c2w_conv_forward (+ bias) as V rows (npix, Cout); rows >= wrows are exact zeros.  images: (b0, b1)."""
+    B, Hin, Win, Cin, Hout, Wout, Cout = (g[k] for k in ("B", "Hin", "Win", "Cin", "Hout", "Wout", "Cout"))
+    taps = 1 if g["mode"] == CONV_1X1 else 9
+    b0, b1 = images or (0, B)
+    X = _rows(x, B * Hin * Win, Cin).view(B, Hin, Win, Cin)[b0:b1]
+    W4 = _weights(w, g)
+    rows = W4.shape[0]
+    K = taps * (kvalid or Cin)
+    out_v = torch.zeros((b1 - b0, Hout, Wout, Cout), dtype=D, device=x.device)
+    out_e = torch.zeros_like(out_v)
+    per = max(Hin * Win * Cin, Hout * Wout * Cin) * (9 if taps == 9 else 1) * (4 if g["mode"] == CONV_UP else 1)
+    for c0, c1 in _chunks(b1 - b0, per):
+        Xc = X[c0:c1].to(D).permute(0, 3, 1, 2)
+        v = _core(Xc, W4, g)
+        sq = _core(Xc * Xc, W4 * W4, g)
+        e = _acc(v, sq, K, K)
+        out_v[c0:c1, :, :, :rows] = v.permute(0, 2, 3, 1)
+        out_e[c0:c1, :, :, :rows] = e.permute(0, 2, 3, 1)
+    return add_bias(V(out_v.view(-1, Cout), out_e.view(-1, Cout)), bias, g)
+
+
+def _mrows(m, npix, HW, C, ldm):
+    if m is None:
+        return None
+    if ldm == 0:
+        return m.reshape(-1)[:C].to(D).view(1, C).expand(npix, C)
+    nb = npix // HW
+    return torch.as_strided(m.reshape(-1), (nb, C), (ldm, 1)).to(D).repeat_interleave(HW, dim=0)
+
+
+def _ln_stats(u, C, eps, unbiased):
+    """ln_fwd_kernel / ln_bwd_kernel / finish_lnf: mean, centred rows, 1/sigma (pointwise.hip:44-60, 118-137)"""
+    mean = _scale(_sum(u, 1), 1.0 / C)
+    c = _sub(u, V(mean.v.unsqueeze(1).expand_as(u.v), mean.e.unsqueeze(1).expand_as(u.v)))
+    q = _sum(_mul(c, c), 1)
+    var = _scale(q, 1.0 / (C - 1 if unbiased else C))
+    rs = _rsqrt(_add(var, float(np.float32(eps))))
+    return mean, c, rs
+
+
+def _bc(a, like):
+    return V(a.v.unsqueeze(1).expand_as(like.v), a.e.unsqueeze(1).expand_as(like.v))
+
+
+def layernorm(u, C, eps, unbiased, dtype):
+    """LN of V rows u (already + m): returns (y rounded to T, rstd V, mean V)"""
+    mean, c, rs = _ln_stats(u, C, eps, unbiased)
+    return _rnd(_mul(c, _bc(rs, c)), dtype), rs, mean
+
+
+def ln_backward_rows(g, u, C, eps, unbiased):
+    """the fp32 rows o = (g - mean(g) - xhat * sum(g xhat)/den) * rs of ln_bwd_kernel (pointwise.hip:118-160), g and u as V rows"""
+    mean, c, rs = _ln_stats(u, C, eps, unbiased)
+    xh = _mul(c, _bc(rs, c))
+    gmean = _scale(_sum(g, 1), 1.0 / C)
+    dot = _scale(_sum(_mul(g, xh), 1), 1.0 / (C - 1 if unbiased else C))
+    o = _mul(_sub(_sub(g, _bc(gmean, g)), _mul(xh, _bc(dot, xh))), _bc(rs, g))
+    return o
+
+
+def dm_sums(o, npix, HW, C, ldm):
+    """dm[b] (or dm) += the pixel sum of the rows o: per image with ldm, all pixels into one row without"""
+    if ldm:
+        return _sum(o.view(npix // HW, HW, C), 1, indep=True)
+    return _sum(o, 0, indep=True).view(1, C)
+
+
+def add_bias(acc, bias, g):
+    """the fp32 bias add of the epilogue (conv_epilogue.h:46) onto an accumulator V from conv_sum(..., bias=None)"""
+    if bias is None:
+        return acc
+    rows = min(g["wrows"], g["Cout"])
+    bv = torch.zeros(g["Cout"], dtype=D, device=acc.v.device)
+    bv[:rows] = bias.reshape(-1)[:rows].to(D)
+    s = _add(acc, V(bv.expand_as(acc.v)))
+    live = torch.arange(g["Cout"], device=acc.v.device) < rows
+    return V(torch.where(live, s.v, acc.v), torch.where(live, s.e, acc.e))
+
+
+def conv(x, w, g, dtype, bias=None, act=ACT_NONE, res=None, mul=None, mulmode=MUL_PLAIN, y2=False, pool2=False, lnf=None, ln=None,
+         kvalid=0, pre=None):
+    """c2w_conv_forward's outputs as V: dict with 'y' (rows (npix or npix/4, Cout)), and where asked 'y2', 'hn' + 'rstd' (lnf), 'dm' (ln).
+    lnf / ln: dict(m, ldm, eps, unbiased[, x]) as in ops.conv (ln['x'] = the LayerNorm input rows, recomputed statistics).
+    pre: conv_sum(x, w, g, kvalid=...) computed once for several epilogues of the same operands."""
+    T = _T(dtype)
+    B, Hout, Wout, Cout, ldy = g["B"], g["Hout"], g["Wout"], g["Cout"], g["ldy"]
+    npix, HW = B * Hout * Wout, Hout * Wout
+    a = add_bias(pre if pre is not None else conv_sum(x, w, g, None, kvalid), bias, g)
+    if act == ACT_SILU:
+        a = _silu(a)
+    a = _rnd(a, T)  # the LDS tile (conv_epilogue.h:53; fp32 tiles :51)
+    out = {}
+    if ln is not None:  # fused LayerNorm backward: g = the stored tile, u = ln_x + m (conv_epilogue.h:256-283)
+        u = exact(_rows(ln["x"], npix, ldy)[:, :Cout])
+        m = _mrows(ln.get("m"), npix, HW, Cout, ln.get("ldm", 0))
+        if m is not None:
+            u = _add(u, V(m))
+        o = ln_backward_rows(a, u, Cout, ln["eps"], ln["unbiased"])
+        out["dm"] = dm_sums(o, npix, HW, Cout, ln.get("ldm", 0))
+        if res is not None:
+            o = _add(o, exact(_rows(res, npix, ldy)[:, :Cout]))
+        out["y"] = _rnd(o, T)
+        return out
+    f = a
+    if mul is not None or res is not None:
+        if mul is not None:
+            mm = exact(_rows(mul, npix, ldy)[:, :Cout])
+            f = _mul(f, _dsilu(mm) if mulmode == MUL_DSILU else mm)
+        if res is not None:
+            f = _add(f, exact(_rows(res, npix, ldy)[:, :Cout]))
+        f = _rnd(f, T)  # conv_epilogue.h:549
+    if act == ACT_SILU_PAIR:
+        out["y"], out["y2"] = _rnd(_silu(f), T), _rnd(_dsilu(f), T)
+        return out
+    if pool2:
+        q = f.view(B, Hout // 2, 2, Wout // 2, 2, Cout)
+        p = _add(_add(_add(V(q.v[:, :, 0, :, 0], q.e[:, :, 0, :, 0]), V(q.v[:, :, 0, :, 1], q.e[:, :, 0, :, 1])),
+                      V(q.v[:, :, 1, :, 0], q.e[:, :, 1, :, 0])), V(q.v[:, :, 1, :, 1], q.e[:, :, 1, :, 1]))
+        out["y"] = _rnd(p, T).view(npix // 4, Cout)
+        return out
+    out["y"] = f
+    if y2:
+        out["y2"] = _rnd(_silu(f), T)
+    if lnf is not None:  # LN of the stored result (+ the consumer's modulation): conv_epilogue.h:429-455
+        m = _mrows(lnf.get("m"), npix, HW, Cout, lnf.get("ldm", 0))
+        u = _add(f, V(m)) if m is not None else f
+        out["hn"], out["rstd"], _ = layernorm(u, Cout, lnf["eps"], lnf["unbiased"], T)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ weight gradient
+
+def _unfold(X, g):
+    """(b, Cin, Hin, Win) -> (b, taps * Cin, Hout * Wout) patches in the [tap][ci] order of the weight rows"""
+    mode = g["mode"]
+    b, Cin = X.shape[:2]
+    if mode == CONV_1X1:
+        return X.reshape(b, Cin, -1)
+    if mode == CONV_UP:
+        X = F.interpolate(X, scale_factor=2.0, mode="nearest")
+    P = F.unfold(X, 3, padding=1, stride=2 if mode == CONV_S2 else 1)  # (b, Cin * 9, L) in [ci][tap] order
+    return P.view(b, Cin, 9, -1).transpose(1, 2).reshape(b, 9 * Cin, -1)
+
+
+def wgrad(x, dy, g, images=None, pixels=None):
+    """c2w_conv_wgrad: (dW V rows (Cout, taps * Cin), dbias V (Cout,)) -- sums over all B * Hout * Wout pixels.
+    images = (b0, b1) and pixels = a boolean (Hout, Wout) mask restrict the sum (the planted defects)."""
+    B, Hin, Win, Cin, Hout, Wout, Cout, ldy = (g[k] for k in ("B", "Hin", "Win", "Cin", "Hout", "Wout", "Cout", "ldy"))
+    taps = 1 if g["mode"] == CONV_1X1 else 9
+    b0, b1 = images or (0, B)
+    X = _rows(x, B * Hin * Win, Cin).view(B, Hin, Win, Cin)
+    G = _rows(dy, B * Hout * Wout, ldy)[:, :Cout].view(B, Hout * Wout, Cout)
+    dw = torch.zeros((Cout, taps * Cin), dtype=D, device=x.device)
+    dw2 = torch.zeros_like(dw)
+    db = torch.zeros(Cout, dtype=D, device=x.device)
+    db2 = torch.zeros_like(db)
+    mask = None if pixels is None else pixels.reshape(-1).to(x.device)
+    per = Hout * Wout * Cin * taps * (4 if g["mode"] == CONV_UP else 1)
+    for c0, c1 in _chunks(b1 - b0, per):
+        Xc = X[b0 + c0:b0 + c1].to(D).permute(0, 3, 1, 2)
+        Gc = G[b0 + c0:b0 + c1].to(D)
+        if mask is not None:
+            Gc = Gc * mask.view(1, -1, 1)
+        P = _unfold(Xc, g)
+        dw += torch.einsum("bkl,blo->ok", P, Gc)
+        dw2 += torch.einsum("bkl,blo->ok", P * P, Gc * Gc)
+        db += Gc.sum((0, 1))
+        db2 += (Gc * Gc).sum((0, 1))
+    N = B * Hout * Wout
+    return V(dw, _acc(dw, dw2, N, N)), V(db, _acc(db, db2, N, N))
+
+
+# --------------------------------------------------------------------------------------------------------- pointwise kernels
+
+def ln_forward(x, m, npix, HW, C, ldm, eps, unbiased, dtype):
+    """ln_fwd_kernel: (y V rows, rstd V)"""
+    u = exact(_rows(x, npix, C))
+    mm = _mrows(m, npix, HW, C, ldm)
+    if mm is not None:
+        u = _add(u, V(mm))
+    y, rs, _ = layernorm(u, C, eps, unbiased, dtype)
+    return y, rs
+
+
+def ln_backward(dy, x, m, dres, npix, HW, C, ldm, eps, unbiased, dtype):
+    """ln_bwd_kernel: (dx V rows, dm V (images or 1, C))"""
+    u = exact(_rows(x, npix, C))
+    mm = _mrows(m, npix, HW, C, ldm)
+    if mm is not None:
+        u = _add(u, V(mm))
+    o = ln_backward_rows(exact(_rows(dy, npix, C)), u, C, eps, unbiased)
+    dm = dm_sums(o, npix, HW, C, ldm)
+    if dres is not None:
+        o = _add(o, exact(_rows(dres, npix, C)))
+    return _rnd(o, dtype), dm
+
+
+def colsum(a, rows, C, lda, dtype):
+    """colsum_kernel (pointwise.hip:200-232): per-thread row loop, the row groups in LDS, one atomic per block and channel"""
+    P = 4 if _T(dtype) == torch.float32 else 8
+    ngrp = 256 // min(C // P, 256)
+    chain = -(-2048 // ngrp) + ngrp + -(-rows // 2048)
+    A = _rows(a, rows, lda)[:, :C].to(D)
+    s, sq = A.sum(0), (A * A).sum(0)
+    return V(s, _acc(s, sq, rows, chain))
+
+
+def _loss_chain(n, nblk, per_atomic_blocks=4):
+    """a grid-stride loop of nblk blocks of 256 threads, a wave tree, one atomicAdd per wave (or per block) onto one address"""
+    per_thread = 2 * -(-n // (nblk * 256)) + 8
+    return per_thread + 6 + per_atomic_blocks * nblk
+
+
+def _nchw(eps, B, C, HW):
+    return eps.reshape(-1)[: B * C * HW].view(B, C, HW).permute(0, 2, 1).reshape(B * HW, C).to(D)
+
+
+def mse_loss_sum(y, eps, B, C, HW, ldc):
+    """the loss sum of c2w_mse_loss_grad (tiled kernel, pointwise.hip:538-582: at most 2048 blocks, one atomic per wave)"""
+    d = _rows(y, B * HW, ldc)[:, :C].to(D) - _nchw(eps, B, C, HW)
+    t = d * d
+    s, sq = t.sum(), (t * t).sum()
+    nblk = min(B * -(-HW // 64), 2048)
+    return V(s, _acc(s, sq, t.numel(), _loss_chain(t.numel(), nblk)))
+
+
+def mse_dy(y, eps, B, C, HW, ldc, gscale, dtype):
+    """dY rows of c2w_mse_loss_grad: (y - eps) * gscale rounded to T, padding channels exact zeros"""
+    d = _sub(exact(_rows(y, B * HW, ldc)[:, :C]), V(_nchw(eps, B, C, HW)))
+    o = _rnd(_scale(d, gscale), dtype)
+    z = torch.zeros((B * HW, ldc), dtype=D, device=y.device)
+    zv, ze = z.clone(), z.clone()
+    zv[:, :C], ze[:, :C] = o.v, o.e
+    return V(zv, ze)
+
+
+def sq_err_sum(y, eps, B, C, HW, ldc):
+    """the loss sum of sq_err_tiled_kernel (pointwise.hip:615-655) -- same grid rule as the loss tail"""
+    return mse_loss_sum(y, eps, B, C, HW, ldc)
+
+
+def fused_loss_sum(y, erows, C, lde, npix, workgroups):
+    """conv_patch3.hip:340-375: per-thread squares of (stored prediction - fp16 noise row), a wave tree, one atomic per workgroup"""
+    d = _rows(y, npix, y.shape[-1])[:, :C].to(D) - _rows(erows, npix, lde)[:, :C].to(D)
+    t = d * d
+    s, sq = t.sum(), (t * t).sum()
+    return V(s, _acc(s, sq, t.numel(), _loss_chain(t.numel(), workgroups, 1)))
+
+
+def sumsq(v, n):
+    """sampler.hip:76-81: grid_for(n, 256, 2048) blocks, a grid-stride loop, one atomic per wave"""
+    a = v.reshape(-1)[:n].to(D)
+    t = a * a
+    s, sq = t.sum(), (t * t).sum()
+    nblk = min(-(-n // 256), 2048)
+    return V(s, _acc(s, sq, n, _loss_chain(n, nblk)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the checks
+
+def _where(idx, layout):
+    """(image, row, column, channel) of a flat index into rows (B * H * W, C), and the regions it lies in"""
+    if not layout:
+        return f"flat index {idx}", []
+    B, H, W, C = layout["B"], layout["H"], layout["W"], layout["C"]
+    pix, c = divmod(idx, C)
+    b, r = divmod(pix, H * W)
+    h, w = divmod(r, W)
+    th, tw = layout.get("tile", (8, 16))
+    reg = []
+    if h in (0, H - 1) or w in (0, W - 1):
+        reg.append("border row/column")
+    if h % th in (0, th - 1) or w % tw in (0, tw - 1):
+        reg.append("tile seam")
+    ct = layout.get("ctile", 128)
+    if C % ct and c >= C // ct * ct:
+        reg.append("last partial channel tile")
+    if c >= layout.get("creal", C):
+        reg.append("padded channels")
+    return f"image {b}, row {h}, column {w}, channel {c}", reg or ["interior"]
+
+
+def ratio(got, ref, bound=None):
+    if bound is None:
+        ref, bound = ref
+    err = (got.to(D).reshape(ref.shape) - ref).abs()
+    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
+    return torch.where(torch.isnan(err), torch.full_like(err, math.inf), r)
+
+
+def assert_within(got, ref, bound=None, what="", layout=None):
+    """|got - ref| <= bound element by element; returns the largest err / bound (printed by the callers).
+    layout = dict(B, H, W, C[, tile, ctile, creal]) names the failing location for rows (B * H * W, C)."""
+    if isinstance(ref, V):
+        ref, bound = ref.v, ref.e
+    r = ratio(got, ref, bound).reshape(-1)
+    worst = r.max().item()
+    if not worst <= 1.0:
+        i = int(r.argmax().item())
+        loc, reg = _where(i, layout)
+        g = got.to(D).reshape(-1)[i].item()
+        raise AssertionError(f"{what}: err/bound {worst:.3g} at {loc} ({', '.join(reg)}): got {g:.6g}, fp64 {ref.reshape(-1)[i].item():.6g}, "
+                             f"bound {bound.reshape(-1)[i].item():.3g}; {int((r > 1).sum().item())} of {r.numel()} elements violate the bound")
+    return worst
+
+
+def assert_rejects(got_with_defect, ref, bound=None, what=""):
+    """the power check: a planted defect must push some element past its bound"""
+    if isinstance(ref, V):
+        ref, bound = ref.v, ref.e
+    worst = ratio(got_with_defect, ref, bound).max().item()
+    assert worst > 1.0, f"{what}: the bound does not see the planted defect (largest err/bound {worst:.3g})"
+    return worst
+
+
+def layout(g):
+    """assert_within's layout of a conv output's rows"""
+    return dict(B=g["B"], H=g["Hout"], W=g["Wout"], C=g["Cout"], creal=min(g["wrows"], g["Cout"]))
+
+
+def accumulated(prev, add):
+    """the fp32 destination of an accumulating call: prev (a tensor the kernel read, or a V) plus the call's result"""
+    return _add(prev if isinstance(prev, V) else exact(prev), add)
+
+
+def report(what, worst):
+    print(f"fp64 bound {what}: max err/bound {worst:.3e}")
+    return worst
+
+
+# --------------------------------------------------------------------------------------------------------- planted defects
+
+def border_mask(H, W, device=None):
+    m = torch.zeros(H, W, dtype=torch.bool, device=device)
+    m[0, :] = m[-1, :] = m[:, 0] = m[:, -1] = True
+    return m
+
+
+def tile_mask(H, W, h0=0, w0=0, th=8, tw=16, device=None):
+    m = torch.zeros(H, W, dtype=torch.bool, device=device)
+    m[h0:h0 + th, w0:w0 + tw] = True
+    return m
+
+
+def conv_term(x, w, g, image, channels, tap=None, pixels=None):
+    """rows (npix, Cout) fp64: the contribution of input channels `channels` (a slice) at one tap (None: all) of one image, limited to
+    the output pixels of `pixels` ((Hout, Wout) mask, None: all) -- subtracted from a kernel's output it plants a missing term"""
+    B, Hin, Win, Cin, Hout, Wout, Cout = (g[k] for k in ("B", "Hin", "Win", "Cin", "Hout", "Wout", "Cout"))
+    X = _rows(x, B * Hin * Win, Cin).view(B, Hin, Win, Cin)[image:image + 1].to(D).permute(0, 3, 1, 2)
+    W4 = _weights(w, g)
+    keep = torch.zeros(Cin, dtype=D, device=x.device)
+    keep[channels] = 1
+    if W4.dim() == 2:
+        W4 = W4 * keep
+    else:
+        W4 = W4 * keep.view(1, -1, 1, 1)
+        if tap is not None:
+            tm = torch.zeros(9, dtype=D, device=x.device)
+            tm[tap] = 1
+            W4 = W4 * tm.view(1, 1, 3, 3)
+    t = _core(X, W4, g)[0].permute(1, 2, 0)  # (Hout, Wout, rows)
+    if pixels is not None:
+        t = t * pixels.to(x.device).view(Hout, Wout, 1)
+    out = torch.zeros((B, Hout, Wout, Cout), dtype=D, device=x.device)
+    out[image, :, :, : t.shape[-1]] = t
+    return out.view(-1, Cout)

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import emu_ops as E
+import fp64_ref as R
 from climate2weather_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
@@ -145,6 +146,7 @@ def _run_conv_case(case, dt, ep):
         close(a, b, TOL[dt], f"{name} [{ep}] {what}")
     if want_lnb:
         close(dm, dm_ref, 1e-2, f"{name} [{ep}] modulation gradient")
+    _bound_conv_case(case, dt, ep, g, x, w, bias, res, y, kw_ref, extra, dm if want_lnb else None)
     if wrows < Cout:
         assert y[:, wrows:].abs().max().item() == 0.0, f"{name}: padded output rows must stay zero"
     if cin_real < Cin:  # C2wConvArgs.kvalid: the promise that the padding channels are zero lets the kernel skip K steps -- same bits
@@ -157,6 +159,34 @@ def _run_conv_case(case, dt, ep):
         assert torch.equal(y_k, y), f"{name} [{ep}]: kvalid = {cin_real} changed the result"
         if want_lnf:
             assert torch.equal(hn_k, hn)
+
+
+def _bound_conv_case(case, dt, ep, g, x, w, bias, res, y, kw_ref, extra, dm):
+    """the fp64 element-wise bound (tests/fp64_ref.py) next to the scale-relative checks of _run_conv_case, and its power checks"""
+    name, cin_real, Cin, Hout, Cout = case[0], case[8], g["Cin"], g["Hout"], g["Cout"]
+    parts = ep.split("+")
+    kw = {k: v for k, v in kw_ref.items() if k in ("act", "mul", "mulmode", "pool2")}
+    if "pair" in parts:
+        kw["act"] = ops.ACT_SILU_PAIR
+    if "lnf" in parts:
+        kw["lnf"] = kw_ref["lnf"]
+    if "lnb" in parts:
+        kw["ln"] = kw_ref["ln"]
+    ref = R.conv(x, w, g, dt, bias=bias, res=res, kvalid=cin_real if cin_real < Cin else 0, **kw)
+    lay = R.layout(g) if "pool" not in parts else dict(B=g["B"], H=Hout // 2, W=Hout // 2, C=Cout, tile=(4, 8))
+    what = f"{name} [{ep}] dt={dt}"
+    R.report(what, R.assert_within(y, ref["y"], what=what, layout=lay))
+    for a, _, w_ in extra:
+        key = "y2" if "silu'" in w_ else "hn"
+        R.report(f"{what} {w_}", R.assert_within(a, ref[key], what=f"{what} {w_}", layout=lay))
+    if dm is not None:
+        R.report(f"{what} modulation gradient", R.assert_within(dm[:, 32:32 + Cout], ref["dm"], what=f"{what} modulation gradient"))
+    if parts[-1] in ("bias", "plain", "res") and "pool" not in parts:  # outputs linear in the conv: the planted defects
+        if cin_real < Cin:  # the padded edge conv: channel cin_real - 1 (the 65th) missing at one tap of image 0
+            t = R.conv_term(x, w, g, 0, slice(cin_real - 1, cin_real), 4)
+            R.assert_rejects(y.double() - t, ref["y"], what=f"{what}: channel {cin_real - 1} missing at one tap")
+        t = R.conv_term(x, w, g, 0, slice(0, 1), 4, R.border_mask(Hout, Hout))
+        R.assert_rejects(y.double() - t, ref["y"], what=f"{what}: one tap of channel 0 missing at the border")
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])
@@ -249,6 +279,9 @@ def test_stride2_forward_on_parity_planes_against_the_gather_kernel(case, dt, mo
         torch.cuda.synchronize()
         close(y, y_ref, TOL[dt], f"{name} {sorted(kw)}")
         close(y, y_g, TOL[dt], f"{name} {sorted(kw)} against the gather kernel")
+        ref = R.conv(x, w, g, dt, bias=bias, **kw)
+        what = f"stride-2 parity planes {name} {sorted(kw)} dt={dt}"
+        R.report(what, R.assert_within(y, ref["y"], what=what, layout=dict(R.layout(g), tile=(8, 16 if Wout >= 16 else 8))))
 
 
 # (name, kernel family, mode, B, Hin, Cin, rows, ldy, cin_real)
@@ -296,6 +329,16 @@ def test_weight_gradient_kernels_at_the_bench_dispatch(case, dt):
     torch.cuda.synchronize()
     close(dw, dw_ref, TOL_W[dt], name)
     close(db, db_ref, TOL_W[dt], name + " bias")
+    nw = rows * 9 * Cin
+    rw, rb = R.wgrad(x, dy, g)
+    rw = rw.view(-1)
+    R.report(f"{name} dt={dt}", R.assert_within(dw[:nw], rw, what=name))
+    R.report(f"{name} dt={dt} bias", R.assert_within(db[:rows], rb, what=name + " bias"))
+    # power checks: one 8x16 output tile of image 0 removed from the pixel sum, and added twice
+    tw, tb = R.wgrad(x, dy, g, images=(0, 1), pixels=R.tile_mask(Hout, Hout, tw=min(16, Hout)))
+    for sgn in (-1.0, 1.0):
+        R.assert_rejects(dw[:nw].double() + sgn * tw.v.reshape(-1), rw, what=f"{name}: one tile x{1 + sgn:g}")
+        R.assert_rejects(db[:rows].double() + sgn * tb.v, rb, what=f"{name} bias: one tile x{1 + sgn:g}")
     assert dw[-64:].abs().max().item() == 0.0 and db[rows:].abs().max().item() == 0.0
     if cin_real < Cin:
         assert dw[: rows * 9 * Cin].view(rows, 9, Cin)[:, :, cin_real:].abs().max().item() == 0.0
@@ -863,6 +906,13 @@ def test_split_k_convolution_for_underfilled_launches(case, epi, dt):
     y_ref = torch.empty_like(y0)
     E.conv(x, w, bias, y_ref, g, dt, **kw)
     close(outs[0], y_ref, 2e-5 if dt == F32 else TOL[dt], name + " / " + epi + ": split vs restatement")
+    ref = R.conv(x, w, g, dt, bias=bias, **kw)
+    what = f"split-K {name} / {epi} dt={dt}"
+    R.report(what, R.assert_within(outs[0], ref["y"], what=what, layout=dict(R.layout(g), tile=(8, 8 if pair else 16))))
+    if epi in ("plain", "bias+res"):  # power check: one K chunk (64 channels; 32 in fp32) of one output tile of image 0 missing
+        chunk = 32 if dt == F32 else 64
+        t = R.conv_term(x, w, g, 0, slice(0, chunk), None, R.tile_mask(H, H, tw=8 if pair else 16))
+        R.assert_rejects(outs[0].double() - t, ref["y"], what=what + ": one K chunk of one tile missing")
     with pytest.raises(_lib.C2wError):  # not the plan's answer
         ops.conv(x, w, bias, y, g, dt, splitk=(ws, ns + 1 if ns < 8 else 2), **kw)  # (scratch sized for the plan's answer; the count alone is refused)
     with pytest.raises(_lib.C2wError):  # scratch too small

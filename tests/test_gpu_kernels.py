@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import emu_ops as E
+import fp64_ref as R
 from climate2weather_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +96,7 @@ def test_conv_forward(case, dt, naive):
     bias = rnd((wrows,), F32, 3)
     res = rnd((B * Hout * Wout, ldy), dt, 4)
     mul = rnd((B * Hout * Wout, ldy), dt, 5)
+    pre = R.conv_sum(x, w, g)  # the fp64 reference's accumulator, shared by the five epilogues
     for variant in range(5):
         kw = [dict(), dict(act=ops.ACT_SILU), dict(res=res), dict(mul=mul, mulmode=ops.MUL_DSILU, res=res), dict()][variant]
         b = None if variant == 3 else bias
@@ -108,6 +110,14 @@ def test_conv_forward(case, dt, naive):
         close(y, y_ref, dt, f"conv mode={mode} variant={variant} naive={naive}")
         if variant == 4:
             close(y2, y2_ref, dt, f"conv second output mode={mode} naive={naive}")
+        what = f"conv mode={mode} dt={dt} variant={variant} naive={naive}"
+        ref = R.conv(x, w, g, dt, bias=b, y2=variant == 4, pre=pre, **kw)
+        R.report(what, R.assert_within(y[:, :Cout], ref["y"], what=what, layout=R.layout(g)))
+        if variant == 4:
+            R.report(what + " second output", R.assert_within(y2[:, :Cout], ref["y2"], what=what + " second output", layout=R.layout(g)))
+        if variant == 0:  # power check: one tap of input channel 0 missing at the border pixels of image 0
+            t = R.conv_term(x, w, g, 0, slice(0, 1), None if mode == ops.CONV_1X1 else 4, R.border_mask(Hout, Wout))
+            R.assert_rejects(y[:, :Cout].double() - t, ref["y"], what=what + ", planted missing border tap")
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])
@@ -127,6 +137,7 @@ def test_conv_16x16_tile_kernel_all_epilogues(dt):
     y_ref, y2_ref = y.clone(), y2.clone()
     variants = [dict(bias=bias), dict(bias=bias, act=ops.ACT_SILU), dict(bias=bias, res=res), dict(mul=mul, mulmode=ops.MUL_DSILU, res=res),
                 dict(mul=mul, mulmode=ops.MUL_PLAIN), dict(bias=bias, y2=True), dict(bias=bias, act=ops.ACT_SILU_PAIR, y2=True)]
+    pre = R.conv_sum(x, w, g)
     for kw in variants:
         kw = dict(kw)
         b = kw.pop("bias", None)
@@ -137,17 +148,28 @@ def test_conv_16x16_tile_kernel_all_epilogues(dt):
         close(y, y_ref, dt, f"16x16 tile kernel {sorted(kw)}")
         if two:
             close(y2, y2_ref, dt, f"16x16 tile kernel second output {sorted(kw)}")
+        ref = R.conv(x, w, g, dt, bias=b, y2=two, pre=pre, **kw)
+        R.report(f"16x16 tile {sorted(kw)}", R.assert_within(y, ref["y"], what=f"16x16 tile kernel {sorted(kw)}", layout=R.layout(g)))
+        if two:
+            R.report(f"16x16 tile second output {sorted(kw)}", R.assert_within(y2, ref["y2"], what=f"16x16 tile second output {sorted(kw)}",
+                                                                              layout=R.layout(g)))
     dm, dm_ref = torch.zeros_like(m), torch.zeros_like(m)
     ln = dict(x=mul, m=m.view(-1)[32:], ldm=C + 64, eps=1e-5, unbiased=True)
     ops.conv(x, w, None, y, g, dt, res=res, ln=dict(ln, dm=dm.view(-1)[32:]))
     E.conv(x, w, None, y_ref, g, dt, res=res, ln=dict(ln, dm=dm_ref.view(-1)[32:]))
     close(y, y_ref, dt, "16x16 tile kernel, fused LN backward")
     close(dm, dm_ref, dt, "16x16 tile kernel, fused LN backward dm", tol=1e-2)
+    ref = R.conv(x, w, g, dt, res=res, ln=ln, pre=pre)
+    R.report("16x16 tile fused LN backward", R.assert_within(y, ref["y"], what="16x16 tile kernel, fused LN backward", layout=R.layout(g)))
+    R.report("16x16 tile fused LN backward dm", R.assert_within(dm[:, 32:32 + C], ref["dm"], what="16x16 tile kernel, fused LN backward dm"))
     lnf = dict(m=m.view(-1)[32:], ldm=C + 64, eps=1e-5, unbiased=True)
     ops.conv(x, w, bias, y, g, dt, res=res, lnf=dict(lnf, y=y2))
     E.conv(x, w, bias, y_ref, g, dt, res=res, lnf=dict(lnf, y=y2_ref))
     close(y, y_ref, dt, "16x16 tile kernel next to fused LN forward")
     close(y2, y2_ref, dt, "16x16 tile kernel, fused LN forward output")
+    ref = R.conv(x, w, g, dt, bias=bias, res=res, lnf=lnf, pre=pre)
+    R.report("16x16 tile next to fused LN forward", R.assert_within(y, ref["y"], what="16x16 tile next to fused LN forward", layout=R.layout(g)))
+    R.report("16x16 tile fused LN forward output", R.assert_within(y2, ref["hn"], what="16x16 tile fused LN forward output", layout=R.layout(g)))
 
 
 @pytest.mark.parametrize("dt", [F32, BF16, F16])
@@ -168,6 +190,8 @@ def test_conv_with_pooled_output(shape, dt):
     ops.conv(x, w, None, yp, g, dt, pool2=True)
     E.conv(x, w, None, yp_ref, g, dt, pool2=True)
     close(yp, yp_ref, dt, "pooled conv output")
+    R.report(f"pooled conv output {shape} dt={dt}", R.assert_within(yp, R.conv(x, w, g, dt, pool2=True)["y"], what="pooled conv output",
+                                                                    layout=dict(B=B, H=H // 2, W=W // 2, C=Cout, tile=(4, 8))))
     full = torch.empty((B * H * W, Cout), dtype=TD[dt], device=dev())
     two = torch.empty_like(yp)
     ops.conv(x, w, None, full, g, dt)
@@ -198,11 +222,16 @@ def test_up_conv_on_the_16x16_tile_kernel_and_its_weight_gradient(dt):
     ops.conv(x, w, bias, y, g, dt, res=res)
     E.conv(x, w, bias, y_ref, g, dt, res=res)
     close(y, y_ref, dt, "up-conv + skip on the 16x16 tile kernel")
+    pre = R.conv_sum(x, w, g)
+    R.report("up-conv + skip", R.assert_within(y, R.conv(x, w, g, dt, bias=bias, res=res, pre=pre)["y"], what="up-conv + skip", layout=R.layout(g)))
     lnf = dict(m=m.view(-1)[32:], ldm=C + 64, eps=1e-5, unbiased=True)
     ops.conv(x, w, bias, y, g, dt, res=res, lnf=dict(lnf, y=y2))
     E.conv(x, w, bias, y_ref, g, dt, res=res, lnf=dict(lnf, y=y2_ref))
     close(y, y_ref, dt, "up-conv next to fused LN forward")
     close(y2, y2_ref, dt, "up-conv, fused LN forward output")
+    ref = R.conv(x, w, g, dt, bias=bias, res=res, lnf=lnf, pre=pre)
+    R.report("up-conv next to fused LN forward", R.assert_within(y, ref["y"], what="up-conv next to fused LN forward", layout=R.layout(g)))
+    R.report("up-conv fused LN forward output", R.assert_within(y2, ref["hn"], what="up-conv fused LN forward output", layout=R.layout(g)))
     dy = rnd((B * H * H, C), dt, 7)
     dw = torch.zeros(C * 9 * C, dtype=torch.float32, device=dev())
     db = torch.zeros(C, dtype=torch.float32, device=dev())
@@ -211,6 +240,9 @@ def test_up_conv_on_the_16x16_tile_kernel_and_its_weight_gradient(dt):
     E.conv_wgrad(x, dy, dw_ref, g, dt, dbias=db_ref)
     close(dw, dw_ref, dt, "up-conv weight gradient (halo patch from the low-resolution map)", tol=1e-2)
     close(db, db_ref, dt, "up-conv bias gradient", tol=1e-2)
+    rw, rb = R.wgrad(x, dy, g)
+    R.report("up-conv weight gradient", R.assert_within(dw, rw.view(-1), what="up-conv weight gradient"))
+    R.report("up-conv bias gradient", R.assert_within(db, rb, what="up-conv bias gradient"))
 
 
 @pytest.mark.parametrize("dt", [F32, BF16, F16])
@@ -232,12 +264,17 @@ def test_conv_silu_pair_outputs(case, dt, naive):
     torch.cuda.synchronize()
     close(y, y_ref, dt, "silu output")
     close(y2, y2_ref, dt, "silu' output")
+    ref = R.conv(x, w, g, dt, bias=bias, act=ops.ACT_SILU_PAIR)
+    R.report(f"silu pair {case} dt={dt}", R.assert_within(y[:, :Cout], ref["y"], what="silu output", layout=R.layout(g)))
+    R.report(f"silu pair second {case} dt={dt}", R.assert_within(y2[:, :Cout], ref["y2"], what="silu' output", layout=R.layout(g)))
     dx, dx_ref = torch.empty_like(y), torch.empty_like(y)
     wT = rnd((Cout, 9, Cout), dt, 4, scale=1.0 / math.sqrt(9 * Cout))
     gd = geom(B, Hin, Win, ldy, Hin, Win, Cout, ldy, Cout, mode)
     ops.conv(y, wT, None, dx, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN, naive=naive)
     E.conv(y, wT, None, dx_ref, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN)
     close(dx, dx_ref, dt, "plain multiplier epilogue")
+    R.report(f"plain multiplier {case} dt={dt}", R.assert_within(dx[:, :Cout], R.conv(y, wT, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN)["y"],
+                                                                 what="plain multiplier epilogue", layout=R.layout(gd)))
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])
@@ -265,6 +302,9 @@ def test_conv_with_fused_ln_forward_output(B, H, W, Cin, per_sample, use_res, un
         torch.cuda.synchronize()
         close(y, y_ref, dt, "conv output next to the fused LN")
         close(hn, hn_ref, dt, "fused LN forward output")
+        ref = R.conv(x, w, g, dt, bias=bias, res=res, lnf=lnf)
+        R.report("conv next to the fused LN", R.assert_within(y, ref["y"], what="conv output next to the fused LN", layout=R.layout(g)))
+        R.report("fused LN forward output", R.assert_within(hn, ref["hn"], what="fused LN forward output", layout=R.layout(g)))
         # ... and, asked for, every pixel row's 1/sigma (C2wConvArgs.lnf_rstd), with the other outputs unchanged bit for bit
         rstd = torch.full((npix + 8,), -1.0, dtype=torch.float32, device=dev())
         rstd_ref = rstd.clone()
@@ -274,6 +314,7 @@ def test_conv_with_fused_ln_forward_output(B, H, W, Cin, per_sample, use_res, un
         torch.cuda.synchronize()
         assert torch.equal(y2_, y) and torch.equal(hn2_, hn)
         close(rstd[:npix], rstd_ref[:npix], dt, "per-pixel 1/sigma of the fused LN", tol=2e-3)
+        R.report("fused LN 1/sigma", R.assert_within(rstd[:npix], ref["rstd"], what="per-pixel 1/sigma of the fused LN"))
         assert (rstd[npix:] == -1.0).all()
 
 
@@ -305,6 +346,10 @@ def test_conv_with_fused_ln_backward(B, H, W, Cin, per_sample, unbiased, dt):
     torch.cuda.synchronize()
     close(y, y_ref, dt, "fused ln bwd dx")
     close(dm, dm_ref, dt, "fused ln bwd dm", tol=1e-2)
+    pre = R.conv_sum(x, w, g)
+    ref = R.conv(x, w, g, dt, res=res, ln=ln, pre=pre)
+    R.report("fused ln bwd dx", R.assert_within(y, ref["y"], what="fused ln bwd dx", layout=R.layout(g)))
+    R.report("fused ln bwd dm", R.assert_within(dm[:, 32:32 + C], ref["dm"], what="fused ln bwd dm"))
     # the same with the statistics the forward kept (C2wConvArgs.ln_rstd): ln_x = the normalised rows, ln_rstd their 1/sigma
     xm = lnx.float() + E._mrows(m.view(-1)[32:], npix, H * W, C, ldm)
     rs = (xm.var(dim=1, unbiased=unbiased) + 1e-5).rsqrt()
@@ -322,6 +367,8 @@ def test_conv_with_fused_ln_backward(B, H, W, Cin, per_sample, unbiased, dt):
     ops.conv(x, w, None, y, g, dt, ln=dict(x=lnx, eps=1e-5, unbiased=unbiased))
     E.conv(x, w, None, y_ref, g, dt, ln=dict(x=lnx, eps=1e-5, unbiased=unbiased))
     close(y, y_ref, dt, "fused ln bwd dx (no m, no res)")
+    ref = R.conv(x, w, g, dt, ln=dict(x=lnx, eps=1e-5, unbiased=unbiased), pre=pre)
+    R.report("fused ln bwd dx (no m, no res)", R.assert_within(y, ref["y"], what="fused ln bwd dx (no m, no res)", layout=R.layout(g)))
 
 
 @pytest.mark.parametrize("dt", [F32, BF16, F16])
@@ -354,16 +401,24 @@ def test_conv_wgrad(case, dt, force_gather, monkeypatch):
     assert 0 <= need <= ops.WORKSPACE_BYTES
     close(dw, dw_ref, dt, f"wgrad mode={mode}", tol=1e-4 if dt == F32 else 1e-2)
     close(db, db_ref, dt, f"wgrad bias mode={mode}", tol=1e-4 if dt == F32 else 1e-2)
+    nw = Cw * taps * Cin
+    rw, rb = R.wgrad(x, dy, g)
+    rw = rw.view(-1)
+    what = f"wgrad {case} dt={dt} {force_gather}"
+    R.report(what, R.assert_within(dw[:nw], rw, what=what))
+    R.report(what + " bias", R.assert_within(db[:Cw], rb, what=what + " bias"))
     assert db[Cw:].abs().max().item() == 0.0
     assert dw[-64:].abs().max().item() == 0.0  # nothing written past the tensor
     # accumulation semantics: a second call adds
     ops.conv_wgrad(x, dy, dw, g, dt, workspace=ws)
     close(dw, 2 * dw_ref, dt, "wgrad accumulate", tol=1e-4 if dt == F32 else 1e-2)
+    R.report(what + " accumulate", R.assert_within(dw[:nw], R.accumulated(rw, rw), what=what + " accumulate"))
     if ws is not None and need > 0:  # a buffer smaller than the launch needs is not used: same result through atomics
         small = torch.empty(max(need // 4 - 4, 4), dtype=torch.float32, device=dev())
         dw2 = torch.zeros_like(dw)
         ops.conv_wgrad(x, dy, dw2, g, dt, workspace=small)
         close(dw2, dw_ref, dt, "wgrad with an undersized workspace", tol=1e-4 if dt == F32 else 1e-2)
+        R.report(what + " undersized workspace", R.assert_within(dw2[:nw], rw, what=what + " undersized workspace"))
 
 
 GROUP_CASES = [
@@ -409,6 +464,12 @@ def test_conv_wgrad_grouped(case, dt):
         emu = pre[i].clone()
         E.conv_wgrad(xs[i], dys[i], emu, g, dt)
         close(dws[i], emu, dt, f"grouped wgrad layer {i} vs restatement", tol=1e-4 if dt == F32 else 1e-2)
+        nw = Cout * taps * Cin
+        rw, rb = R.wgrad(xs[i], dys[i], g)
+        what = f"grouped wgrad {case} dt={dt} layer {i}"
+        R.report(what, R.assert_within(dws[i][:nw], R.accumulated(pre[i][:nw], rw.view(-1)), what=what))
+        if i % 2 == 0:
+            R.report(what + " bias", R.assert_within(dbs[i][:Cout], rb, what=what + " bias"))
         close(dws[i], dw_ref, dt, f"grouped wgrad layer {i} vs single launch", tol=1e-5 if dt == F32 else 2e-3)
         if i % 2 == 0:
             close(dbs[i], db_ref, dt, f"grouped wgrad bias {i}", tol=1e-4 if dt == F32 else 1e-2)
@@ -443,6 +504,7 @@ def test_layernorm_fwd_bwd(shape, dt):
         ops.ln_forward(x, mm, y, npix, HW, C, ldm, 1e-5, True, dt)
         E.ln_forward(x, mm, y_ref, npix, HW, C, ldm, 1e-5, True, dt)
         close(y, y_ref, dt, "ln fwd")
+        R.report(f"ln fwd {shape} dt={dt}", R.assert_within(y, R.ln_forward(x, mm, npix, HW, C, ldm, 1e-5, True, dt)[0], what="ln fwd"))
         dy = rnd((npix, C), dt, 3)
         dres = rnd((npix, C), dt, 4)
         dx, dx_ref = torch.empty_like(x), torch.empty_like(x)
@@ -453,6 +515,10 @@ def test_layernorm_fwd_bwd(shape, dt):
         close(dx, dx_ref, dt, "ln bwd dx")
         if use_m:
             close(dm, dm_ref, dt, "ln bwd dm", tol=1e-4 if dt == F32 else 1e-2)
+        rdx, rdm = R.ln_backward(dy, x, mm, dres, npix, HW, C, ldm, 1e-5, True, dt)
+        R.report(f"ln bwd dx {shape} dt={dt}", R.assert_within(dx, rdx, what="ln bwd dx"))
+        if use_m:
+            R.report(f"ln bwd dm {shape} dt={dt}", R.assert_within(dm[:, 32:32 + C], rdm, what="ln bwd dm"))
     # biased variant switch
     y = torch.empty_like(x)
     y_ref = torch.empty_like(x)
@@ -855,6 +921,10 @@ def test_conv_center_vs_emulation(dt, B, H, W, Cin, wrows, r0, nr):
     torch.cuda.synchronize()
     assert torch.equal(out[:, nr:].cpu(), ref_cpu[:, nr:])  # nothing written outside the kept planes
     close(out[:, :nr].cpu(), ref_cpu[:, :nr], dt, "conv_center")
+    gc = geom(B, H, W, Cin, H, W, nr, nr, nr, ops.CONV_S1)
+    rc = R._rnd(R.conv_sum(x, w.view(wrows, 9, Cin)[r0:r0 + nr], gc, bias[r0:r0 + nr]), TD[dt]).view(B, H, W, nr)
+    rc = R.V(rc.v.permute(0, 3, 1, 2), rc.e.permute(0, 3, 1, 2))
+    R.report(f"conv_center dt={dt}", R.assert_within(out[:, :nr], rc, what="conv_center"))
     # the same rows out of the full convolution agree to the rounding of the compute type (different summation order)
     ldy = 128
     y = torch.zeros((B * H * W, ldy), dtype=TD[dt], device=dev())
