@@ -1,4 +1,4 @@
-"""Float64 references of the conv, weight-gradient, LayerNorm and reduction kernels, each with an element-wise error bound.
+"""Float64 references of the conv, weight-gradient, LayerNorm, reduction and attention kernels, each with an element-wise error bound.
 
 Every function takes the kernel's own (storage-typed) operands, computes the exact operation in torch.float64 with torch's own ops on
 the operands' device (F.conv2d, F.conv_transpose2d, F.interpolate, F.unfold, einsum; chunked by image) and returns V(ref, bound): two
@@ -34,6 +34,15 @@ LayerNorm backward reads the conv tile as stored (:256), restates ln_bwd_kernel'
 dm receives the fp32 rows before the residual (:283, :362).  LayerNorm (pointwise.hip:24-72, 80-195): u = x + m, mean, c = u - mean,
 q = sum c^2, rs = 1/sqrt(q/den + eps), out = c rs -- the statistics' errors propagate through these same rules, so (x - mean) * rstd
 carries the error of the mean in c and the error of q in rs.
+
+Attention (attention.hip, attention_mfma.hip): three routes with different arithmetic -- VALU (fp32 P / dP / dS, expf), T64 (one
+64-key block: P normalised then rounded to T, delta inside the kernel) and BLOCKS (online softmax: P rounded unnormalised, accumulators
+rescaled by alpha, delta from rowdot) -- each restated in attention_forward / attention_backward, whose docstrings cite every rounding
+counted.  Errors shared by a softmax row (lse, delta, the fp32 scale) are summed worst case over the keys, one-per-element roundings
+(the K-sums of S and dP, the exponentials, P and dS stored as T) in quadrature with C_ACC.  Two rules are local to that section: a
+value stored as T is off by at most u_T |v| + floor_T and never by more than |v| (_store_err); a K-sum's error never exceeds the
+classical n u32 sum |t_i| (_ksum_err).  The backward reference is the exact gradient at (qkv, do); the o / lse the kernel was given
+enter through their actual distance from the exact ones, so one function serves emulated and kernel-produced inputs.
 
 Bench-size cases: the reference is computed for every image and every reduction in full (no subset); the GPU tier's budget note is in
 tests/test_gpu_fp64_bounds.py.
@@ -449,12 +458,208 @@ def sumsq(v, n):
     return V(s, _acc(s, sq, n, _loss_chain(n, nblk)))
 
 
+# ------------------------------------------------------------------------------------------------------------------ attention
+
+VALU, T64, BLOCKS = "valu", "t64", "blocks"  # the three code paths of c2w_attention_forward / _backward
+KB = 64  # key block of the matrix-core kernels (attention_mfma.hip:23)
+
+
+def _qkv(qkv, B, T, C):
+    X = _rows(qkv, B * T, 3 * C).to(D).view(B, T, 3 * C)
+    return X[..., :C], X[..., C:2 * C], X[..., 2 * C:]
+
+
+def _quad(x, dim=-1):
+    """independent roundings along dim: C_ACC standard deviations, never more than the worst case"""
+    return torch.minimum(C_ACC * (x * x).sum(dim).sqrt(), x.sum(dim))
+
+
+def _mixv(W, M, coh, ind, n):
+    """out[b,t,c] = sum_s W[b,t,s] M[b,s,c] as an fp32 chain of n terms; coh / ind: absolute errors of W that add up coherently
+    (shared by the row: worst case) / independently (one rounding per element: quadrature)"""
+    v = torch.einsum("bts,bsc->btc", W, M)
+    Ma, M2 = M.abs(), M * M
+    worst = torch.einsum("bts,bsc->btc", ind, Ma)
+    e = torch.einsum("bts,bsc->btc", coh, Ma) + torch.minimum(C_ACC * torch.einsum("bts,bsc->btc", ind * ind, M2).clamp_min(0).sqrt(), worst)
+    return V(v, e + _acc(v, torch.einsum("bts,bsc->btc", W * W, M2), n, n))
+
+
+def _store_err(mag, T_):
+    """the rounding of a value of magnitude <= mag to T: u_T mag + floor_T, and never more than mag itself (zero is on the grid: what
+    rounds to zero is off by exactly its own size -- most weights of a peaked row, most dS s^2 of a 2^-12 gradient in fp16)"""
+    return torch.minimum(UT[T_] * mag + FLOOR[T_], mag)
+
+
+def attention_exact(qkv, B, T, C, do=None):
+    """the textbook operation in float64: dict of S (scaled scores), m, l, P, lse, o and, given do, dP, delta, dS, dq, dk, dv"""
+    q, k, v = _qkv(qkv, B, T, C)
+    s2 = 1.0 / math.sqrt(C)
+    S = torch.einsum("btc,bsc->bts", q, k) * s2
+    m = S.amax(-1, keepdim=True)
+    e = (S - m).exp()
+    l = e.sum(-1, keepdim=True)
+    P = e / l
+    x = dict(q=q, k=k, v=v, s2=s2, S=S, m=m, l=l, P=P, lse=(m + l.log()).squeeze(-1), o=torch.einsum("bts,bsc->btc", P, v))
+    if do is not None:
+        dO = _rows(do, B * T, C).to(D).view(B, T, C)
+        dP = torch.einsum("btc,bsc->bts", dO, v)
+        delta = (dO * x["o"]).sum(-1)
+        dS = P * (dP - delta.unsqueeze(-1))
+        x.update(dO=dO, dP=dP, delta=delta, dS=dS, dq=s2 * torch.einsum("bts,bsc->btc", dS, k),
+                 dk=s2 * torch.einsum("bts,btc->bsc", dS, q), dv=torch.einsum("bts,btc->bsc", P, dO))
+    return x
+
+
+def _ksum_err(total, sumsq, sumabs, n):
+    """an fp32 fma chain of n products: the module's _acc rule, and never more than the classical worst case n u32 sum |t_i| (short
+    chains of same-sign products -- logits that share an offset -- where C_ACC sqrt(n) exceeds n)"""
+    return torch.minimum(_acc(total, sumsq, n, n), n * U32 * (1 + n * U32) * sumabs)
+
+
+def _score_err(x, C):
+    """the fp32 K-sum of S before the scale (attention.hip:58, attention_mfma.hip:79/269: N = L = C), times s^2"""
+    raw = x["S"] / x["s2"]
+    q, k = x["q"], x["k"]
+    return _ksum_err(raw, torch.einsum("btc,bsc->bts", q * q, k * k), torch.einsum("btc,bsc->bts", q.abs(), k.abs()), C) * x["s2"]
+
+
+def _running_max(S, T):
+    """the running row maximum after each 64-key block (attention_mfma.hip:282, 291), spread over the block's keys: (B, T, T)"""
+    B = S.shape[0]
+    nb = T // KB
+    M = S.view(B, T, nb, KB).amax(-1).cummax(-1).values
+    return M, M.repeat_interleave(KB, dim=-1)
+
+
+def attention_forward(qkv, B, T, C, dtype, route, parts=None):
+    """c2w_attention_forward: (o V rows (B * T, C), lse V (B * T,)).
+
+    Weights.  S~ = s2~ * (fp32 K-sum): the sum's rounding is independent per (query, key); s2~ = 1.0f / sqrtf(C) is up to two roundings
+    from C^-1/2 and multiplies every score of the tensor alike: S~ - m~ = (1 + d)(S - m), an error d |S - m| in the exponent that is
+    shared (coherent) along the row.  m~, the row maximum of S~, is an arbitrary shift: softmax and lse = m~ + log sum exp(S~ - m~)
+    do not depend on it, so only the roundings of S~ s2~ (u32 |S|, attention.hip:62, attention_mfma.hip:142/279), of the subtraction
+    (u32 |x|, :121, mfma :149/287) and of the exponential count.  expf (attention.hip:121) is K_ULP ulps; __expf(x) (mfma :149, :283,
+    :287) is exp2(x log2 e): the product's rounding is an absolute error u32 |x| log2 e in the exponent of 2, i.e. a relative 2 u32 |x|
+    of the result once the constant's own rounding is counted.  The row sum is a chain of T / 16 + 8 additions (attention.hip:120-126;
+    mfma :150-152, :288-290) of positive terms; 1 / sum and the product (attention.hip:127-128, mfma :153-156, :313-316) 2 u32.
+    Routes:  VALU: P stays fp32 in LDS, o = fp32 chain over the T keys (attention.hip:79-95), one rounding to T (:95).
+    T64: P normalised, then rounded to T (mfma :156): an independent u_T P + floor_T per element; o rounded (:109).
+    BLOCKS: P_j = exp(s - running max) rounded to T unnormalised (:293) -- in units of the final weights u_T P + floor_T A / l, with
+    A = exp(running max - final max) <= 1 the later rescales; the row sum is taken from the fp32 values (:290); every later block
+    multiplies accumulator and sum by alpha = __expf(m_old - m_new) (:283, :290, :303): per transition 2 u32 |m_old - m_new| + K_ULP ulps
+    + two product roundings, shared by the row; o = oacc / l rounded (:313-316).  lse = m + logf / __logf(sum) (attention.hip:129,
+    mfma :157, :317): the sum's relative error, K_ULP ulps of |log sum| + 1, one addition."""
+    T_ = _T(dtype)
+    x = parts or attention_exact(qkv, B, T, C)
+    S, m, l, P, v = x["S"], x["m"], x["l"], x["P"], x["v"]
+    fast = route != VALU
+    if route == BLOCKS:
+        M, Mj = _running_max(S, T)
+        xa = (S - Mj).abs()
+        a = (M[..., :-1] - M[..., 1:]).abs()  # the transitions' exponents (the first block's alpha multiplies zeros)
+        ralpha = (U32 * (2 * a + K_ULP + 2)).sum(-1, keepdim=True)
+        A = (Mj - m).exp()
+    else:
+        xa = (S - m).abs()
+        ralpha = torch.zeros_like(m)
+    rc = 2 * U32 * (S - m).abs()
+    ri = _score_err(x, C) + U32 * S.abs() + U32 * xa * (3 if fast else 1) + K_ULP * U32
+    chain = T // 16 + 8
+    rel_l = (P * (rc + ri)).sum(-1, keepdim=True) + ralpha + C_ACC * U32 * (math.sqrt(T) * (P * P).sum(-1, keepdim=True).sqrt() + math.sqrt(chain))
+    coh = P * (rc + rel_l + ralpha + 2 * U32)
+    ind = P * ri
+    if route == T64:
+        ind = ind + _store_err(P + coh + ind, T_)
+    elif route == BLOCKS:  # the stored value is P l / A
+        ind = ind + _store_err((P + coh + ind) * l / A, T_) * A / l
+    o = _rnd(_mixv(P, v, coh, ind, T), T_)
+    lse = x["lse"]
+    e_lse = rel_l.squeeze(-1) + K_ULP * U32 * (l.squeeze(-1).log().abs() + 1) + U32 * (lse.abs() + m.squeeze(-1).abs())
+    return o.view(B * T, C), V(lse.reshape(-1), e_lse.reshape(-1))
+
+
+def rowdot(a, b, rows, C):
+    """rowdot_kernel (attention.hip:192-209): 16 lanes per row, each an fma chain over C / 16 elements, four shuffle additions"""
+    A, Bm = _rows(a, rows, C).to(D), _rows(b, rows, C).to(D)
+    t = A * Bm
+    s = t.sum(-1)
+    return V(s, _acc(s, (t * t).sum(-1), C, -(-C // 16) + 4))
+
+
+def attention_backward(qkv, o_in, do, lse_in, B, T, C, dtype, route, parts=None):
+    """c2w_attention_backward: dqkv V rows (B * T, 3 C); the reference is the exact gradient at (qkv, do); o_in / lse_in are the
+    tensors the kernel was given and enter through their ACTUAL distance from the exact o / lse.
+
+    P~ = exp(S~ s2~ - lse_in) (attention.hip:162/181 expf; mfma :202, :364 __expf): the exponent is off by |lse_in - lse| (shared by
+    the row), by 2 u32 |S| for s2~ (shared by the tensor: here nothing cancels it, S~ and lse are two large numbers when the logits
+    share an offset), and independently by the K-sum of S, u32 |S| (the product), u32 |S - lse| (the subtraction) and the exponential
+    (K_ULP ulps; __expf 2 u32 |S - lse| more).  dP = dO v^T is an fp32 K-sum over C (attention.hip:157/177, mfma :189, :400, :450).
+    delta: VALU and BLOCKS read rowdot(dO, o_in) (attention.hip:226, :259-260): its distance from the exact delta is the actual
+    |sum_c dO (o_in - o)| plus rowdot's own chain.  T64 sums P~ dP~ over the row's 64 keys in fp32 (mfma :203-205) and never reads o_in.
+    dS = P~ (dP~ - delta~): the errors of delta and lse are the same for every key of the row and add up coherently in dq_i
+    (s2 e sum_j P_ij |k_j|); so does, here, the part of P~'s error that s2~ causes.  VALU keeps P and dS fp32 in LDS and applies s2~
+    after the key sum (attention.hip:169, :187; 2 u32); the matrix-core routes round P and dS s2~ to T (mfma :209-210, :365-366), an
+    independent u_T |.| + floor_T per element, summed over T keys (dq, :220/:460) or T queries (dk :231/:415, dv :224/:411).
+    Each output is one more rounding to T (attention.hip:95, mfma :109, :349)."""
+    T_ = _T(dtype)
+    x = parts or attention_exact(qkv, B, T, C, do)
+    S, P, q, k, s2, dO, dP, delta, dS = (x[n] for n in ("S", "P", "q", "k", "s2", "dO", "dP", "delta", "dS"))
+    fast = route != VALU
+    dl = (_rows(lse_in, B, T).to(D) - x["lse"]).abs().unsqueeze(-1)
+    xa = (S - x["lse"].unsqueeze(-1)).abs()
+    rc = dl + 2 * U32 * S.abs()
+    ri = _score_err(x, C) + U32 * S.abs() + U32 * xa * (3 if fast else 1) + K_ULP * U32
+    eDP = _ksum_err(dP, torch.einsum("btc,bsc->bts", dO * dO, x["v"] ** 2), torch.einsum("btc,bsc->bts", dO.abs(), x["v"].abs()), C)
+    if route == T64:
+        dd = (P * dP.abs() * rc).sum(-1) + _quad(P * (dP.abs() * ri + eDP)) + _acc(delta, (P * P * dP * dP).sum(-1), T, 8)
+    else:
+        oin = _rows(o_in, B * T, C).to(D).view(B, T, C)
+        dd = (dO * (oin - x["o"])).sum(-1).abs() + rowdot(do, o_in, B * T, C).e.view(B, T)
+    dev = (dP - delta.unsqueeze(-1)).abs()
+    coh = P * (dev * rc + dd.unsqueeze(-1))
+    ind = P * (dev * ri + eDP) + 3 * U32 * dS.abs()
+    g = dS * s2
+    gc, gi = coh * s2 + 2 * U32 * g.abs(), ind * s2
+    Pc, Pi = P * rc, P * ri
+    if route != VALU:
+        gi = gi + _store_err(g.abs() + gc + gi, T_)
+        Pi = Pi + _store_err(P + Pc + Pi, T_)
+    tr = lambda t: t.transpose(1, 2)
+    dq = _rnd(_mixv(g, k, gc, gi, T), T_)
+    dk = _rnd(_mixv(tr(g), q, tr(gc), tr(gi), T), T_)
+    dv = _rnd(_mixv(tr(P), dO, tr(Pc), tr(Pi), T), T_)
+    return V(torch.cat((dq.v, dk.v, dv.v), -1).view(B * T, 3 * C), torch.cat((dq.e, dk.e, dv.e), -1).view(B * T, 3 * C))
+
+
+def attn_layout(B, T, C, sections):
+    """assert_within's layout of attention rows (B * T, len(sections) * C): sections 'o' or 'qkv'; () for lse / delta (B * T,)"""
+    return dict(attn=True, B=B, T=T, C=C, sections=tuple(sections))
+
+
+def _where_attn(idx, lay):
+    T, C, sec = lay["T"], lay["C"], lay["sections"]
+    row, col = divmod(idx, max(len(sec), 1) * C) if sec else (idx, 0)
+    b, t = divmod(row, T)
+    reg = [f"16-row strip {t // 16} of {-(-T // 16)}", f"64-token block {t // KB} of {-(-T // KB)}"]
+    if t < 16 or t >= (T - 1) // 16 * 16:
+        reg.append(("first" if t < 16 else "last") + " 16-row strip")
+    if t < KB or t >= (T - 1) // KB * KB:
+        reg.append(("first" if t < KB else "last") + " 64-key block")
+    if not sec:
+        return f"image {b}, token {t}", reg
+    s, c = divmod(col, C)
+    reg.append(("upper" if c // 16 >= (C // 16) // 2 else "lower") + " wave half's column tiles")
+    return f"image {b}, token {t}, section {sec[s]}, channel {c}", reg
+
+
 # ---------------------------------------------------------------------------------------------------------------- the checks
 
 def _where(idx, layout):
     """(image, row, column, channel) of a flat index into rows (B * H * W, C), and the regions it lies in"""
     if not layout:
         return f"flat index {idx}", []
+    if layout.get("attn"):
+        return _where_attn(idx, layout)
     B, H, W, C = layout["B"], layout["H"], layout["W"], layout["C"]
     pix, c = divmod(idx, C)
     b, r = divmod(pix, H * W)
@@ -483,7 +688,7 @@ def ratio(got, ref, bound=None):
 
 def assert_within(got, ref, bound=None, what="", layout=None):
     """|got - ref| <= bound element by element; returns the largest err / bound (printed by the callers).
-    layout = dict(B, H, W, C[, tile, ctile, creal]) names the failing location for rows (B * H * W, C)."""
+    layout = dict(B, H, W, C[, tile, ctile, creal]) names the failing location for rows (B * H * W, C); attn_layout(...) for attention rows."""
     if isinstance(ref, V):
         ref, bound = ref.v, ref.e
     r = ratio(got, ref, bound).reshape(-1)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import attention_cases as A
 import emu_ops as E
 import fp64_ref as R
 
@@ -285,3 +286,280 @@ def test_assert_within_names_the_place_and_region():
     assert "image 1, row 7, column 3, channel 170" in msg and "border row/column" in msg and "tile seam" in msg
     assert "last partial channel tile" in msg and "1 of" in msg
     assert R.assert_within(ref, ref, bound) == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------- attention
+ATT_TOL = {F32: 1e-4, BF16: 2e-2, F16: 4e-3}  # test_gpu_kernels.py:22, the tolerance of the check that stays beside the bound
+LOG2E = 1.4426950408889634
+
+
+def fast_exp(x):
+    """__expf: exp2 of the fp32 product x * log2(e)"""
+    return torch.exp2(x * np.float32(LOG2E))
+
+
+def _halves(out, prev, C, mutate):
+    """the two wave halves' column tiles of an output strip (attention_mfma.hip:164-165, 215, 388, 439); the mutant's upper half starts
+    one tile late, so tile ctm keeps the buffer's previous content"""
+    if mutate != "ctm+1":
+        return out
+    ctm = (C // 16) // 2
+    res = out.clone()
+    res[..., 16 * ctm:16 * ctm + 16] = prev
+    return res
+
+
+def restate_forward(qkv, B, T, C, dt, route, mutate=None, prev=7.0):
+    """fp32 / storage-typed restatement of the route's forward arithmetic -> (o rows of the storage type, lse fp32)"""
+    t = TD[dt]
+    q, k, v = qkv.float().view(B, T, 3 * C).split(C, dim=-1)
+    s2 = np.float32(1.0) / np.sqrt(np.float32(C))
+    S = torch.einsum("btc,bsc->bts", q, k) * s2
+    if route == R.VALU:  # attention.hip:113-132: fp32 P, expf
+        m = S.amax(-1, keepdim=True)
+        e = (S - m).exp()
+        l = e.sum(-1, keepdim=True)
+        o = torch.einsum("bts,bsc->btc", e * (1.0 / l), v)
+        return o.to(t).view(B * T, C), (m + l.log()).reshape(-1)
+    if route == R.T64:  # attention_mfma.hip:138-157: P normalised, then rounded
+        m = S.amax(-1, keepdim=True)
+        e = fast_exp(S - m)
+        l = e.sum(-1, keepdim=True)
+        P = (e * (1.0 / l)).to(t).float()
+        o = _halves(torch.einsum("bts,bsc->btc", P, v), prev, C, mutate)
+        return o.to(t).view(B * T, C), (m + l.log()).reshape(-1)
+    mrun = torch.full((B, T, 1), -math.inf)  # attention_mfma.hip:257-318: online softmax over 64-key blocks, P rounded unnormalised
+    lrun = torch.zeros((B, T, 1))
+    oacc = torch.zeros((B, T, C))
+    for j in range(T // 64):
+        s = S[..., 64 * j:64 * j + 64]
+        mx = torch.maximum(s.amax(-1, keepdim=True), mrun)
+        alpha = fast_exp(mrun - mx)
+        e = fast_exp(s - mx)
+        lrun = lrun * alpha + e.sum(-1, keepdim=True)
+        mrun = mx
+        if mutate != "no_alpha":
+            oacc = oacc * alpha
+        oacc = oacc + torch.einsum("bts,bsc->btc", e.to(t).float(), v[:, 64 * j:64 * j + 64])
+    return (oacc * (1.0 / lrun)).to(t).view(B * T, C), (mrun + lrun.log()).reshape(-1)
+
+
+def restate_backward(qkv, o_in, do, lse_in, B, T, C, dt, route, mutate=None, prev=7.0):
+    """fp32 / storage-typed restatement of the route's backward arithmetic -> (dqkv rows of the storage type, delta fp32 or None)"""
+    t = TD[dt]
+    q, k, v = qkv.float().view(B, T, 3 * C).split(C, dim=-1)
+    dO = do.float().view(B, T, C)
+    l = lse_in.float().view(B, T, 1)
+    s2 = np.float32(1.0) / np.sqrt(np.float32(C))
+    S = torch.einsum("btc,bsc->bts", q, k) * s2
+    dP = torch.einsum("btc,bsc->bts", dO, v)
+    if route == R.VALU:  # attention.hip:150-188: P, dS fp32, expf, s^2 after the sum
+        delta = (dO * o_in.float().view(B, T, C)).sum(-1, keepdim=True)
+        P = (S - l).exp()
+        dS = P * (dP - delta)
+        dq = torch.einsum("bts,bsc->btc", dS, k) * s2
+        dk = torch.einsum("bts,btc->bsc", dS, q) * s2
+        dv = torch.einsum("bts,btc->bsc", P, dO)
+        return torch.cat((dq, dk, dv), -1).to(t).view(B * T, 3 * C), delta.reshape(-1)
+    P = fast_exp(S - l)
+    if route == R.T64:  # attention_mfma.hip:196-212: delta = the fp32 row sum of P dP
+        delta = (P * dP).sum(-1, keepdim=True)
+    else:  # attention.hip:259-260, attention_mfma.hip:356-368: delta = rowdot(dO, o_in)
+        delta = (dO * o_in.float().view(B, T, C)).sum(-1, keepdim=True)
+    dS = (P * (dP - delta) * s2).to(t).float()
+    Pr = P.to(t).float()
+    dq = _halves(torch.einsum("bts,bsc->btc", dS, k), prev, C, mutate)
+    dk = _halves(torch.einsum("bts,btc->bsc", dS, q), prev, C, mutate)
+    dv = _halves(torch.einsum("bts,btc->bsc", Pr, dO), prev, C, mutate)
+    return torch.cat((dq, dk, dv), -1).to(t).view(B * T, 3 * C), None if route == R.T64 else delta.reshape(-1)
+
+
+# every regime on each route: T64, BLOCKS, VALU (every dtype; the tiny test network's attention level); then the kernels' edge widths
+# (ksm = 0; odd nks and ctm) and a T that is no multiple of 16
+ATT_CPU = [((3, 64, 512), r) for r in A.REGIMES] + [((2, 256, 512), r) for r in A.REGIMES] + [((2, 64, 16), r) for r in A.REGIMES]
+ATT_CPU += [(s, r) for s in ((2, 64, 32), (2, 192, 160), (3, 36, 64)) for r in ("randn", "peaked")]
+ATT_DEFECTS = {R.VALU: ("p_tile", "key", "delta_row", "ds_scale"), R.T64: ("p_tile", "key", "delta_row", "ds_scale"),
+               R.BLOCKS: ("p_tile", "key", "alpha", "dq_block", "delta_row", "ds_scale")}
+SECTION = A.SECTION
+
+
+def _att_dtypes(shape):
+    return [F32, BF16, F16] if A.attn_route(*shape, BF16) == R.VALU else [BF16, F16]
+
+
+def _vacuity(name, bound, scale, dt):
+    r = bound / (ATT_TOL[dt] * scale)
+    med, mx = r.median().item(), r.max().item()
+    print(f"    {name}: bound / (TOL x scale) median {med:.3f} max {mx:.3f}")
+    assert med < 1.0, f"{name}: the bound is wider than the old tolerance at a typical element (median {med:.3f})"
+    return med
+
+
+def check_regime_property(regime, qkv, B, T, C):
+    pmax, lmin, lmax, up, flat = A.attention_regime_stats(qkv, B, T, C)
+    ng = -(-T // A.attention_group(T))
+    print(f"    regime {regime}: mean row max {pmax:.3f}, |lse| in [{lmin:.1f}, {lmax:.1f}], groups raising the maximum {up:.2f} of {ng - 1}")
+    if regime in ("randn", "smallgrad"):
+        assert pmax < 0.6 and lmax <= 14
+    elif regime == "peaked":
+        assert pmax > 0.8
+    elif regime == "shifted":
+        assert 40 <= lmin and lmax <= 90 and pmax < 0.5
+    elif regime == "rising":
+        assert up >= 0.95 * (ng - 1)
+    elif regime == "falling":
+        assert up <= 0.05 * (ng - 1)
+    elif regime == "uniform":
+        assert abs(pmax - 1.0 / T) < 1e-12
+
+
+@pytest.mark.parametrize("shape,regime", ATT_CPU)
+def test_restatement_is_within_the_bound_attention(shape, regime):
+    """Each route's restatement is within the bound at every element, forward and backward (on the emulated and on its own forward
+    outputs); every planted defect is rejected; the regime has the property it is named for; the bound is tighter than the old
+    tolerance at the median element.  Measured medians of bound / (TOL x scale), the largest over the regimes run at the shape
+    (o / dq / dk / dv; TOL x scale = the old check's tolerance: max |o| forward, max |dqkv| backward):
+      (3, 64, 512)  T64    bf16 0.420 / 0.175 / 0.246 / 0.134 (uniform)   fp16 0.298 / 0.373 / 0.372 / 0.090 (uniform; dq, dk smallgrad)
+      (2, 256, 512) BLOCKS bf16 0.616 / 0.240 / 0.391 / 0.168 (uniform)   fp16 0.460 / 0.877 / 0.873 / 0.115 (uniform; dq, dk smallgrad)
+      (2, 64, 16)   VALU   fp32 0.646 / 0.444 / 0.442 / 0.087 (shifted)   bf16 0.065 / 0.036 / 0.056 / 0.017   fp16 0.049 / 0.029 / 0.039 / 0.012
+      (2, 64, 32)   T64    bf16 0.085 / 0.046 / 0.043 / 0.026             fp16 0.055 / 0.031 / 0.029 / 0.017
+      (2, 192, 160) BLOCKS bf16 0.068 / 0.072 / 0.068 / 0.037             fp16 0.062 / 0.048 / 0.046 / 0.024
+      (3, 36, 64)   VALU   fp32 0.616 / 0.061 / 0.053 / 0.048 (peaked)    bf16 0.040 / 0.020 / 0.018 / 0.007   fp16 0.038 / 0.013 / 0.012 / 0.005
+    The two largest: fp16 with do * 2^-12 at T = 256, where dS s^2 is rounded on the fp16 subnormal grid (2^-25 per element over 256
+    keys: the old tolerance is itself near that floor), and fp32 with |lse| about 50, where the K-sum of S costs C u32 |S| in the
+    exponent.  fp32 at a common offset is run at C = 16 only: at (3, 36, 64) the median for o is 1.62, the old fp32 tolerance of 1e-4 being
+    tighter there than the worst case of a 64-term same-sign K-sum.
+    The weakest rejection of a planted defect over all cases: p_tile 19.7, key 6.3, alpha 15.1, dq_block 43, delta_row 112,
+    ds_scale 534 times the bound."""
+    B, T, C = shape
+    for dt in _att_dtypes(shape):
+        if regime == "smallgrad" and dt != F16:
+            continue
+        route = A.attn_route(B, T, C, dt)
+        print(f"  {shape} {regime} dtype {dt} route {route}")
+        qkv, do = A.attention_inputs(regime, B, T, C, dt)
+        check_regime_property(regime, qkv, B, T, C)
+        x = R.attention_exact(qkv, B, T, C, do)
+        lo, ll, lq = R.attn_layout(B, T, C, "o"), R.attn_layout(B, T, C, ()), R.attn_layout(B, T, C, "qkv")
+        ro, rl = R.attention_forward(qkv, B, T, C, dt, route, parts=x)
+        o, lse = restate_forward(qkv, B, T, C, dt, route)
+        R.assert_within(o, ro, what="attention o", layout=lo)
+        R.assert_within(lse, rl, what="attention lse", layout=ll)
+        _vacuity("o", ro.e, ro.v.abs().max(), dt)
+        o_emu, lse_emu = x["o"].float().to(TD[dt]).view(B * T, C), x["lse"].float().reshape(-1)
+        gscale = torch.cat((x["dq"], x["dk"], x["dv"]), -1).abs().max()
+        for tag, oi, li in (("emulated", o_emu, lse_emu), ("own", o, lse)):
+            rg = R.attention_backward(qkv, oi, do, li, B, T, C, dt, route, parts=x)
+            assert (rg.e > 0).all()
+            dqkv, delta = restate_backward(qkv, oi, do, li, B, T, C, dt, route)
+            for s, i in SECTION.items():
+                sl = slice(i * C, (i + 1) * C)
+                R.assert_within(dqkv[:, sl], V_(rg, sl), what=f"attention d{s} ({tag} inputs)", layout=R.attn_layout(B, T, C, s))
+            R.assert_within(dqkv, rg, what=f"attention dqkv ({tag} inputs)", layout=lq)
+            if delta is not None:
+                R.assert_within(delta, R.rowdot(do, oi, B * T, C), what="delta", layout=ll)
+        for s, i in SECTION.items():
+            _vacuity("d" + s, rg.e[:, i * C:(i + 1) * C], gscale, dt)
+        for kind in ATT_DEFECTS[route]:
+            if kind == "alpha" and regime != "rising":
+                continue  # defined where the maximum grows across blocks
+            sec, term, where = A.attention_defect(kind, qkv, do, B, T, C, image=B - 1)
+            if sec == "o":
+                w = R.assert_rejects(o.double() + term, ro, what=f"{kind} ({where})")
+            else:
+                sl = slice(SECTION[sec] * C, (SECTION[sec] + 1) * C)
+                w = R.assert_rejects(dqkv[:, sl].double() + term, V_(rg, sl), what=f"{kind} ({where})")
+            print(f"    defect {kind} at {where}: err/bound {w:.3g}")
+        R.assert_rejects(A.stale_upper_half(dqkv, B, T, C, "v", image=B - 1), rg, what="upper half of dv stale")
+
+
+def V_(ref, sl):
+    return R.V(ref.v[:, sl], ref.e[:, sl])
+
+
+def test_attention_reference_equals_the_loop_and_float64_autograd():
+    B, T, C = 2, 5, 8
+    qkv, do = rnd((B * T, 3 * C), F32, 1, 1.5), rnd((B * T, C), F32, 2)
+    x = R.attention_exact(qkv, B, T, C, do)
+    Q = qkv.double().view(B, T, 3 * C).numpy()
+    o, lse = np.zeros((B, T, C)), np.zeros((B, T))
+    for b in range(B):
+        for i in range(T):
+            s = np.array([sum(Q[b, i, c] * Q[b, j, C + c] for c in range(C)) / math.sqrt(C) for j in range(T)])
+            w = np.exp(s - s.max())
+            lse[b, i] = s.max() + math.log(w.sum())
+            for c in range(C):
+                o[b, i, c] = sum(w[j] / w.sum() * Q[b, j, 2 * C + c] for j in range(T))
+    np.testing.assert_allclose(x["o"].numpy(), o, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(x["lse"].numpy(), lse, rtol=1e-12, atol=1e-12)
+    p = qkv.double().view(B, T, 3 * C).clone().requires_grad_(True)
+    q, k, v = p.split(C, dim=-1)
+    out = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(C), -1) @ v
+    (g,) = torch.autograd.grad(out, p, do.double().view(B, T, C))
+    for route, dt in ((R.VALU, F32), (R.VALU, BF16)):
+        ro, rl = R.attention_forward(qkv, B, T, C, dt, route)
+        rg = R.attention_backward(qkv, x["o"].float(), do, x["lse"].float(), B, T, C, dt, route)
+        np.testing.assert_allclose(ro.v.numpy(), o.reshape(B * T, C), rtol=1e-12, atol=1e-12)
+        np.testing.assert_allclose(rl.v.numpy(), lse.reshape(-1), rtol=1e-12, atol=1e-12)
+        np.testing.assert_allclose(rg.v.numpy(), g.reshape(B * T, 3 * C).numpy(), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(R.rowdot(do, x["o"].float(), B * T, C).v.numpy(), x["delta"].reshape(-1).numpy(), rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(R.rowdot(do, do, B * T, C).v.numpy(), (do.double() ** 2).sum(-1).numpy(), rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+def test_attention_bound_rejects_the_two_numerical_mutants(dt):
+    """the alpha multiply of attention_mfma.hip:303 skipped; the upper wave half's column tiles starting at ctm + 1 -- as switches of
+    the restatements; the failure message names the 64-token block / the wave half"""
+    B, T, C = 2, 256, 512
+    qkv, do = A.attention_inputs("rising", B, T, C, dt)
+    # only the queries of 64-token block 2 keep the rising direction; the others look down it: their maximum is in key block 0 and
+    # alpha = 1 afterwards, so the mutant's damage is confined to the rows of that block
+    X = qkv.double().view(B, T, 3 * C).clone()
+    others = torch.ones(T, dtype=torch.bool)
+    others[128:192] = False
+    X[:, others, :C] -= 2 * (2.0 * C ** 0.25) / math.sqrt(C)
+    qkv = X.view(B * T, 3 * C).to(TD[dt])
+    ro, _ = R.attention_forward(qkv, B, T, C, dt, R.BLOCKS)
+    lay = R.attn_layout(B, T, C, "o")
+    R.assert_within(restate_forward(qkv, B, T, C, dt, R.BLOCKS)[0], ro, what="unmutated", layout=lay)
+    o, _ = restate_forward(qkv, B, T, C, dt, R.BLOCKS, mutate="no_alpha")
+    with pytest.raises(AssertionError) as ei:
+        R.assert_within(o, ro, what="no alpha", layout=lay)
+    assert "64-token block 2 of 4" in str(ei.value) and "section o" in str(ei.value), str(ei.value)
+    rows = (R.ratio(o, ro) > 1).any(1).view(B, T)
+    assert rows[:, 128:192].all() and not rows[:, others].any()  # every row of that block in both images, and no other
+    B, T, C = 3, 64, 352  # odd ctm
+    for regime in ("randn", "peaked"):
+        qkv, do = A.attention_inputs(regime, B, T, C, dt)
+        x = R.attention_exact(qkv, B, T, C, do)
+        ro, rl = R.attention_forward(qkv, B, T, C, dt, R.T64, parts=x)
+        o, lse = restate_forward(qkv, B, T, C, dt, R.T64, mutate="ctm+1", prev=0.0)
+        with pytest.raises(AssertionError) as ei:
+            R.assert_within(o, ro, what="ctm + 1", layout=R.attn_layout(B, T, C, "o"))
+        assert "upper wave half's column tiles" in str(ei.value), str(ei.value)
+        cols = (R.ratio(o, ro) > 1).any(0).nonzero().reshape(-1)
+        assert cols.min() >= 16 * 11 and cols.max() < 16 * 12 and len(cols) == 16  # exactly the tile the mutant skips
+        rg = R.attention_backward(qkv, o, do, lse, B, T, C, dt, R.T64, parts=x)
+        good, _ = restate_backward(qkv, o, do, lse, B, T, C, dt, R.T64)
+        bad, _ = restate_backward(qkv, o, do, lse, B, T, C, dt, R.T64, mutate="ctm+1", prev=good[:, 3 * C - 16:].float().view(B, T, 16))
+        with pytest.raises(AssertionError) as ei:  # the previous content: the neighbouring tile's values, of the right size
+            R.assert_within(bad, rg, what="ctm + 1", layout=R.attn_layout(B, T, C, "qkv"))
+        assert "upper wave half's column tiles" in str(ei.value), str(ei.value)
+
+
+def test_attention_locator_names_token_section_strip_block_and_half():
+    B, T, C = 2, 256, 64
+    lay = R.attn_layout(B, T, C, "qkv")
+    ref = torch.zeros((B * T, 3 * C), dtype=torch.float64)
+    got = ref.clone()
+    got[1 * T + 250, 1 * C + 40] = 1.0
+    with pytest.raises(AssertionError) as ei:
+        R.assert_within(got, ref, torch.full_like(ref, 1e-3), "probe", layout=lay)
+    msg = str(ei.value)
+    assert "image 1, token 250, section k, channel 40" in msg and "last 16-row strip" in msg and "last 64-key block" in msg
+    assert "upper wave half's column tiles" in msg and "64-token block 3 of 4" in msg
+    got = torch.zeros(B * T, dtype=torch.float64)
+    got[3] = 1.0
+    with pytest.raises(AssertionError) as ei:
+        R.assert_within(got, torch.zeros_like(got), torch.full_like(got, 1e-3), "probe", layout=R.attn_layout(B, T, C, ()))
+    assert "image 0, token 3" in str(ei.value) and "first 16-row strip" in str(ei.value)

@@ -19,6 +19,7 @@ import os
 import pytest
 import torch
 
+import attention_cases as AB
 import emu_ops as E
 import fp64_ref as R
 from climate2weather_amd import _lib, ops
@@ -358,6 +359,7 @@ def test_attention_block_kernels_at_the_bench_batch(dt):
     ops.ln_forward(x, None, hl, npix, T, C, 0, 1e-5, True, dt)
     E.ln_forward(x, None, hl_ref, npix, T, C, 0, 1e-5, True, dt)
     close(hl, hl_ref, TOL[dt], "LayerNorm(512) forward")
+    R.report(f"attention block LayerNorm(512) forward dt={dt}", R.assert_within(hl, R.ln_forward(x, None, npix, T, C, 0, 1e-5, True, dt)[0], what="LayerNorm(512) forward"))
     for rows, use_res in ((3 * C, False), (C, True)):
         g = geom(npix, 1, 1, C, 1, 1, rows, rows, rows, K1)
         assert ops.conv_dispatch(g, dt) == GATHER
@@ -369,6 +371,8 @@ def test_attention_block_kernels_at_the_bench_batch(dt):
         ops.conv(hl_ref, w, bias, y, g, dt, res=res)
         E.conv(hl_ref, w, bias, y_ref, g, dt, res=res)
         close(y, y_ref, TOL[dt], f"1x1 512->{rows}")
+        R.report(f"attention block 1x1 512->{rows} dt={dt}",
+                 R.assert_within(y, R.conv(hl_ref, w, g, dt, bias=bias, res=res)["y"], what=f"1x1 512->{rows}", layout=R.layout(g)))
         dy = rnd((npix, rows), dt, 5)
         dw = torch.zeros(rows * C, dtype=torch.float32, device=dev())
         db = torch.zeros(rows, dtype=torch.float32, device=dev())
@@ -377,12 +381,19 @@ def test_attention_block_kernels_at_the_bench_batch(dt):
         E.conv_wgrad(hl_ref, dy, dw_ref, g, dt, dbias=db_ref)
         close(dw, dw_ref, TOL_W[dt], f"1x1 512->{rows} weight gradient")
         close(db, db_ref, TOL_W[dt], f"1x1 512->{rows} bias gradient")
+        rw, rb = R.wgrad(hl_ref, dy, g)
+        R.report(f"attention block 1x1 512->{rows} weight gradient dt={dt}",
+                 R.assert_within(dw, R.accumulated(torch.zeros_like(dw), rw.view(-1)), what=f"1x1 512->{rows} weight gradient"))
+        R.report(f"attention block 1x1 512->{rows} bias gradient dt={dt}",
+                 R.assert_within(db, R.accumulated(torch.zeros_like(db), rb), what=f"1x1 512->{rows} bias gradient"))
         gd = geom(npix, 1, 1, rows, 1, 1, C, C, C, K1)  # input gradient: the same GEMM over dy with the transposed weights
         wT = rnd((C, 1, rows), dt, 6, scale=1.0 / math.sqrt(rows))
         dx, dx_ref = torch.empty((npix, C), dtype=TD[dt], device=dev()), torch.empty((npix, C), dtype=TD[dt], device=dev())
         ops.conv(dy, wT, None, dx, gd, dt)
         E.conv(dy, wT, None, dx_ref, gd, dt)
         close(dx, dx_ref, TOL[dt], f"1x1 {rows}->512 input gradient")
+        R.report(f"attention block 1x1 {rows}->512 input gradient dt={dt}",
+                 R.assert_within(dx, R.conv(dy, wT, gd, dt)["y"], what=f"1x1 {rows}->512 input gradient", layout=R.layout(gd)))
     qkv = rnd((npix, 3 * C), dt, 7, scale=1.5)
     o, o_ref = torch.empty((npix, C), dtype=TD[dt], device=dev()), torch.empty((npix, C), dtype=TD[dt], device=dev())
     lse, lse_ref = torch.empty(npix, device=dev()), torch.empty(npix, device=dev())
@@ -391,11 +402,20 @@ def test_attention_block_kernels_at_the_bench_batch(dt):
     close(o, o_ref, TOL[dt], "attention forward")
     close(lse, lse_ref, 1e-4, "attention lse")
     do = rnd((npix, C), dt, 8)
+    route, tag = AB.attn_route(B, T, C, dt), f"attention block ({B}, {T}, {C}) dt={dt}"
+    assert route == R.T64
+    parts = R.attention_exact(qkv, B, T, C, do)
+    AB.forward_bounds(qkv, o, lse, B, T, C, dt, route, tag, parts)
     dq, dq_ref = torch.empty_like(qkv), torch.empty_like(qkv)
     delta = torch.empty(npix, device=dev())
     ops.attention_backward(qkv, o_ref, do, lse_ref, delta, dq, B, T, C, dt)
     E.attention_backward(qkv, o_ref, do, lse_ref, delta, dq_ref, B, T, C, dt)
     close(dq, dq_ref, TOL[dt], "attention backward")
+    AB.backward_bounds(qkv, o_ref, do, lse_ref, dq, delta, B, T, C, dt, route, tag + " backward on emulated inputs", parts)
+    dq_own = torch.empty_like(qkv)
+    ops.attention_backward(qkv, o, do, lse, delta, dq_own, B, T, C, dt)  # what the engine feeds it: the forward kernel's own outputs
+    close(dq_own, dq_ref, TOL[dt], "attention backward on own outputs")
+    AB.backward_bounds(qkv, o, do, lse, dq_own, delta, B, T, C, dt, route, tag + " backward on own outputs", parts)
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import attention_cases as AB
 import emu_ops as E
 import fp64_ref as R
 from climate2weather_amd import _lib, ops
@@ -719,6 +720,8 @@ def test_grad_scaler_and_fp16_shadow():
 def test_attention(shape, dt):
     B, T, C = shape
     d = dev()
+    route = AB.attn_route(B, T, C, dt)
+    tag = f"attention {shape} dtype {dt} {route}"
     qkv = rnd((B * T, 3 * C), dt, 1, scale=1.5)
     o, o_ref = torch.empty((B * T, C), dtype=TD[dt], device=d), torch.empty((B * T, C), dtype=TD[dt], device=d)
     lse, lse_ref = torch.empty(B * T, device=d), torch.empty(B * T, device=d)
@@ -727,11 +730,18 @@ def test_attention(shape, dt):
     close(o, o_ref, dt, "attention fwd")
     close(lse, lse_ref, F32, "attention lse", tol=1e-4)
     do = rnd((B * T, C), dt, 2)
+    parts = R.attention_exact(qkv, B, T, C, do)
+    AB.forward_bounds(qkv, o, lse, B, T, C, dt, route, tag, parts)
     dq, dq_ref = torch.empty_like(qkv), torch.empty_like(qkv)
     delta = torch.empty(B * T, device=d)
     ops.attention_backward(qkv, o_ref, do, lse_ref, delta, dq, B, T, C, dt)
     E.attention_backward(qkv, o_ref, do, lse_ref, delta, dq_ref, B, T, C, dt)
     close(dq, dq_ref, dt, "attention bwd")
+    AB.backward_bounds(qkv, o_ref, do, lse_ref, dq, delta, B, T, C, dt, route, tag + " backward on emulated inputs", parts)
+    dq_own, delta_own = torch.empty_like(qkv), torch.empty(B * T, device=d)
+    ops.attention_backward(qkv, o, do, lse, delta_own, dq_own, B, T, C, dt)  # what the engine feeds it: the forward kernel's own outputs
+    close(dq_own, dq_ref, dt, "attention bwd on own outputs")
+    AB.backward_bounds(qkv, o, do, lse, dq_own, delta_own, B, T, C, dt, route, tag + " backward on own outputs", parts)
 
 
 def test_regenerated_noise_stream_and_the_kernels_that_consume_it():
