@@ -15,7 +15,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 CONV_1X1, CONV_S1, CONV_S2, CONV_UP, CONV_TS2 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_SILU, ACT_SILU_PAIR, ACT_RELU, ACT_RELU_PAIR = 0, 1, 2, 3, 4
 MUL_PLAIN, MUL_DSILU = 0, 1
-CONV_POOL2, CONV_WPACKED, CONV_NO_Y = 1, 2, 4  # ConvArgs.flags (bit set)
+CONV_POOL2, CONV_WPACKED, CONV_NO_Y, CONV_DETERMINISTIC = 1, 2, 4, 8  # ConvArgs.flags (bit set)
 KERNEL_GATHER, KERNEL_PATCH_8X16, KERNEL_PATCH_16X16, KERNEL_PATCH_PAIR, KERNEL_PATCH_TS2, KERNEL_PATCH_S2 = 0, 1, 2, 3, 4, 5  # c2w_conv_dispatch
 
 
@@ -35,6 +35,7 @@ class ConvArgs(Structure):
         ("lnf_mean", c_void_p), ("res_rstd", c_void_p), ("res_mean", c_void_p), ("res_m", c_void_p),
         ("loss_sum", c_void_p), ("loss_scaler", c_void_p), ("loss_eps", c_void_p), ("loss_gscale", c_float), ("loss_C", c_int32),
         ("loss_lde", c_int32), ("splitk_ws", c_void_p), ("splitk_ws_bytes", c_ulonglong), ("splitk", c_int32),
+        ("det_ws", c_void_p), ("det_ws_bytes", c_ulonglong),
     ]
 
 
@@ -50,6 +51,7 @@ _PROTOS = {
     "c2w_conv_loss_supported": [POINTER(ConvArgs), c_int],
     "c2w_conv_splitk_plan": [POINTER(ConvArgs), c_int, POINTER(c_ulonglong)],
     "c2w_conv_lnfwd_chain_supported": [POINTER(ConvArgs), c_int],
+    "c2w_conv_det_scratch_bytes": [POINTER(ConvArgs), c_int],
     "c2w_conv_patch_supported": [POINTER(ConvArgs), c_int],
     "c2w_conv_pool2_supported": [POINTER(ConvArgs), c_int],
     "c2w_conv_dispatch": [POINTER(ConvArgs), c_int],
@@ -63,7 +65,12 @@ _PROTOS = {
     "c2w_ln_forward": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p],
     "c2w_ln_backward": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_int,
                         c_int, c_void_p],
+    "c2w_ln_backward_det": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_int,
+                            c_void_p, c_ulonglong, c_int, c_void_p],
+    "c2w_ln_backward_det_scratch_bytes": [c_longlong, c_int, c_int, c_int],
     "c2w_colsum": [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p],
+    "c2w_colsum_det": [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_ulonglong, c_int, c_void_p],
+    "c2w_colsum_det_scratch_bytes": [c_longlong, c_int],
     "c2w_silu": [c_void_p, c_void_p, c_longlong, c_int, c_void_p],
     "c2w_silu_backward": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p],
     "c2w_sumpool2": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
@@ -78,6 +85,13 @@ _PROTOS = {
     "c2w_mse_loss_grad_noise": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p],
     "c2w_sq_err": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "c2w_sq_err_noise": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_loss_det_scratch_bytes": [],
+    "c2w_mse_loss_grad_det": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_ulonglong, c_int,
+                              c_void_p],
+    "c2w_mse_loss_grad_noise_det": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_ulonglong,
+                                    c_int, c_void_p],
+    "c2w_sq_err_det": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ulonglong, c_int, c_void_p],
+    "c2w_sq_err_noise_det": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ulonglong, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

@@ -178,6 +178,10 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- deterministic mode (C2W_CONV_DETERMINISTIC, the c2w_*_det launchers): a workgroup that would add its contribution with an fp32
+// atomic STORES it into slot s of a caller-owned scratch (s a pure function of the launch geometry; every slot is written by the
+// launch, nothing is zero-filled), and a small launch behind it on the same stream adds the slots onto the destination in a fixed
+// order.
 template <int N> struct IC { static constexpr int value = N; };
 template <typename F, int... I> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(IC<I>{}), ...); }
 // f(IC<0>{}), ..., f(IC<N - 1>{}): loop indices that are constant expressions (asm immediates, register-array subscripts)
@@ -195,3 +199,40 @@ struct tr_frag {
         hipError_t _e = (expr);             \
         if (_e != hipSuccess) return (int)_e; \
     } while (0)
+
+// The reduce of the deterministic mode: dst[(i / cols) * ld_dst + i % cols] += sum over slots s of part[s * slot_stride + i], i < n.
+// `tpo` threads share an output: thread g adds slots g, g + tpo, ... in ascending order, the tpo partial sums meet in LDS and thread 0
+// of the output adds them in ascending g -- a tree fixed by (nslot, tpo), and tpo is chosen from nslot alone (det_reduce_tpo).
+// blk: the block's index among the blocks of this reduce (256 threads each; all of them must call: barrier inside).
+__device__ __forceinline__ void det_reduce_body(const float* __restrict__ part, float* __restrict__ dst, int nslot, long long n, int cols,
+                                                long long ld_dst, int tpo, long long slot_stride, int blk) {
+    __shared__ float det_red[256];
+    const int opb = 256 / tpo;
+    const int ol = threadIdx.x % opb, g = threadIdx.x / opb;
+    const long long i = (long long)blk * opb + ol;
+    float acc = 0.f;
+    if (i < n)
+        for (int s = g; s < nslot; s += tpo) acc += part[(size_t)s * slot_stride + i];
+    det_red[threadIdx.x] = acc;  // = det_red[g][ol]
+    __syncthreads();
+    if (g == 0 && i < n) {
+        for (int k = 1; k < tpo; ++k) acc += det_red[k * opb + ol];
+        float* d = dst + (i / cols) * ld_dst + (i % cols);
+        *d = *d + acc;
+    }
+}
+static inline int det_reduce_tpo(long long nslot) { return nslot >= 1024 ? 256 : nslot >= 16 ? 16 : 1; }
+static inline int det_reduce_blocks(long long nslot, long long n) {
+    const int opb = 256 / det_reduce_tpo(nslot);
+    return (int)((n + opb - 1) / opb);
+}
+
+static __global__ __launch_bounds__(256) void det_reduce_kernel(const float* __restrict__ part, float* __restrict__ dst, int nslot, long long n, int cols,
+                                                                long long ld_dst, int tpo) {
+    det_reduce_body(part, dst, nslot, n, cols, ld_dst, tpo, n, (int)blockIdx.x);
+}
+
+static inline int det_reduce(const float* part, float* dst, long long nslot, long long n, int cols, long long ld_dst, hipStream_t st) {
+    det_reduce_kernel<<<det_reduce_blocks(nslot, n), 256, 0, st>>>(part, dst, (int)nslot, n, cols, ld_dst, det_reduce_tpo(nslot));
+    return (int)hipGetLastError();
+}

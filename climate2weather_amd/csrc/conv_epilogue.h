@@ -97,6 +97,15 @@ __device__ __forceinline__ void epi_acc_to_lds_n(char* O, int OS, const f32x4_t 
 // LDS rows [NROWS][128 channels] -> global.  pix(row) maps a tile row to the NHWC pixel index, or -1 if the row is outside.
 // Split in two so that the residual / multiplier loads fly while the accumulators are staged through LDS:
 //   EpiStore st; st.prefetch(...);  __syncthreads(); epi_acc_to_lds(...); __syncthreads();  st.finish(...);
+// host: the reduce launch behind a convolution with the fused LayerNorm backward in deterministic mode (EpiStore::finish_ln_dm wrote a
+// row per workgroup; `tpi` workgroups per image)
+static inline int conv_ln_dm_reduce(const C2wConvArgs& a, int tpi, hipStream_t st) {
+    if ((a.flags & C2W_CONV_DETERMINISTIC) == 0 || a.ln_x == nullptr || a.ln_dm == nullptr) return (int)hipGetLastError();
+    HIP_CHECK_RET(hipGetLastError());
+    if (a.ln_ldm) return det_reduce(a.det_ws, a.ln_dm, tpi, (long long)a.B * 128, 128, a.ln_ldm, st);
+    return det_reduce(a.det_ws, a.ln_dm, (long long)a.B * tpi, 128, 128, 0, st);
+}
+
 template <typename T, int NROWS, int NTHR>
 struct EpiStore {
     static constexpr int ESZ = sizeof(T);
@@ -212,12 +221,17 @@ struct EpiStore {
         }
     };
     // one call = one pass of NROWS tile rows and the modulation-gradient reduction behind it (tiles of one pass)
-    __device__ __forceinline__ void finish_ln(const C2wConvArgs& p, const char* O, int OS, int tid, int img, float* red) {
+    // tt / tpi: this call's position among / the number of the calls that contribute to image `img` (the tile in the image: the slot of
+    // the deterministic mode, see finish_ln_dm)
+    // DET = false: an instantiation without the deterministic mode's branch (the all-in-one 16x16-tile kernel, which no LayerNorm
+    // launch reaches, has no registers for it)
+    template <bool DET = true>
+    __device__ __forceinline__ void finish_ln(const C2wConvArgs& p, const char* O, int OS, int tid, int img, float* red, int tt, int tpi) {
         LnColSums cs;
         cs.clear();
         if (p.ln_rstd != nullptr) finish_ln_rows<true>(p, O, OS, tid, img, cs);  // kernel argument: uniform
         else finish_ln_rows<false>(p, O, OS, tid, img, cs);
-        finish_ln_dm(p, tid, img, red, cs);
+        finish_ln_dm<DET>(p, tid, img, red, cs, tt, tpi, (float*)const_cast<char*>(O));
     }
     // the rows of one pass; the column sums are carried in `acc` (a tile of several passes reduces them once: finish_ln_dm).
     // STORED: the forward kept the normalised rows and their 1/sigma (C2wConvArgs.ln_rstd) -- a template parameter, because the 16x16-tile
@@ -346,9 +360,45 @@ struct EpiStore {
     // column sums -> ln_dm[img]: across the four pixel rows of a wave in registers (lanes l, l+16, l+32, l+48 hold the same channels),
     // across the waves through 128 floats of LDS (`red`, zeroed by the caller before the barrier that precedes the first pass), then
     // one global atomic per channel.  Every thread of the workgroup must call it (barrier inside).
-    __device__ __forceinline__ void finish_ln_dm(const C2wConvArgs& p, int tid, int img, float* red, const LnColSums& acc) {
+    // Deterministic mode (p.flags & C2W_CONV_DETERMINISTIC): neither the LDS atomics (their order is the waves' timing) nor the global
+    // ones.  Every wave stores its 128 column sums as its own row of `wrows` (LDS: the start of the output tile, whose rows every wave
+    // has finished behind the first barrier), thread c adds channel c of the rows in wave order and stores the workgroup's sum into
+    // the workgroup's row of p.det_ws -- per-image rows: [tile tt][image][128], one shared row (ln_ldm == 0): [image][tile][128] -- and
+    // det_reduce_kernel, launched behind the convolution, adds the rows of an image in that order.
+    template <bool DET = true>
+    __device__ __forceinline__ void finish_ln_dm(const C2wConvArgs& p, int tid, int img, float* red, const LnColSums& acc, int tt, int tpi,
+                                                 float* wrows) {
         if (p.ln_dm == nullptr) return;  // kernel argument: uniform
         const int cs = tid & (SEGS - 1);
+        if (DET && (p.flags & C2W_CONV_DETERMINISTIC) != 0) {  // kernel argument: uniform
+            constexpr int NWV = NTHR / 64;
+            const int wave = tid >> 6;
+            const size_t row = p.ln_ldm ? (size_t)tt * p.B + img : (size_t)img * tpi + tt;
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    float s = acc.am[k][h];
+                    s += __shfl_xor(s, 16, 64);
+                    s += __shfl_xor(s, 32, 64);
+                    v[2 * k + h] = s;
+                }
+            __syncthreads();  // the tile's rows are finished by every wave: its LDS is free
+            if ((tid & 63) < 16) {
+                float* const dst = wrows + wave * 128 + cs * PER16;
+                *(f32x4_t*)dst = (f32x4_t){v[0], v[1], v[2], v[3]};
+                *(f32x4_t*)(dst + 4) = (f32x4_t){v[4], v[5], v[6], v[7]};
+            }
+            __syncthreads();
+            if (tid < 128) {
+                float s = wrows[tid];
+#pragma unroll
+                for (int w = 1; w < NWV; ++w) s += wrows[w * 128 + tid];
+                p.det_ws[row * 128 + tid] = s;
+            }
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll

@@ -431,6 +431,25 @@ extern "C" int c2w_conv_loss_supported(const C2wConvArgs* a, int dtype) {
     return !k.force_gather && k.loss_fusion && k.wgrad_narrow && c2w_conv_patch_eligible(*a) && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
 }
 
+// Deterministic mode: the scratch behind the fused reductions of c2w_conv_forward.  LayerNorm backward: a row of 128 floats per
+// workgroup -- sized for 8 x 16-pixel tiles (the 16 x 16-tile kernel has half as many workgroups), so that the answer does not
+// depend on which of the tile kernels the launch takes.
+// Loss: one float per workgroup of the 16 x 16-tile kernel.
+extern "C" long long c2w_conv_det_scratch_bytes(const C2wConvArgs* a, int dtype) {
+    if (a == nullptr) return C2W_ERR_BAD_ARG;
+    if (a->ln_x != nullptr && a->ln_dm != nullptr) {
+        if (!c2w_conv_lnbwd_supported(a, dtype)) return C2W_ERR_UNSUPPORTED;
+        return (long long)a->B * (a->Hout >> 3) * (a->Wout >> 4) * 128 * (long long)sizeof(float);
+    }
+    if (a->loss_sum != nullptr) {
+        C2wConvArgs g = *a;
+        g.loss_sum = nullptr;  // the geometry's answer: the query is made without the loss operands
+        if (!c2w_conv_loss_supported(&g, dtype)) return C2W_ERR_UNSUPPORTED;
+        return (long long)a->B * (a->Hout >> 4) * (a->Wout >> 4) * ((a->Cout + 127) / 128) * (long long)sizeof(float);
+    }
+    return 0;
+}
+
 extern "C" int c2w_conv_wpacked_supported(const C2wConvArgs* a, int dtype) {
     if (a == nullptr || (dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16)) return 0;
     return !c2w_knobs().force_gather && c2w_knobs().wpacked && c2w_conv_patch_eligible(*a) && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
@@ -468,6 +487,10 @@ extern "C" int c2w_conv_forward(const C2wConvArgs* a, int dtype, int naive, void
     }
     if ((a->flags & C2W_CONV_POOL2) != 0 && (naive != 0 || !c2w_conv_pool2_supported(a, dtype))) return C2W_ERR_BAD_SHAPE;
     if (a->loss_sum != nullptr && (naive != 0 || !c2w_conv_loss_supported(a, dtype))) return C2W_ERR_BAD_SHAPE;  // no silent unfused result
+    if ((a->flags & C2W_CONV_DETERMINISTIC) != 0 && ((a->ln_x != nullptr && a->ln_dm != nullptr) || a->loss_sum != nullptr)) {
+        const long long need = c2w_conv_det_scratch_bytes(a, dtype);  // never a silent fall-back to atomics
+        if (need < 0 || a->det_ws == nullptr || a->det_ws_bytes < (unsigned long long)need) return C2W_ERR_BAD_ARG;
+    }
     if (a->splitk > 1) {  // exactly the plan's answer, with its scratch, or nothing
         unsigned long long need = 0;
         if (naive != 0 || a->splitk_ws == nullptr || c2w_conv_splitk_plan_impl(*a, dtype, &need) != a->splitk || a->splitk_ws_bytes < need) return C2W_ERR_BAD_SHAPE;

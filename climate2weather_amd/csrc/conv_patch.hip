@@ -257,7 +257,7 @@ __global__ __launch_bounds__(H_NTHR, 2) void conv_patch_half_kernel(const C2wCon
     if (pool2) {
         est.finish_pool2(p, O, OS, tid, co0, ((long long)b * (H >> 1) + (oh0 >> 1)) * (W >> 1) + (ow0 >> 1), W >> 1);
     } else if constexpr (ESZ == 2 && !PAIR) {
-        if (p.ln_x != nullptr) est.finish_ln(p, O, OS, tid, b, red);
+        if (p.ln_x != nullptr) est.finish_ln(p, O, OS, tid, b, red, tt, tpi);
         else if (p.lnf_y != nullptr) est.finish_lnf(p, O, OS, tid, b);
         else est.finish(p, O, OS, tid);
     } else {
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(H8_NTHR, DB ? 1 : 2) void conv_patch_half8_kernel(c
     if (pool2) {
         est.finish_pool2(p, O, OS, tid, co0, ((long long)b * (H >> 1) + (oh0 >> 1)) * (W >> 1) + (ow0 >> 1), W >> 1);
     } else if constexpr (ESZ == 2 && !PAIR) {
-        if (p.ln_x != nullptr) est.finish_ln(p, O, OS, tid, b, red);
+        if (p.ln_x != nullptr) est.finish_ln(p, O, OS, tid, b, red, tt, tpi);
         else if (p.lnf_y != nullptr) est.finish_lnf(p, O, OS, tid, b);
         else est.finish(p, O, OS, tid);
     } else {
@@ -1317,9 +1317,13 @@ int launch(const C2wConvArgs& a, hipStream_t st) {  // two 8x16-tile workgroups 
     const int nN = (a.Cout + 127) / 128;
     const int nMh = a.B * (a.Hout >> 3) * (a.Wout >> 4);
     if (a.splitk > 1) return launch_splitk<T, false>(a, nMh * nN, st);
-    if (half8_wanted<T>((long long)nMh * nN)) return launch_half8<T, false, false>(a, nMh * nN, st);
+    const int tpi = (a.Hout >> 3) * (a.Wout >> 4);
+    if (half8_wanted<T>((long long)nMh * nN)) {
+        const int rc = launch_half8<T, false, false>(a, nMh * nN, st);
+        return rc != 0 ? rc : conv_ln_dm_reduce(a, tpi, st);
+    }
     conv_patch_half_kernel<T><<<nMh * nN, H_NTHR, H_LDS, st>>>(a);
-    return (int)hipGetLastError();
+    return conv_ln_dm_reduce(a, tpi, st);
 }
 
 }  // namespace

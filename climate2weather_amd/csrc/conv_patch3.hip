@@ -372,7 +372,9 @@ __global__ __launch_bounds__(64 * NW, (T3Cfg<TR, NW>::WAVES_PER_SIMD)) void conv
                 float tot = 0.f;
 #pragma unroll
                 for (int i = 0; i < NW; ++i) tot += red[i];
-                atomicAdd(p.loss_sum, tot);
+                // deterministic mode: the workgroup's sum goes to its own slot, det_reduce_kernel adds the slots behind this launch
+                if (p.flags & C2W_CONV_DETERMINISTIC) p.det_ws[blockIdx.x] = tot;  // kernel argument: uniform
+                else atomicAdd(p.loss_sum, tot);
             }
         }
         typename EpiStore<T, 128, T3_NTHR>::LnColSums dmsum;  // LayerNorm backward: modulation-gradient column sums, carried over both blocks
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(64 * NW, (T3Cfg<TR, NW>::WAVES_PER_SIMD)) void conv
             else if constexpr (EPI == 6) est.template finish_ln_rows<true>(p, Oh, T3_OS, tid_e, b, dmsum);
             else est.finish(p, Oh, T3_OS, tid_e);
         }
-        if constexpr (EPI == 3 || EPI == 6) est0.finish_ln_dm(p, tid_e, b, red, dmsum);  // one reduction per tile (was: per block, with two more barriers between)
+        if constexpr (EPI == 3 || EPI == 6) est0.finish_ln_dm(p, tid_e, b, red, dmsum, tt, tpi, (float*)O);  // one reduction per tile (was: per block, with two more barriers between)
     } else {
 #pragma unroll
         for (int h = 0; h < CF::NPASS; ++h) {
@@ -398,10 +400,10 @@ __global__ __launch_bounds__(64 * NW, (T3Cfg<TR, NW>::WAVES_PER_SIMD)) void conv
         const char* const Oh = O + h * 128 * T3_OS;
         // EPI 2 / 3 / 4: instantiations that carry one epilogue only (picked by the launcher)
         if constexpr (EPI == 2 || EPI == 8) est.template finish_lnf<EPI == 8>(p, Oh, T3_OS, tid_e, b);
-        else if constexpr (EPI == 3 || EPI == 6) est.finish_ln(p, Oh, T3_OS, tid_e, b, red);
+        else if constexpr (EPI == 3 || EPI == 6) est.template finish_ln<false>(p, Oh, T3_OS, tid_e, b, red, tt, tpi);
         else if constexpr (EPI == 4) est.finish(p, Oh, T3_OS, tid_e);
         else if (pool2) est.finish_pool2(p, Oh, T3_OS, tid_e, co0, ((long long)b * (H >> 1) + ((oh0 + 8 * h) >> 1)) * (W >> 1) + (ow0 >> 1), W >> 1);
-        else if (p.ln_x != nullptr) est.finish_ln(p, Oh, T3_OS, tid_e, b, red);
+        else if (p.ln_x != nullptr) est.template finish_ln<false>(p, Oh, T3_OS, tid_e, b, red, tt, tpi);  // (no launch with a LayerNorm takes EPI 0: t3_launch)
         else if (p.lnf_y != nullptr) est.finish_lnf(p, Oh, T3_OS, tid_e, b);
         else est.finish(p, Oh, T3_OS, tid_e);
         if (h + 1 < CF::NPASS) __syncthreads();  // the LayerNorm column sums are re-zeroed for the next block only after everyone read them
@@ -420,6 +422,13 @@ int t3_launch_wpk(const C2wConvArgs& a, hipStream_t st) {
     const int nN = (a.Cout + 127) / 128;
     const int nM = a.B * (a.Hout / TR) * (a.Wout >> 4);
     conv_patch_t3_kernel<TR, T, NW, EPI, WPK><<<nM * nN, CF::NTHR, CF::LDS, st>>>(a);
+    if constexpr (EPI == 3 || EPI == 6) return conv_ln_dm_reduce(a, (a.Hout / TR) * (a.Wout >> 4), st);
+    if constexpr (EPI == 7) {
+        if ((a.flags & C2W_CONV_DETERMINISTIC) != 0) {  // loss_sum += the workgroups' sums, in a fixed order
+            HIP_CHECK_RET(hipGetLastError());
+            return det_reduce(a.det_ws, a.loss_sum, (long long)nM * nN, 1, 1, 0, st);
+        }
+    }
     return (int)hipGetLastError();
 }
 template <int TR, typename T, int NW, int EPI>
@@ -436,6 +445,7 @@ int t3_launch(const C2wConvArgs& a, hipStream_t st) {
         if (a.wrows <= 80 && a.Cout <= 128 && c2w_knobs().wgrad_narrow) return t3_launch_as<16, T, NW, 5>(a, st);  // the output conv: 65 weight rows
         return t3_launch_as<16, T, NW, 4>(a, st);
     }
+    if ((a.flags & C2W_CONV_DETERMINISTIC) != 0 && a.ln_x != nullptr) return C2W_ERR_UNSUPPORTED;  // the all-in-one kernel carries no fixed-order reduction
     return t3_launch_as<TR, T, NW, 0>(a, st);
 }
 

@@ -79,7 +79,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ m,
                                                      const T* __restrict__ dres, T* __restrict__ dx, float* __restrict__ dm,
-                                                     int HW, int C, int ldm, float eps, float inv_den, int pix_per_block) {
+                                                     int HW, int C, int ldm, float eps, float inv_den, int pix_per_block,
+                                                     float* __restrict__ part) {
     constexpr int P = Elem<T>::PER16;
     extern __shared__ __attribute__((aligned(16))) float ln_red[];  // [16 pixel sub-groups][C], only with dm
     const int sub = threadIdx.x >> 4, j = threadIdx.x & 15;
@@ -185,11 +186,15 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
         }
         __syncthreads();
         float* dr = dm + (size_t)(ldm ? b : 0) * ldm;
+        // deterministic mode (part != nullptr, workgroup-uniform): the block's row goes to its own slot instead -- per-image rows:
+        // [chunk][image][C], summed over the chunks; one shared row: [image * chunks + chunk][C] (c2w_ln_backward_det)
+        float* pr = part ? part + (ldm ? (size_t)blockIdx.x * gridDim.y + b : (size_t)b * gridDim.x + blockIdx.x) * C : nullptr;
         for (int c = threadIdx.x; c < C; c += 256) {
             float sum = 0.f;
 #pragma unroll
             for (int sb = 0; sb < 16; ++sb) sum += ln_red[sb * C + c];
-            atomicAdd(dr + c, sum);
+            if (pr) pr[c] = sum;
+            else atomicAdd(dr + c, sum);
         }
     }
 }
@@ -198,13 +203,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
 // (coalesced); row groups are combined through LDS and each block issues one contiguous atomic sweep.
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ a, float* __restrict__ out, long long rows, int C, int lda,
-                                                     int rows_per_block) {
+                                                     int rows_per_block, float* __restrict__ part) {
     constexpr int P = Elem<T>::PER16;
     __shared__ float red[256 * P];
     const int vbase = blockIdx.y * 256;              // this block's slice of the row: up to 256 vectors of 16 B
     const int nvec = (C / P - vbase) < 256 ? (C / P - vbase) : 256;
     a += (size_t)vbase * P;
     out += (size_t)vbase * P;
+    if (part) part += (size_t)blockIdx.x * C + (size_t)vbase * P;  // deterministic mode: slot = row block, [row block][C]
     C = nvec * P;
     const int ngrp = 256 / nvec;
     const int vec = threadIdx.x % nvec, grp = threadIdx.x / nvec;
@@ -227,7 +233,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ a, fl
     for (int c = threadIdx.x; c < C; c += 256) {
         float s = 0.f;
         for (int g = 0; g < ngrp; ++g) s += red[g * C + c];
-        atomicAdd(out + c, s);
+        if (part) part[c] = s;
+        else atomicAdd(out + c, s);
     }
 }
 
@@ -340,12 +347,19 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T* __restrict__
     }
 }
 
+// A wave's share of the loss scalar (lane 0 of every wave of a 256-thread block): one fp32 atomic, or -- deterministic mode, part !=
+// nullptr (workgroup-uniform) -- a plain store into the wave's own slot part[4 * block + wave], added up by det_reduce_kernel.
+__device__ __forceinline__ void loss_contribute(float* loss_sum, float* part, float local) {
+    if (part) part[blockIdx.x * 4 + (threadIdx.x >> 6)] = local;
+    else atomicAdd(loss_sum, local);
+}
+
 // Training loss tail (src/thor/pipelines.py:35 + training_loop.py:377):  l = mean((y - eps)^2) * scale
 //   dy[b][pix][c] = 2 (y - eps) * scale / N   (NHWC T, padded channels = 0);  loss_sum += sum (y-eps)^2 (fp32 atomics)
 template <typename T>
 __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const T* __restrict__ y, const float* __restrict__ eps, T* __restrict__ dy,
                                                             float* __restrict__ loss_sum, int B, int C, int HW, int ldc, float gscale,
-                                                            const float* __restrict__ dscale) {
+                                                            const float* __restrict__ dscale, float* __restrict__ part) {
     if (dscale != nullptr) gscale *= dscale[0];  // dynamic loss scale (c2w_grad_scaler_*), read on the device
     constexpr int P = Elem<T>::PER16;
     const int nvec = ldc / P;
@@ -372,7 +386,7 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const T* __restrict_
         *(u32x4_t*)(dy + o) = pack16<T>(f);
     }
     local = wave_sum(local);
-    if ((threadIdx.x & 63) == 0) atomicAdd(loss_sum, local);
+    if ((threadIdx.x & 63) == 0) loss_contribute(loss_sum, part, local);
 }
 
 // ---- LDS-tiled layout kernels: one block = one image x 64 pixels.  Channel planes (NCHW fp32) are read as coalesced rows
@@ -537,7 +551,8 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_eps_kernel(const float* __re
 template <typename T, bool PHILOX = false>
 __global__ __launch_bounds__(256) void mse_loss_grad_tiled_kernel(const T* __restrict__ y, const float* __restrict__ eps, T* __restrict__ dy,
                                                                   float* __restrict__ loss_sum, int B, int C, int HW, int ldc, float gscale,
-                                                                  const float* __restrict__ dscale, uint32_t k0 = 0, uint32_t k1 = 0) {
+                                                                  const float* __restrict__ dscale, float* __restrict__ part, uint32_t k0 = 0,
+                                                                  uint32_t k1 = 0) {
     if (dscale != nullptr) gscale *= dscale[0];
     constexpr int P = Elem<T>::PER16;
     extern __shared__ float lt_tile[];
@@ -578,7 +593,7 @@ __global__ __launch_bounds__(256) void mse_loss_grad_tiled_kernel(const T* __res
         __syncthreads();
     }
     local = wave_sum(local);
-    if ((threadIdx.x & 63) == 0) atomicAdd(loss_sum, local);
+    if ((threadIdx.x & 63) == 0) loss_contribute(loss_sum, part, local);
 }
 
 // NHWC T -> NCHW fp32 through the same LDS tile: rows of 64 pixels x ldc channels are read as one contiguous run, channel planes
@@ -613,7 +628,8 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_tiled_kernel(const T* __rest
 // regenerated from the step's Philox stream (SQ == 2: four consecutive pixels of a channel plane are one counter).  HW % 4 == 0.
 template <typename T, int SQ>
 __global__ __launch_bounds__(256) void sq_err_tiled_kernel(const T* __restrict__ y, const float* __restrict__ eps, float* __restrict__ out,
-                                                           float* __restrict__ loss_sum, int B, int C, int HW, int ldc, uint32_t k0, uint32_t k1) {
+                                                           float* __restrict__ loss_sum, int B, int C, int HW, int ldc, uint32_t k0, uint32_t k1,
+                                                           float* __restrict__ part) {
     constexpr int P = Elem<T>::PER16;
     extern __shared__ float lt_tile[];
     const int ntile = (HW + LT_PT - 1) / LT_PT, nvec = ldc / P;
@@ -650,7 +666,7 @@ __global__ __launch_bounds__(256) void sq_err_tiled_kernel(const T* __restrict__
     }
     if (loss_sum != nullptr) {  // sum of the tensor just written: the caller's .mean() without a second pass over it
         local = wave_sum(local);
-        if ((threadIdx.x & 63) == 0) atomicAdd(loss_sum, local);
+        if ((threadIdx.x & 63) == 0) loss_contribute(loss_sum, part, local);
     }
 }
 
@@ -845,6 +861,23 @@ inline int grid_for(long long n, int per_block = 256, int cap = 8192) {
     return (int)(g < cap ? g : cap);
 }
 
+// launch geometry shared by the launchers and their scratch-size queries
+struct LnBwdPlan { int ppb; unsigned gx, gy; };
+LnBwdPlan ln_bwd_plan(long long npix, int HW) {
+    // pixels per block: 512 at the large levels; fewer where that would leave the chip with under ~2048 blocks (32x32 and
+    // below at B = 128: 256 / 128 blocks of 4 waves were latency-bound at 3.5 TB/s)
+    long long want = (npix / 2048 + 15) / 16 * 16;
+    if (want < 16) want = 16;
+    if (want > 512) want = 512;
+    LnBwdPlan r;
+    r.ppb = HW < want ? HW : (int)want;
+    r.gx = (unsigned)((HW + r.ppb - 1) / r.ppb);
+    r.gy = (unsigned)(npix / HW);
+    return r;
+}
+constexpr int COLSUM_RPB = 2048;
+constexpr long long LOSS_MAX_BLOCKS = 4096;  // the largest grid of the loss kernels (sq_err_launch); 4 waves = 4 slots per block
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL)                                                         \
@@ -870,35 +903,79 @@ extern "C" int c2w_ln_forward(const void* x, const float* m, void* y, long long 
     return (int)hipGetLastError();
 }
 
-extern "C" int c2w_ln_backward(const void* dy, const void* x, const float* m, const void* dres, void* dx, float* dm, long long npix, int HW,
-                               int C, int ldm, float eps, int unbiased, int dtype, void* stream) {
+extern "C" long long c2w_ln_backward_det_scratch_bytes(long long npix, int HW, int C, int ldm) {
+    (void)ldm;  // both layouts hold one row of C floats per block
+    if (HW <= 0 || npix <= 0 || npix % HW != 0 || C <= 0) return C2W_ERR_BAD_SHAPE;
+    const LnBwdPlan pl = ln_bwd_plan(npix, HW);
+    return (long long)pl.gx * pl.gy * C * (long long)sizeof(float);
+}
+
+static int ln_backward_launch(const void* dy, const void* x, const float* m, const void* dres, void* dx, float* dm, long long npix, int HW,
+                              int C, int ldm, float eps, int unbiased, bool det, float* scratch, unsigned long long scratch_bytes, int dtype,
+                              void* stream) {
     if (!dy || !x || !dx || !vec_ok(dtype, C) || C > 16 * LN_MAXV * (dtype == C2W_DTYPE_F32 ? 4 : 8) || C < 2) return C2W_ERR_BAD_SHAPE;
     const float inv_den = 1.0f / (float)(unbiased ? C - 1 : C);
     if (HW <= 0 || npix % HW != 0) return C2W_ERR_BAD_SHAPE;
-    // pixels per block: 512 at the large levels; fewer where that would leave the chip with under ~2048 blocks (32x32 and
-    // below at B = 128: 256 / 128 blocks of 4 waves were latency-bound at 3.5 TB/s)
-    long long want = (npix / 2048 + 15) / 16 * 16;
-    if (want < 16) want = 16;
-    if (want > 512) want = 512;
-    const int ppb = HW < want ? HW : (int)want;
-    dim3 grid((HW + ppb - 1) / ppb, (unsigned)(npix / HW));
+    const LnBwdPlan pl = ln_bwd_plan(npix, HW);
+    const int ppb = pl.ppb;
+    dim3 grid(pl.gx, pl.gy);
+    float* const part = det && dm != nullptr ? scratch : nullptr;
+    if (det && dm != nullptr && (scratch == nullptr || scratch_bytes < (unsigned long long)pl.gx * pl.gy * C * sizeof(float))) return C2W_ERR_BAD_ARG;
     const int nv = (C + 16 * (dtype == C2W_DTYPE_F32 ? 4 : 8) - 1) / (16 * (dtype == C2W_DTYPE_F32 ? 4 : 8));
     const size_t red_bytes = dm != nullptr ? (size_t)16 * C * sizeof(float) : 0;  // <= 64 KiB (C <= 1024)
 #define LN_BWD(NVV) DISPATCH_T(dtype, (ln_bwd_kernel<T, NVV><<<grid, 256, red_bytes, (hipStream_t)stream>>>( \
-    (const T*)dy, (const T*)x, m, (const T*)dres, (T*)dx, dm, HW, C, ldm, eps, inv_den, ppb)))
+    (const T*)dy, (const T*)x, m, (const T*)dres, (T*)dx, dm, HW, C, ldm, eps, inv_den, ppb, part)))
     if (nv <= 1) LN_BWD(1); else if (nv == 2) LN_BWD(2); else if (nv == 3) LN_BWD(3); else if (nv == 4) LN_BWD(4);
     else if (nv <= 6) LN_BWD(6); else LN_BWD(8);
 #undef LN_BWD
+    if (part != nullptr) {
+        HIP_CHECK_RET(hipGetLastError());
+        if (ldm) return det_reduce(part, dm, pl.gx, (long long)pl.gy * C, C, ldm, (hipStream_t)stream);  // image b: chunk 0, 1, ...
+        return det_reduce(part, dm, (long long)pl.gx * pl.gy, C, C, 0, (hipStream_t)stream);          // one row: (image, chunk) raster order
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int c2w_ln_backward(const void* dy, const void* x, const float* m, const void* dres, void* dx, float* dm, long long npix, int HW,
+                               int C, int ldm, float eps, int unbiased, int dtype, void* stream) {
+    return ln_backward_launch(dy, x, m, dres, dx, dm, npix, HW, C, ldm, eps, unbiased, false, nullptr, 0, dtype, stream);
+}
+
+extern "C" int c2w_ln_backward_det(const void* dy, const void* x, const float* m, const void* dres, void* dx, float* dm, long long npix, int HW,
+                                   int C, int ldm, float eps, int unbiased, float* scratch, unsigned long long scratch_bytes, int dtype,
+                                   void* stream) {
+    return ln_backward_launch(dy, x, m, dres, dx, dm, npix, HW, C, ldm, eps, unbiased, true, scratch, scratch_bytes, dtype, stream);
+}
+
+extern "C" long long c2w_colsum_det_scratch_bytes(long long rows, int C) {
+    if (rows <= 0 || C <= 0) return C2W_ERR_BAD_SHAPE;
+    return (rows + COLSUM_RPB - 1) / COLSUM_RPB * C * (long long)sizeof(float);
+}
+
+static int colsum_launch(const void* a, float* out, long long rows, int C, int lda, bool det, float* scratch, unsigned long long scratch_bytes,
+                         int dtype, void* stream) {
+    if (!a || !out || !vec_ok(dtype, C) || !vec_ok(dtype, lda)) return C2W_ERR_BAD_SHAPE;
+    if (det && rows <= 0) return C2W_ERR_BAD_SHAPE;
+    const int rpb = COLSUM_RPB;
+    const int nvec_total = C / (dtype == C2W_DTYPE_F32 ? 4 : 8);
+    const dim3 grid((unsigned)((rows + rpb - 1) / rpb), (unsigned)((nvec_total + 255) / 256));
+    if (det && (scratch == nullptr || scratch_bytes < (unsigned long long)grid.x * C * sizeof(float))) return C2W_ERR_BAD_ARG;
+    float* const part = det ? scratch : nullptr;
+    DISPATCH_T(dtype, (colsum_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T*)a, out, rows, C, lda, rpb, part)));
+    if (part != nullptr) {
+        HIP_CHECK_RET(hipGetLastError());
+        return det_reduce(part, out, grid.x, C, C, 0, (hipStream_t)stream);
+    }
     return (int)hipGetLastError();
 }
 
 extern "C" int c2w_colsum(const void* a, float* out, long long rows, int C, int lda, int dtype, void* stream) {
-    if (!a || !out || !vec_ok(dtype, C) || !vec_ok(dtype, lda)) return C2W_ERR_BAD_SHAPE;
-    const int rpb = 2048;
-    const int nvec_total = C / (dtype == C2W_DTYPE_F32 ? 4 : 8);
-    const dim3 grid((unsigned)((rows + rpb - 1) / rpb), (unsigned)((nvec_total + 255) / 256));
-    DISPATCH_T(dtype, (colsum_kernel<T><<<grid, 256, 0, (hipStream_t)stream>>>((const T*)a, out, rows, C, lda, rpb)));
-    return (int)hipGetLastError();
+    return colsum_launch(a, out, rows, C, lda, false, nullptr, 0, dtype, stream);
+}
+
+extern "C" int c2w_colsum_det(const void* a, float* out, long long rows, int C, int lda, float* scratch, unsigned long long scratch_bytes, int dtype,
+                              void* stream) {
+    return colsum_launch(a, out, rows, C, lda, true, scratch, scratch_bytes, dtype, stream);
 }
 
 extern "C" int c2w_silu(const void* x, void* y, long long n, int dtype, void* stream) {
@@ -969,20 +1046,46 @@ extern "C" int c2w_nhwc_to_nchw(const void* y, float* out, int B, int C, int HW,
     return (int)hipGetLastError();
 }
 
-extern "C" int c2w_mse_loss_grad_scaled(const void* y, const float* eps, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
-                                        const float* scaler_state, int dtype, void* stream) {
+// One size for every loss launcher (c2w_mse_loss_grad*_det, c2w_sq_err*_det): a slot per wave of the largest grid any of them uses.
+extern "C" long long c2w_loss_det_scratch_bytes(void) { return LOSS_MAX_BLOCKS * 4 * (long long)sizeof(float); }
+
+// deterministic mode: the scratch must hold a slot per wave; then the slots are added onto loss_sum by det_reduce
+static bool loss_scratch_ok(bool det, const float* scratch, unsigned long long scratch_bytes) {
+    return !det || (scratch != nullptr && scratch_bytes >= (unsigned long long)c2w_loss_det_scratch_bytes());
+}
+static int loss_finish(float* part, float* loss_sum, int nblk, void* stream) {
+    if (part == nullptr) return (int)hipGetLastError();
+    HIP_CHECK_RET(hipGetLastError());
+    return det_reduce(part, loss_sum, (long long)nblk * 4, 1, 1, 0, (hipStream_t)stream);
+}
+
+static int mse_loss_grad_launch(const void* y, const float* eps, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
+                                const float* scaler_state, bool det, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream) {
     if (!y || !eps || !dy || !loss_sum || !vec_ok(dtype, ldc) || ldc < C) return C2W_ERR_BAD_SHAPE;
+    if (!loss_scratch_ok(det, scratch, scratch_bytes)) return C2W_ERR_BAD_ARG;
+    float* const part = det ? scratch : nullptr;
     const int P = dtype == C2W_DTYPE_F32 ? 4 : 8;
     const size_t lds = (size_t)ldc * LT_LD * sizeof(float);
     if (lds <= 64 * 1024) {
         const int nblk = (int)std::min<long long>((long long)B * ((HW + LT_PT - 1) / LT_PT), 2048);
         DISPATCH_T(dtype, (mse_loss_grad_tiled_kernel<T><<<nblk, 256, lds, (hipStream_t)stream>>>((const T*)y, eps, (T*)dy, loss_sum, B, C, HW,
-                                                                                                  ldc, gscale, scaler_state)));
-        return (int)hipGetLastError();
+                                                                                                  ldc, gscale, scaler_state, part)));
+        return loss_finish(part, loss_sum, nblk, stream);
     }
-    DISPATCH_T(dtype, (mse_loss_grad_kernel<T><<<grid_for((long long)B * HW * (ldc / P), 256, 2048), 256, 0, (hipStream_t)stream>>>(
-                          (const T*)y, eps, (T*)dy, loss_sum, B, C, HW, ldc, gscale, scaler_state)));
-    return (int)hipGetLastError();
+    const int nblk = grid_for((long long)B * HW * (ldc / P), 256, 2048);
+    DISPATCH_T(dtype, (mse_loss_grad_kernel<T><<<nblk, 256, 0, (hipStream_t)stream>>>(
+                          (const T*)y, eps, (T*)dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, part)));
+    return loss_finish(part, loss_sum, nblk, stream);
+}
+
+extern "C" int c2w_mse_loss_grad_scaled(const void* y, const float* eps, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
+                                        const float* scaler_state, int dtype, void* stream) {
+    return mse_loss_grad_launch(y, eps, dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, false, nullptr, 0, dtype, stream);
+}
+
+extern "C" int c2w_mse_loss_grad_det(const void* y, const float* eps, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
+                                     const float* scaler_state, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream) {
+    return mse_loss_grad_launch(y, eps, dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, true, scratch, scratch_bytes, dtype, stream);
 }
 
 extern "C" int c2w_mse_loss_grad(const void* y, const float* eps, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
@@ -1034,31 +1137,57 @@ extern "C" int c2w_windows_to_nhwc_noise(const float* data, const long long* img
     return (int)hipGetLastError();
 }
 
-extern "C" int c2w_mse_loss_grad_noise(const void* y, unsigned long long seed, void* dy, float* loss_sum, int B, int C, int HW, int ldc,
-                                       float gscale, const float* scaler_state, int dtype, void* stream) {
+static int mse_loss_grad_noise_launch(const void* y, unsigned long long seed, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
+                                      const float* scaler_state, bool det, float* scratch, unsigned long long scratch_bytes, int dtype,
+                                      void* stream) {
     if (!y || !dy || !loss_sum || !vec_ok(dtype, ldc) || ldc < C) return C2W_ERR_BAD_SHAPE;
     const size_t lds = (size_t)ldc * LT_LD * sizeof(float);
     if (lds > 64 * 1024) return C2W_ERR_UNSUPPORTED;
+    if (!loss_scratch_ok(det, scratch, scratch_bytes)) return C2W_ERR_BAD_ARG;
+    float* const part = det ? scratch : nullptr;
     const int nblk = (int)std::min<long long>((long long)B * ((HW + LT_PT - 1) / LT_PT), 2048);
     DISPATCH_T(dtype, (mse_loss_grad_tiled_kernel<T, true><<<nblk, 256, lds, (hipStream_t)stream>>>(
-                          (const T*)y, nullptr, (T*)dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, (uint32_t)seed, (uint32_t)(seed >> 32))));
-    return (int)hipGetLastError();
+                          (const T*)y, nullptr, (T*)dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, part, (uint32_t)seed, (uint32_t)(seed >> 32))));
+    return loss_finish(part, loss_sum, nblk, stream);
+}
+
+extern "C" int c2w_mse_loss_grad_noise(const void* y, unsigned long long seed, void* dy, float* loss_sum, int B, int C, int HW, int ldc,
+                                       float gscale, const float* scaler_state, int dtype, void* stream) {
+    return mse_loss_grad_noise_launch(y, seed, dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, false, nullptr, 0, dtype, stream);
+}
+
+extern "C" int c2w_mse_loss_grad_noise_det(const void* y, unsigned long long seed, void* dy, float* loss_sum, int B, int C, int HW, int ldc,
+                                           float gscale, const float* scaler_state, float* scratch, unsigned long long scratch_bytes, int dtype,
+                                           void* stream) {
+    return mse_loss_grad_noise_launch(y, seed, dy, loss_sum, B, C, HW, ldc, gscale, scaler_state, true, scratch, scratch_bytes, dtype, stream);
 }
 
 static int sq_err_launch(const void* y, const float* eps, unsigned long long seed, bool regen, float* out, float* loss_sum, int B, int C, int HW,
-                         int ldc, int dtype, void* stream) {
+                         int ldc, int dtype, void* stream, bool det = false, float* scratch = nullptr, unsigned long long scratch_bytes = 0) {
     if (!y || !out || (!regen && !eps) || !vec_ok(dtype, ldc) || ldc < C) return C2W_ERR_BAD_SHAPE;
     const size_t lds = (size_t)ldc * LT_LD * sizeof(float);
     if (lds > 64 * 1024 || (HW & 3) != 0 || ((uintptr_t)out & 15) != 0 || (eps && ((uintptr_t)eps & 15) != 0)) return C2W_ERR_UNSUPPORTED;
-    const int nblk = (int)std::min<long long>((long long)B * ((HW + LT_PT - 1) / LT_PT), 4096);  // bounded: one atomic per wave
+    if (loss_sum != nullptr && !loss_scratch_ok(det, scratch, scratch_bytes)) return C2W_ERR_BAD_ARG;
+    float* const part = det && loss_sum != nullptr ? scratch : nullptr;
+    const int nblk = (int)std::min<long long>((long long)B * ((HW + LT_PT - 1) / LT_PT), LOSS_MAX_BLOCKS);  // bounded: one atomic per wave
     if (regen) {
         DISPATCH_T(dtype, (sq_err_tiled_kernel<T, 2><<<nblk, 256, lds, (hipStream_t)stream>>>((const T*)y, nullptr, out, loss_sum, B, C, HW, ldc,
-                                                                                              (uint32_t)seed, (uint32_t)(seed >> 32))));
+                                                                                              (uint32_t)seed, (uint32_t)(seed >> 32), part)));
     } else {
         DISPATCH_T(dtype, (sq_err_tiled_kernel<T, 1><<<nblk, 256, lds, (hipStream_t)stream>>>((const T*)y, eps, out, loss_sum, B, C, HW, ldc, 0u,
-                                                                                              0u)));
+                                                                                              0u, part)));
     }
-    return (int)hipGetLastError();
+    return loss_finish(part, loss_sum, nblk, stream);
+}
+
+extern "C" int c2w_sq_err_det(const void* y, const float* eps, float* out, float* loss_sum, int B, int C, int HW, int ldc, float* scratch,
+                              unsigned long long scratch_bytes, int dtype, void* stream) {
+    return sq_err_launch(y, eps, 0ull, false, out, loss_sum, B, C, HW, ldc, dtype, stream, true, scratch, scratch_bytes);
+}
+
+extern "C" int c2w_sq_err_noise_det(const void* y, unsigned long long seed, float* out, float* loss_sum, int B, int C, int HW, int ldc,
+                                    float* scratch, unsigned long long scratch_bytes, int dtype, void* stream) {
+    return sq_err_launch(y, nullptr, seed, true, out, loss_sum, B, C, HW, ldc, dtype, stream, true, scratch, scratch_bytes);
 }
 
 extern "C" int c2w_sq_err(const void* y, const float* eps, float* out, float* loss_sum, int B, int C, int HW, int ldc, int dtype, void* stream) {

@@ -35,6 +35,10 @@ struct WgradArgs {
     int nsplit, ktiles_per_split;
     FastDiv div_hw, div_w;
     float* ws;  // optional scratch [split][tile][COT][4*CIB] fp32 for the partial sums (else fp32 atomics)
+    // deterministic mode (C2W_CONV_DETERMINISTIC), as in wgrad_patch.hip: wsb != nullptr: bias rows [split][tilesM * COT] behind the partial
+    // tiles, added in a fixed order by extra blocks of the reduce launch (det_reduce_body); wsb == nullptr (no split): plain read-modify-write of db
+    float* wsb;
+    int det;
 };
 
 __device__ __forceinline__ uint32_t swz(int row) { return (uint32_t)(((row & 3) << 2) | ((row >> 2) & 3)); }
@@ -54,6 +58,7 @@ struct WgradGroupArgs {
     WgradArgs c;  // geometry, split plan, ws = base of the group's workspace
     int n, live_per_item;
     unsigned long long ws_item_floats;
+    unsigned long long wsb_item_floats;  // bias rows of one layer (deterministic mode)
     WgItem item[WG_MAX_ITEMS];
 };
 
@@ -284,8 +289,14 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p, const int L) {
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wm * (COT / 2) + m * 16 + lg * 4 + r;
-                if (co < p.Cout) atomicAdd(p.db + co, accb[m][r]);
+                const int row = wm * (COT / 2) + m * 16 + lg * 4 + r;
+                const int co = co0 + row;
+                if (p.det) {  // kernel argument: uniform
+                    if (p.wsb != nullptr) p.wsb[((size_t)split * tilesM + tm) * COT + row] = accb[m][r];
+                    else if (co < p.Cout) p.db[co] = p.db[co] + accb[m][r];
+                } else if (co < p.Cout) {
+                    atomicAdd(p.db + co, accb[m][r]);
+                }
             }
     }
     if (p.ws != nullptr) {  // partial tile by coalesced stores; wgrad_gather_reduce_kernel adds the splits into dw
@@ -334,20 +345,33 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_group_kernel(const WgradGro
     p.dw = e.dw;
     p.db = e.db;
     p.ws = g.c.ws != nullptr ? g.c.ws + (size_t)it * g.ws_item_floats : nullptr;
+    p.wsb = g.c.wsb != nullptr ? g.c.wsb + (size_t)it * g.wsb_item_floats : nullptr;
     wgrad_body<T, MODE>(p, Lg - it * g.live_per_item);
+}
+
+// the bias part of a reduce launch (deterministic mode; wsb == nullptr: none, nmain = the whole grid), as in wgrad_patch.hip
+struct WgradBiasReduce {
+    const float* wsb;  // [split][cols] bias rows of the launch (grouped: of layer 0; layers wsb_item_floats apart)
+    float* db;
+    int cols, tpo, nmain;
+};
+static inline WgradBiasReduce bias_reduce_of(const float* wsb, float* db, int cols, int nsplit, int nmain) {
+    WgradBiasReduce br;
+    br.wsb = wsb; br.db = db; br.cols = cols; br.tpo = det_reduce_tpo(nsplit); br.nmain = nmain;
+    return br;
 }
 
 // dw += sum over splits of the partial tiles (same 64 x 4 layout of a block as wgrad_reduce_kernel in wgrad_patch.hip)
 template <int COT, int CIB, int NT>
 __device__ __forceinline__ void wgrad_gather_reduce_body(const float* __restrict__ ws, float* __restrict__ dw, int nsplit, int tilesM,
-                                                         int tilesN, int Cin, int Cout) {
+                                                         int tilesN, int Cin, int Cout, int nblk) {  // nblk: blocks that share the sweep
     constexpr int NCOL = 4 * CIB;
     __shared__ f32x4_t red[4][64];
     const size_t per4 = (size_t)tilesM * tilesN * COT * NCOL / 4;
     const f32x4_t* ws4 = (const f32x4_t*)ws;
     const int q = threadIdx.x & 63, grp = threadIdx.x >> 6;
     const int cib_per_tap = Cin / CIB, nb_total = NT * cib_per_tap;
-    for (size_t base = (size_t)blockIdx.x * 64; base < per4; base += (size_t)gridDim.x * 64) {
+    for (size_t base = (size_t)blockIdx.x * 64; base < per4; base += (size_t)nblk * 64) {
         const size_t i4 = base + q;
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         if (i4 < per4) {
@@ -380,14 +404,23 @@ __device__ __forceinline__ void wgrad_gather_reduce_body(const float* __restrict
 
 template <int COT, int CIB, int NT>
 __global__ __launch_bounds__(256) void wgrad_gather_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nsplit, int tilesM,
-                                                                  int tilesN, int Cin, int Cout) {
-    wgrad_gather_reduce_body<COT, CIB, NT>(ws, dw, nsplit, tilesM, tilesN, Cin, Cout);
+                                                                  int tilesN, int Cin, int Cout, WgradBiasReduce br) {
+    if ((int)blockIdx.x >= br.nmain) {  // deterministic mode: extra blocks that add the splits' bias rows onto db
+        det_reduce_body(br.wsb, br.db, nsplit, Cout, Cout, 0, br.tpo, br.cols, (int)blockIdx.x - br.nmain);
+        return;
+    }
+    wgrad_gather_reduce_body<COT, CIB, NT>(ws, dw, nsplit, tilesM, tilesN, Cin, Cout, br.nmain);
 }
 template <int COT, int CIB, int NT>
-__global__ __launch_bounds__(256) void wgrad_gather_reduce_group_kernel(const WgradGroupArgs g, int nsplit, int tilesM, int tilesN) {
+__global__ __launch_bounds__(256) void wgrad_gather_reduce_group_kernel(const WgradGroupArgs g, int nsplit, int tilesM, int tilesN, WgradBiasReduce br) {
     const int it = (int)blockIdx.y;
     const WgItem e = wg_item(it);
-    wgrad_gather_reduce_body<COT, CIB, NT>(g.c.ws + (size_t)it * g.ws_item_floats, e.dw, nsplit, tilesM, tilesN, g.c.Cin, g.c.Cout);
+    if ((int)blockIdx.x >= br.nmain) {  // deterministic mode: the bias rows of layer `it`
+        if (e.db != nullptr)  // (uniform over the block)
+            det_reduce_body(g.c.wsb + (size_t)it * g.wsb_item_floats, e.db, nsplit, g.c.Cout, g.c.Cout, 0, br.tpo, br.cols, (int)blockIdx.x - br.nmain);
+        return;
+    }
+    wgrad_gather_reduce_body<COT, CIB, NT>(g.c.ws + (size_t)it * g.ws_item_floats, e.dw, nsplit, tilesM, tilesN, g.c.Cin, g.c.Cout, br.nmain);
 }
 
 FastDiv make_div(uint32_t d) {
@@ -423,7 +456,8 @@ static size_t ws_need(const C2wConvArgs& a) {
     constexpr int COT = 256 / ESZ, CIB = 128 / ESZ;
     int tilesM, tilesN, nsplit, per;
     split_plan<ESZ, NT>(a, tilesM, tilesN, nsplit, per);
-    return nsplit > 1 ? (size_t)nsplit * tilesM * tilesN * COT * 4 * CIB * sizeof(float) : 0;
+    const size_t bias_rows = (a.flags & C2W_CONV_DETERMINISTIC) ? (size_t)nsplit * tilesM * COT * sizeof(float) : 0;
+    return nsplit > 1 ? (size_t)nsplit * tilesM * tilesN * COT * 4 * CIB * sizeof(float) + bias_rows : 0;
 }
 
 template <typename T, int MODE>
@@ -448,12 +482,20 @@ int launch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_t ws_byte
         attr_set = true;
     }
     const size_t need = (size_t)p.nsplit * tilesMN * COT * 4 * CIB * sizeof(float);
+    p.det = (a.flags & C2W_CONV_DETERMINISTIC) ? 1 : 0;
+    if (p.det) {  // never a silent fall-back to atomics: the knob is refused, the workspace must be what c2w_conv_wgrad_workspace_bytes asks for
+        if (c2w_knobs().wgrad_atomics) return C2W_ERR_BAD_ARG;
+        if (p.nsplit > 1 && (ws == nullptr || need + (size_t)p.nsplit * tilesM * COT * sizeof(float) > ws_bytes)) return C2W_ERR_BAD_ARG;
+    }
     p.ws = (ws != nullptr && need <= ws_bytes && p.nsplit > 1 && !c2w_knobs().wgrad_atomics) ? ws : nullptr;
+    p.wsb = p.det && p.nsplit > 1 && db != nullptr ? ws + need / sizeof(float) : nullptr;
     wgrad_kernel<T, MODE><<<tilesMN * p.nsplit, NTHREADS, lds, st>>>(p);
     if (p.ws != nullptr) {
         const size_t per4 = (size_t)tilesMN * COT * 4 * CIB / 4;
         const int grid = (int)((per4 + 63) / 64 < 4096 ? (per4 + 63) / 64 : 4096);
-        wgrad_gather_reduce_kernel<COT, CIB, NT><<<grid, 256, 0, st>>>(p.ws, dw, p.nsplit, tilesM, tilesN, a.Cin, a.Cout);
+        const int extra = p.wsb != nullptr ? det_reduce_blocks(p.nsplit, a.Cout) : 0;
+        wgrad_gather_reduce_kernel<COT, CIB, NT><<<grid + extra, 256, 0, st>>>(p.ws, dw, p.nsplit, tilesM, tilesN, a.Cin, a.Cout,
+                                                                               bias_reduce_of(p.wsb, db, tilesM * COT, p.nsplit, grid));
     }
     return (int)hipGetLastError();
 }
@@ -485,7 +527,8 @@ static size_t gather_group_ws_need(const C2wConvArgs& a, int n) {
     split_plan<ESZ, NT>(a, tilesM, tilesN, ns1, per1);
     const long long npix = (long long)a.B * a.Hout * a.Wout;
     gather_group_plan(n, tilesM * tilesN, (int)((npix + KT - 1) / KT), nsplit, per);
-    return nsplit > 1 ? (size_t)n * nsplit * tilesM * tilesN * COT * 4 * CIB * sizeof(float) : 0;
+    const size_t bias_rows = (a.flags & C2W_CONV_DETERMINISTIC) ? (size_t)n * nsplit * tilesM * COT * sizeof(float) : 0;
+    return nsplit > 1 ? (size_t)n * nsplit * tilesM * tilesN * COT * 4 * CIB * sizeof(float) + bias_rows : 0;
 }
 
 template <typename T, int MODE>
@@ -505,7 +548,11 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
     p.div_hw = make_div((uint32_t)(a.Hout * a.Wout));
     p.div_w = make_div((uint32_t)a.Wout);
     const size_t item_floats = (size_t)p.nsplit * tilesMN * COT * 4 * CIB;
-    if (p.nsplit > 1 && (ws == nullptr || (size_t)n * item_floats * sizeof(float) > ws_bytes)) return C2W_ERR_BAD_ARG;
+    p.det = (a.flags & C2W_CONV_DETERMINISTIC) ? 1 : 0;
+    const size_t bias_item_floats = p.det ? (size_t)p.nsplit * tilesM * COT : 0;
+    if (p.nsplit > 1 && (ws == nullptr || (size_t)n * (item_floats + bias_item_floats) * sizeof(float) > ws_bytes)) return C2W_ERR_BAD_ARG;
+    p.wsb = p.det && p.nsplit > 1 ? ws + (size_t)n * item_floats : nullptr;
+    g.wsb_item_floats = bias_item_floats;
     p.ws = p.nsplit > 1 ? ws : nullptr;  // no split: one workgroup per output tile, its atomics onto dw have no partner (deterministic)
     g.n = n;
     g.live_per_item = tilesMN * p.nsplit;
@@ -526,7 +573,9 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
     if (p.ws != nullptr) {
         const size_t per4 = (size_t)tilesMN * COT * 4 * CIB / 4;
         const int grid = (int)((per4 + 63) / 64 < 4096 ? (per4 + 63) / 64 : 4096);
-        wgrad_gather_reduce_group_kernel<COT, CIB, NT><<<dim3(grid, n), 256, 0, st>>>(g, p.nsplit, tilesM, tilesN);
+        const int extra = p.wsb != nullptr ? det_reduce_blocks(p.nsplit, a.Cout) : 0;
+        wgrad_gather_reduce_group_kernel<COT, CIB, NT><<<dim3(grid + extra, n), 256, 0, st>>>(g, p.nsplit, tilesM, tilesN,
+                                                                                              bias_reduce_of(p.wsb, nullptr, tilesM * COT, p.nsplit, grid));
     }
     return (int)hipGetLastError();
 }

@@ -57,6 +57,11 @@ struct WpArgs {
     int ktiles, ktiles_per_split;
     float* ws;  // optional workspace [split][tile][tap][COT][CIB] fp32: partial sums by plain stores, reduced by a second launch
     int direct;  // no split (one workgroup per output tile): the tile is added onto dw by plain read-modify-write stores, no atomics
+    // deterministic mode (C2W_CONV_DETERMINISTIC): no atomics onto db either.  wsb != nullptr: the workgroup stores its column sums as row
+    // `split` of [split][tilesM * COT] fp32 (behind the partial tiles in the workspace), extra blocks of the reduce launch add the rows in
+    // a fixed order (det_reduce_body); wsb == nullptr (no split: one workgroup per channel): plain read-modify-write
+    float* wsb;
+    int det;
 };
 
 // Grouped launch: the weight gradients of up to WP_MAX_ITEMS layers of ONE geometry (the residual-block convs of a level: their output
@@ -77,6 +82,7 @@ struct WpGroupArgs {
     int n;                // layers
     int live_per_item;    // workgroups per layer = tilesMN * nsplit; the grid is n * live_per_item
     unsigned long long ws_item_floats;
+    unsigned long long wsb_item_floats;  // bias rows of one layer (deterministic mode)
     WpItem item[WP_MAX_ITEMS];
 };
 
@@ -390,8 +396,14 @@ __device__ __forceinline__ void wgrad_patch_body(const WpArgs& p, const int L) {
         for (int m = 0; m < MTW; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int co = co0 + (mt0 + m) * 16 + lg * 4 + r;
-                if (co < p.Cout) atomicAdd(p.db + co, accb[m][r]);
+                const int row = (mt0 + m) * 16 + lg * 4 + r;
+                const int co = co0 + row;
+                if (p.det) {  // kernel argument: uniform
+                    if (p.wsb != nullptr) p.wsb[((size_t)split * tilesM + tm) * COT + row] = accb[m][r];
+                    else if (co < p.Cout) p.db[co] = p.db[co] + accb[m][r];
+                } else if (co < p.Cout) {
+                    atomicAdd(p.db + co, accb[m][r]);
+                }
             }
     }
     constexpr int OS = CIB + 4;
@@ -457,7 +469,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_patch_group_kernel(const Wp
     p.dw = e.dw;
     p.db = e.db;
     p.ws = g.c.ws != nullptr ? g.c.ws + (size_t)it * g.ws_item_floats : nullptr;
+    p.wsb = g.c.wsb != nullptr ? g.c.wsb + (size_t)it * g.wsb_item_floats : nullptr;
     wgrad_patch_body<T, PAIR, false>(p, L);
+}
+
+// the bias part of a reduce launch (deterministic mode; wsb == nullptr: none, nmain = the whole grid)
+struct WgradBiasReduce {
+    const float* wsb;  // [split][cols] bias rows of the launch (grouped: of layer 0; layers wsb_item_floats apart)
+    float* db;
+    int cols, tpo, nmain;
+};
+static inline WgradBiasReduce bias_reduce_of(const float* wsb, float* db, int cols, int nsplit, int nmain) {
+    WgradBiasReduce br;
+    br.wsb = wsb; br.db = db; br.cols = cols; br.tpo = det_reduce_tpo(nsplit); br.nmain = nmain;
+    return br;
 }
 
 // dw[co][tap][ci] += sum over splits of ws[split][tile][tap][row][col].  RC float4 columns x RG split groups per block (RC * RG =
@@ -469,13 +494,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_patch_group_kernel(const Wp
 #endif
 template <int COT, int CIB>
 __device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ ws, float* __restrict__ dw, int nsplit, int tilesMN, int ncib,
-                                                  int Cin, int Cout) {
+                                                  int Cin, int Cout, int nblk) {  // nblk: blocks that share the sweep (= the grid but for the bias blocks)
     constexpr int RC = C2W_RED_COLS, RG = 256 / RC;
     __shared__ f32x4_t red[RG][RC];
     const size_t per4 = (size_t)tilesMN * 9 * COT * CIB / 4;  // float4 vectors per split
     const f32x4_t* ws4 = (const f32x4_t*)ws;
     const int q = threadIdx.x % RC, grp = threadIdx.x / RC;
-    for (size_t base = (size_t)blockIdx.x * RC; base < per4; base += (size_t)gridDim.x * RC) {
+    for (size_t base = (size_t)blockIdx.x * RC; base < per4; base += (size_t)nblk * RC) {
         const size_t i4 = base + q;
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         if (i4 < per4) {
@@ -507,15 +532,26 @@ __device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ ws, 
 
 template <int COT, int CIB>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nsplit, int tilesMN, int ncib,
-                                                           int Cin, int Cout) {
-    wgrad_reduce_body<COT, CIB>(ws, dw, nsplit, tilesMN, ncib, Cin, Cout);
+                                                           int Cin, int Cout, WgradBiasReduce br) {
+    // deterministic mode: the launch carries extra blocks behind the first br.nmain that add the splits' bias rows onto db (default
+    // mode: nmain = the grid)
+    if ((int)blockIdx.x >= br.nmain) {
+        det_reduce_body(br.wsb, br.db, nsplit, Cout, Cout, 0, br.tpo, br.cols, (int)blockIdx.x - br.nmain);
+        return;
+    }
+    wgrad_reduce_body<COT, CIB>(ws, dw, nsplit, tilesMN, ncib, Cin, Cout, br.nmain);
 }
 // the same for every layer of a grouped launch: blockIdx.y = layer
 template <int COT, int CIB>
-__global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const WpGroupArgs g, int nsplit, int tilesMN, int ncib) {
+__global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const WpGroupArgs g, int nsplit, int tilesMN, int ncib, WgradBiasReduce br) {
     const int it = (int)blockIdx.y;
     const WpItem e = wp_item(it);
-    wgrad_reduce_body<COT, CIB>(g.c.ws + (size_t)it * g.ws_item_floats, e.dw, nsplit, tilesMN, ncib, g.c.Cin, g.c.Cout);
+    if ((int)blockIdx.x >= br.nmain) {  // deterministic mode: the bias rows of layer `it` (see wgrad_reduce_kernel)
+        if (e.db != nullptr)  // (uniform over the block: every thread reaches the barrier inside, or none)
+            det_reduce_body(g.c.wsb + (size_t)it * g.wsb_item_floats, e.db, nsplit, g.c.Cout, g.c.Cout, 0, br.tpo, br.cols, (int)blockIdx.x - br.nmain);
+        return;
+    }
+    wgrad_reduce_body<COT, CIB>(g.c.ws + (size_t)it * g.ws_item_floats, e.dw, nsplit, tilesMN, ncib, g.c.Cin, g.c.Cout, br.nmain);
 }
 
 // split of the K (pixel-tile) range over workgroups: one resident workgroup per CU and ONE round: tilesMN * nsplit <= 256 (rounding
@@ -538,7 +574,8 @@ static size_t ws_need(const C2wConvArgs& a) {
     constexpr int COT = 256 / ESZ, CIB = 128 / ESZ;
     int ktiles, tilesMN, nsplit, per;
     split_plan<ESZ, PAIR>(a, ktiles, tilesMN, nsplit, per);
-    return nsplit > 1 ? (size_t)nsplit * tilesMN * 9 * COT * CIB * sizeof(float) : 0;
+    const size_t bias_rows = (a.flags & C2W_CONV_DETERMINISTIC) ? (size_t)nsplit * ((a.Cout + COT - 1) / COT) * COT * sizeof(float) : 0;
+    return nsplit > 1 ? (size_t)nsplit * tilesMN * 9 * COT * CIB * sizeof(float) + bias_rows : 0;
 }
 
 template <typename T, bool PAIR, bool NARROW = false>
@@ -557,13 +594,22 @@ int launch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_t ws_byte
         attr_set = true;
     }
     const size_t need = (size_t)nsplit * tilesMN * 9 * COT * CIB * sizeof(float);
+    const int bias_cols = (tilesMN / (a.Cin / CIB)) * COT;
+    p.det = (a.flags & C2W_CONV_DETERMINISTIC) ? 1 : 0;
+    if (p.det) {  // never a silent fall-back to atomics: the knob is refused, the workspace must be what c2w_conv_wgrad_workspace_bytes asks for
+        if (c2w_knobs().wgrad_atomics) return C2W_ERR_BAD_ARG;
+        if (nsplit > 1 && (ws == nullptr || need + (size_t)nsplit * bias_cols * sizeof(float) > ws_bytes)) return C2W_ERR_BAD_ARG;
+    }
     p.ws = (ws != nullptr && need <= ws_bytes && nsplit > 1 && !c2w_knobs().wgrad_atomics) ? ws : nullptr;
+    p.wsb = p.det && nsplit > 1 && db != nullptr ? ws + need / sizeof(float) : nullptr;
     p.direct = nsplit == 1 && !c2w_knobs().wgrad_atomics ? 1 : 0;
     wgrad_patch_kernel<T, PAIR, NARROW><<<tilesMN * nsplit, NTHREADS, LDS_BYTES, st>>>(p);
     if (p.ws != nullptr) {
         const size_t per_split = (size_t)tilesMN * 9 * COT * CIB;
         const int grid = (int)std::min<size_t>((per_split / 4 + C2W_RED_COLS - 1) / C2W_RED_COLS, 8192);
-        wgrad_reduce_kernel<COT, CIB><<<grid, 256, 0, st>>>(p.ws, dw, nsplit, tilesMN, a.Cin / CIB, a.Cin, a.Cout);
+        const int extra = p.wsb != nullptr ? det_reduce_blocks(nsplit, a.Cout) : 0;
+        wgrad_reduce_kernel<COT, CIB><<<grid + extra, 256, 0, st>>>(p.ws, dw, nsplit, tilesMN, a.Cin / CIB, a.Cin, a.Cout,
+                                                                    bias_reduce_of(p.wsb, db, bias_cols, nsplit, grid));
     }
     return (int)hipGetLastError();
 }
@@ -599,7 +645,8 @@ static size_t group_ws_need(const C2wConvArgs& a, int n) {
     int ktiles, tilesMN, ns1, per1, nsplit, per;
     split_plan<ESZ, PAIR>(a, ktiles, tilesMN, ns1, per1);
     group_plan(n, tilesMN, ktiles, nsplit, per);
-    return nsplit > 1 ? (size_t)n * nsplit * tilesMN * 9 * COT * CIB * sizeof(float) : 0;
+    const size_t bias_rows = (a.flags & C2W_CONV_DETERMINISTIC) ? (size_t)n * nsplit * ((a.Cout + COT - 1) / COT) * COT * sizeof(float) : 0;
+    return nsplit > 1 ? (size_t)n * nsplit * tilesMN * 9 * COT * CIB * sizeof(float) + bias_rows : 0;
 }
 
 template <typename T, bool PAIR>
@@ -615,8 +662,13 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
     split_plan<ESZ, PAIR>(a, p.ktiles, tilesMN, ns1, per1);
     group_plan(n, tilesMN, p.ktiles, nsplit, p.ktiles_per_split);
     const size_t item_floats = (size_t)nsplit * tilesMN * 9 * COT * CIB;
-    if (nsplit > 1 && (ws == nullptr || (size_t)n * item_floats * sizeof(float) > ws_bytes)) return C2W_ERR_BAD_ARG;  // the caller sized it with c2w_conv_wgrad_grouped_workspace_bytes
+    const int bias_cols = (tilesMN / (a.Cin / CIB)) * COT;
+    p.det = (a.flags & C2W_CONV_DETERMINISTIC) ? 1 : 0;
+    const size_t bias_item_floats = p.det ? (size_t)nsplit * bias_cols : 0;
+    if (nsplit > 1 && (ws == nullptr || (size_t)n * (item_floats + bias_item_floats) * sizeof(float) > ws_bytes)) return C2W_ERR_BAD_ARG;  // the caller sized it with c2w_conv_wgrad_grouped_workspace_bytes
     p.ws = nsplit > 1 ? ws : nullptr;
+    p.wsb = p.det && nsplit > 1 ? ws + (size_t)n * item_floats : nullptr;
+    g.wsb_item_floats = bias_item_floats;
     p.direct = nsplit == 1 ? 1 : 0;
     g.n = n;
     g.live_per_item = tilesMN * nsplit;
@@ -634,7 +686,9 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
     if (p.ws != nullptr) {
         const size_t per_split = (size_t)tilesMN * 9 * COT * CIB;
         const int grid = (int)std::min<size_t>((per_split / 4 + C2W_RED_COLS - 1) / C2W_RED_COLS, 8192);
-        wgrad_reduce_group_kernel<COT, CIB><<<dim3(grid, n), 256, 0, st>>>(g, nsplit, tilesMN, a.Cin / CIB);
+        const int extra = p.wsb != nullptr ? det_reduce_blocks(nsplit, a.Cout) : 0;
+        wgrad_reduce_group_kernel<COT, CIB><<<dim3(grid + extra, n), 256, 0, st>>>(g, nsplit, tilesMN, a.Cin / CIB,
+                                                                                   bias_reduce_of(p.wsb, nullptr, bias_cols, nsplit, grid));
     }
     return (int)hipGetLastError();
 }

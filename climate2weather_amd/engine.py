@@ -258,6 +258,13 @@ class Engine:
         self._pub = None  # ops.HostRing of published scalars (publish / published)
         self._skip_dw = False  # inside backward(want_dw=False): weight-gradient launches are skipped
         self._ws: Dict[int, torch.Tensor] = {}  # stream handle -> split-K scratch of the weight-gradient launches on that stream
+        # Deterministic mode (opt-in; C2W_DETERMINISTIC=1 sets the default, Trainer(deterministic=...) / ScoreUNet.deterministic the
+        # engine's): the bias gradients, the LayerNorm modulation gradients and the loss sum -- everything a training step adds up with
+        # fp32 atomics -- go through per-stream scratch buffers in a fixed order instead (include/c2w_hip.h, C2W_CONV_DETERMINISTIC).
+        # Off: no launch, no ops.* call and no keyword argument differs from before.
+        self.deterministic = os.environ.get("C2W_DETERMINISTIC", "0") not in ("", "0")
+        self._det_ws: Dict[int, torch.Tensor] = {}  # stream handle -> scratch of the fixed-order reductions on that stream
+        self._det_need: Dict[tuple, int] = {}  # (kind, geometry, dtype, knobs) -> bytes (pure size queries, asked once)
         self._splitk_plans: Dict[tuple, tuple] = {}  # conv geometry -> (workgroups per tile, scratch bytes) (_splitk)
         self.debug_trace: Optional[list] = None  # diagnostics: a list collects (name, output tensor[, operands of a conv]) of every conv / attention launch of a forward
         self.attach(net)
@@ -619,13 +626,48 @@ class Engine:
         stream next to an exact-guidance backward elsewhere), never see each other's partial sums.  ``min_bytes``: a grouped launch's
         need (ops.conv_wgrad_grouped_workspace_bytes); a larger buffer replaces the stream's (the old one is freed behind the launches
         that used it: same stream)."""
-        if self.flat is None or not self.flat.is_cuda:
+        if self.flat is None or not (self.flat.is_cuda or self.deterministic):
             return None
-        key = torch.cuda.current_stream(self.flat.device).cuda_stream
+        # (CPU tensors -- the emulated tier of the tests -- have no split to hold; the deterministic mode's bias rows live here too)
+        key = torch.cuda.current_stream(self.flat.device).cuda_stream if self.flat.is_cuda else 0
         ws = self._ws.get(key)
         if ws is None or ws.device != self.flat.device or ws.numel() * 4 < min_bytes:
             ws = self._ws[key] = ops.new_workspace(self.flat.device, max(ops.WORKSPACE_BYTES, (min_bytes + (1 << 20) - 1) >> 20 << 20))
         return ws
+
+    # ------------------------------------------------------------------ deterministic mode: scratch sizes and buffers
+    def _det_bytes(self, key: tuple, query) -> int:
+        key = key + (ops.KNOBS_GENERATION,)
+        n = self._det_need.get(key)
+        if n is None:
+            n = self._det_need[key] = int(query())
+        return n
+
+    def det_scratch(self, nbytes: int) -> torch.Tensor:
+        """Scratch of a fixed-order reduction launched on torch's CURRENT stream (one buffer per stream, like ``workspace``; it only
+        grows, so a training run allocates it during its first step and never again)."""
+        key = torch.cuda.current_stream(self.flat.device).cuda_stream if self.flat.is_cuda else 0
+        ws = self._det_ws.get(key)
+        if ws is None or ws.device != self.flat.device or ws.numel() * 4 < nbytes:
+            ws = self._det_ws[key] = torch.empty(max((nbytes + 3) // 4, 1 << 16), dtype=torch.float32, device=self.flat.device)
+        return ws
+
+    def loss_det_kw(self) -> dict:
+        """Keyword arguments of the loss launchers (ops.mse_loss_grad, mse_loss_grad_noise, sq_err): nothing unless the mode is on."""
+        if not self.deterministic:
+            return {}
+        return dict(det=self.det_scratch(self._det_bytes(("loss",), ops.loss_det_scratch_bytes)))
+
+    @staticmethod
+    def _gkey(g: dict) -> tuple:
+        return (g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"], g["wrows"], g["mode"])
+
+    def _wgrad_kw(self, g: dict, dt: int) -> dict:
+        """workspace (+ deterministic) arguments of one ops.conv_wgrad launch on the current stream"""
+        if not self.deterministic:
+            return dict(workspace=self.workspace())
+        need = self._det_bytes(("wgrad", self._gkey(g), dt), lambda: ops.conv_wgrad_workspace_bytes(g, dt, deterministic=True))
+        return dict(workspace=self.workspace(need), deterministic=True)
 
     def _splitk(self, g: dict, dt: int, act: int):
         """(scratch, workgroups per tile) if this inference launch should deal its K chunks to several workgroups (ops.conv_splitk_plan:
@@ -670,7 +712,7 @@ class Engine:
                     if not self._wg_groups:
                         self._release_done()
                 return
-        self._on_grad_stream(lambda: ops.conv_wgrad(x, gy, self._gw(rec), g, dt, dbias=self._gb(rec), workspace=self.workspace()), x, gy)
+        self._on_grad_stream(lambda: ops.conv_wgrad(x, gy, self._gw(rec), g, dt, dbias=self._gb(rec), **self._wgrad_kw(g, dt)), x, gy)
 
     def _flush_group(self, key: tuple) -> None:
         lst = self._wg_groups.pop(key, None)
@@ -680,12 +722,13 @@ class Engine:
         if len(lst) == 1 or not ops.conv_wgrad_grouped_supported(g, len(lst), dt):
             for x, gy, rec, gi in lst:
                 self._on_grad_stream(lambda x=x, gy=gy, rec=rec, gi=gi: ops.conv_wgrad(x, gy, self._gw(rec), gi, dt, dbias=self._gb(rec),
-                                                                                    workspace=self.workspace()), x, gy)
+                                                                                    **self._wgrad_kw(gi, dt)), x, gy)
             return
 
         def run():
-            ws = self.workspace(ops.conv_wgrad_grouped_workspace_bytes(g, len(lst), dt))
-            ops.conv_wgrad_grouped([(x, gy, self._gw(rec), self._gb(rec)) for x, gy, rec, _ in lst], g, dt, workspace=ws)
+            kw = dict(deterministic=True) if self.deterministic else {}
+            ws = self.workspace(ops.conv_wgrad_grouped_workspace_bytes(g, len(lst), dt, **kw))
+            ops.conv_wgrad_grouped([(x, gy, self._gw(rec), self._gb(rec)) for x, gy, rec, _ in lst], g, dt, workspace=ws, **kw)
         self._on_grad_stream(run, *[t for x, gy, _, _ in lst for t in (x, gy)])
 
     def flush_wgrad_groups(self) -> None:
@@ -713,7 +756,7 @@ class Engine:
                 buf = self._gwpad[rec.name] = torch.zeros(n, dtype=torch.float32, device=self.flat.device)
             else:
                 buf.zero_()
-            ops.conv_wgrad(x, gy, buf, g, dt, dbias=self._gb(rec), workspace=self.workspace())
+            ops.conv_wgrad(x, gy, buf, g, dt, dbias=self._gb(rec), **self._wgrad_kw(g, dt))
             self.flat_grad[rec.w_off: rec.w_off + rec.rows * rec.taps * rec.cin].view(rec.rows, rec.taps, rec.cin).add_(
                 buf.view(rec.rows, rec.taps, rec.kstride)[:, :, : rec.cin])
         self._on_grad_stream(run, x, gy)
@@ -752,7 +795,7 @@ class Engine:
                     gt = self._geom(rec.rows, 1, 1, rec.cin, 1, 1, rows, ld, rows, CONV_1X1)
                     # same kernels, same split-K workspace as the weight gradients: same stream, then wait for the result
                     wmat = self._w(rec, DTYPE_F32)
-                    self._on_grad_stream(lambda: ops.conv_wgrad(wmat, gyT, dx, gt, DTYPE_F32, workspace=self.workspace()), gyT, dx)
+                    self._on_grad_stream(lambda: ops.conv_wgrad(wmat, gyT, dx, gt, DTYPE_F32, **self._wgrad_kw(gt, DTYPE_F32)), gyT, dx)
                     self.join_grad_stream()
                     # only now: this route reads the layer's weights from the flat buffer itself, and "done" may start the
                     # optimizer on them (Trainer: the update chases the backward)
@@ -908,8 +951,11 @@ class Engine:
             # padded operand (network input at C = 65: rows of 128 channels): channels >= rec.cin are zero in x and in w -- a promise the
             # 16x16-tile kernel turns into fewer K steps
             wop, wpk = self._conv_weights("f", rec, dt, g)
+            kw = {}
+            if loss is not None and self.deterministic:  # the workgroups' loss sums in a fixed order
+                kw["det"] = self.det_scratch(self._det_bytes(("conv_loss", self._gkey(g), dt), lambda: ops.conv_det_scratch_bytes(g, dt, loss=True)))
             ops.conv(xin, wop, self._b(rec), y if y is not None else hn, g, dt, act=act, res=res, y2=y2, lnf=lnf,
-                     kvalid=rec.cin if rec.kstride != rec.cin else 0, wpacked=wpk, loss=loss, resn=resn, no_y=no_y,
+                     kvalid=rec.cin if rec.kstride != rec.cin else 0, wpacked=wpk, loss=loss, resn=resn, no_y=no_y, **kw,
                      splitk=self._splitk(g, dt, act) if (not train and lnf is None and y2 is None and loss is None and not wpk) else None)
             if self.debug_trace is not None and y is not None:
                 self.debug_trace.append((name, y, dict(x=xin, w=self._w(rec, dt), g=g, act=act, res=res)))
@@ -929,8 +975,12 @@ class Engine:
             # output conv at C = 65: gy rows are padded to dg_ld = 128 channels, the padding is zero (mse_loss_grad) and so are the
             # operand's columns there
             wop, wpk = self._conv_weights("d", rec, dt, g, fused_ln_bwd=ln is not None)
+            kw = {}
+            if ln is not None and ln.get("dm") is not None and self.deterministic:  # the modulation gradient in a fixed order
+                kw["det"] = self.det_scratch(self._det_bytes(("conv_ln", self._gkey(g), dt, ln["ldm"]),
+                                                             lambda: ops.conv_det_scratch_bytes(g, dt, ln_ldm=ln["ldm"])))
             ops.conv(gy, wop, None, dx, g, dt, res=res, mul=mul, mulmode=mulmode, ln=ln,
-                     kvalid=rec.rows if rec.dg_ld != rec.rows else 0, wpacked=wpk)
+                     kvalid=rec.rows if rec.dg_ld != rec.rows else 0, wpacked=wpk, **kw)
             return dx
 
         def res_block(b: BlockSpec, xin, Hc, Wc, h0=None, want_ln=None, elide=False):
@@ -979,7 +1029,11 @@ class Engine:
                         assert xin is not None, "chain form: the fused LayerNorm backward this block was built on is gone (knobs changed between forward and backward?)"
                         dh0 = dgrad(r1, da1, Hc, Wc, Hc, Wc, CONV_S1, Cc)
                         dx = torch.empty_like(dh0)
-                        ops.ln_backward(dh0, xin, m, gy, dx, dm, npix, Hc * Wc, Cc, ldm, LN_EPS, self.ln_unbiased, dt)
+                        kw = {}
+                        if self.deterministic:
+                            kw["det"] = self.det_scratch(self._det_bytes(("ln", npix, Hc * Wc, Cc, ldm),
+                                                                         lambda: ops.ln_backward_det_scratch_bytes(npix, Hc * Wc, Cc, ldm)))
+                        ops.ln_backward(dh0, xin, m, gy, dx, dm, npix, Hc * Wc, Cc, ldm, LN_EPS, self.ln_unbiased, dt, **kw)
                     tape.done(r1.w_off)  # behind the block's last launch: "done" = gradients final AND weights (copies included) no longer read
                     return dx
                 tape.steps.append(bw)

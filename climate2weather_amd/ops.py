@@ -54,14 +54,19 @@ def _conv_args(x, w, bias, res, mul, y, g, act, mulmode, y2=None, ln=None, lnf=N
 
 def conv(x, w, bias, y, g: dict, dtype: int, act: int = ACT_NONE, res=None, mul=None, mulmode: int = MUL_PLAIN, naive=False, y2=None,
          ln=None, lnf=None, pool2: bool = False, kvalid: int = 0, wpacked: bool = False, loss: Optional[dict] = None,
-         resn: Optional[dict] = None, no_y: bool = False, splitk: Optional[tuple] = None):
+         resn: Optional[dict] = None, no_y: bool = False, splitk: Optional[tuple] = None, det: Optional[torch.Tensor] = None):
     """c2w_conv_forward.  g: geometry dict(B,Hin,Win,Cin,Hout,Wout,Cout,ldy,wrows,mode).
     ln = dict(x, m, dm, ldm, eps, unbiased[, rstd]): fuse the LayerNorm backward into the epilogue (y = res + dLN(conv; x + m),
     dm accumulated) -- only where conv_lnbwd_supported(g, dtype) says so.  With ``rstd`` (what the forward's lnf kept), ``x`` holds the
     NORMALISED rows and ``m`` is not read.
     lnf = dict(y, m, ldm, eps, unbiased[, rstd]): also write y = LN(result + m), the consumer block's normalised input (and, with
-    ``rstd``, every pixel row's 1/sigma) -- only where conv_lnfwd_supported(g, dtype) says so."""
+    ``rstd``, every pixel row's 1/sigma) -- only where conv_lnfwd_supported(g, dtype) says so.
+    det: deterministic mode -- the fp32 scratch tensor (>= conv_det_scratch_bytes) the fused epilogue's sums onto ln["dm"] / loss["sum"]
+    go through in a fixed order instead of fp32 atomics."""
     a = _conv_args(x, w, bias, res, mul, y, g, act, mulmode, y2, ln, lnf, resn)
+    if det is not None:
+        a.flags |= _lib.CONV_DETERMINISTIC
+        a.det_ws, a.det_ws_bytes = _p(det), det.numel() * det.element_size()
     if no_y:  # with lnf: the result itself is not written (``y``: any valid pointer) -- only where conv_lnfwd_chain_supported says so; so are
         a.flags |= _lib.CONV_NO_Y  # lnf["mean"] and ``resn`` = dict(rstd, mean[, m]): ``res`` holds normalised rows, the residual is rebuilt
     if pool2:  # y: [B][Hout/2][Wout/2][ldy] <- 2x2 sums of the result (only where conv_pool2_supported says so)
@@ -146,6 +151,22 @@ def conv_loss_supported(g: dict, dtype: int) -> bool:
     return bool(_lib.load().c2w_conv_loss_supported(ctypes.byref(_geom_args(g)), dtype))
 
 
+def conv_det_scratch_bytes(g: dict, dtype: int, ln_ldm: Optional[int] = None, loss: bool = False) -> int:
+    """Bytes of the ``det`` scratch ``conv`` needs for this geometry with a fused LayerNorm backward (``ln_ldm``: the stride of its
+    modulation-gradient rows, 0 = one shared row) or the fused loss (include/c2w_hip.h::c2w_conv_det_scratch_bytes)."""
+    a = _geom_args(g)
+    a.flags = _lib.CONV_DETERMINISTIC
+    if ln_ldm is not None:
+        a.ln_x = a.ln_dm = ctypes.c_void_p(16)  # only tested against NULL
+        a.ln_ldm = int(ln_ldm)
+    if loss:
+        a.loss_sum = ctypes.c_void_p(16)
+    n = int(_lib.load().c2w_conv_det_scratch_bytes(ctypes.byref(a), dtype))
+    if n < 0:
+        check(n, "c2w_conv_det_scratch_bytes")
+    return n
+
+
 def conv_lnbwd_supported(g: dict, dtype: int) -> bool:
     a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
                  g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
@@ -172,19 +193,25 @@ def conv_wgrad_dispatch(g: dict, dtype: int) -> int:
     return rc
 
 
-def conv_wgrad(x, dy, dw, g: dict, dtype: int, dbias=None, workspace: Optional[torch.Tensor] = None):
+def conv_wgrad(x, dy, dw, g: dict, dtype: int, dbias=None, workspace: Optional[torch.Tensor] = None, deterministic: bool = False):
     """c2w_conv_wgrad: dw += dY^T . gather(x); dbias (optional) += column sums of dY.
     ``workspace``: fp32 scratch tensor for the split-K partial sums (``new_workspace``), handed over per call; one per stream.
-    Without it (or when it is too small for the geometry) the partial sums are combined with fp32 atomics."""
+    Without it (or when it is too small for the geometry) the partial sums are combined with fp32 atomics.
+    ``deterministic``: dbias too is summed in a fixed order (its partial rows ride in the workspace, sized by
+    conv_wgrad_workspace_bytes(..., deterministic=True)); a missing or short workspace then raises."""
     a = _conv_args(x, None, None, None, None, dy, g, 0, 0)
     a.w = None
+    if deterministic:
+        a.flags |= _lib.CONV_DETERMINISTIC
     nbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
     check(_lib.load().c2w_conv_wgrad(ctypes.byref(a), _p(dw), _p(dbias), _p(workspace), nbytes, dtype, _stream()), "c2w_conv_wgrad")
 
 
-def conv_wgrad_workspace_bytes(g: dict, dtype: int) -> int:
+def conv_wgrad_workspace_bytes(g: dict, dtype: int, deterministic: bool = False) -> int:
     a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
                  g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
+    if deterministic:
+        a.flags = _lib.CONV_DETERMINISTIC
     n = int(_lib.load().c2w_conv_wgrad_workspace_bytes(ctypes.byref(a), dtype))
     if n < 0:
         check(n, "c2w_conv_wgrad_workspace_bytes")
@@ -201,21 +228,27 @@ def conv_wgrad_grouped_supported(g: dict, n: int, dtype: int) -> bool:
     return bool(_lib.load().c2w_conv_wgrad_grouped_supported(ctypes.byref(_geom_args(g)), n, dtype))
 
 
-def conv_wgrad_grouped_workspace_bytes(g: dict, n: int, dtype: int) -> int:
-    nb = int(_lib.load().c2w_conv_wgrad_grouped_workspace_bytes(ctypes.byref(_geom_args(g)), n, dtype))
+def conv_wgrad_grouped_workspace_bytes(g: dict, n: int, dtype: int, deterministic: bool = False) -> int:
+    a = _geom_args(g)
+    if deterministic:
+        a.flags = _lib.CONV_DETERMINISTIC
+    nb = int(_lib.load().c2w_conv_wgrad_grouped_workspace_bytes(ctypes.byref(a), n, dtype))
     if nb < 0:
         check(nb, "c2w_conv_wgrad_grouped_workspace_bytes")
     return nb
 
 
-def conv_wgrad_grouped(items, g: dict, dtype: int, workspace: Optional[torch.Tensor] = None):
+def conv_wgrad_grouped(items, g: dict, dtype: int, workspace: Optional[torch.Tensor] = None, deterministic: bool = False):
     """items: [(x, dy, dw, dbias or None)] of layers that share geometry ``g``: every dw += dY^T . patches(x), every dbias += column sums
     of dY, by one launch (+ one reduction launch when the plan splits K)."""
     arr = (_lib.WgradItem * len(items))()
     for i, (x, dy, dw, db) in enumerate(items):
         arr[i].x, arr[i].dy, arr[i].dw, arr[i].dbias = x.data_ptr(), dy.data_ptr(), dw.data_ptr(), (db.data_ptr() if db is not None else None)
     nbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
-    check(_lib.load().c2w_conv_wgrad_grouped(ctypes.byref(_geom_args(g)), arr, len(items), _p(workspace), nbytes, dtype, _stream()),
+    a = _geom_args(g)
+    if deterministic:
+        a.flags = _lib.CONV_DETERMINISTIC
+    check(_lib.load().c2w_conv_wgrad_grouped(ctypes.byref(a), arr, len(items), _p(workspace), nbytes, dtype, _stream()),
           "c2w_conv_wgrad_grouped")
 
 
@@ -233,12 +266,37 @@ def ln_forward(x, m, y, npix, HW, C, ldm, eps, unbiased, dtype):
     check(_lib.load().c2w_ln_forward(_p(x), _p(m), _p(y), npix, HW, C, ldm, eps, int(unbiased), dtype, _stream()), "c2w_ln_forward")
 
 
-def ln_backward(dy, x, m, dres, dx, dm, npix, HW, C, ldm, eps, unbiased, dtype):
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def ln_backward_det_scratch_bytes(npix, HW, C, ldm) -> int:
+    return int(_lib.load().c2w_ln_backward_det_scratch_bytes(npix, HW, C, ldm))
+
+
+def colsum_det_scratch_bytes(rows, C) -> int:
+    return int(_lib.load().c2w_colsum_det_scratch_bytes(rows, C))
+
+
+def loss_det_scratch_bytes() -> int:
+    """One size for the ``det`` scratch of mse_loss_grad / mse_loss_grad_noise / sq_err."""
+    return int(_lib.load().c2w_loss_det_scratch_bytes())
+
+
+def ln_backward(dy, x, m, dres, dx, dm, npix, HW, C, ldm, eps, unbiased, dtype, det: Optional[torch.Tensor] = None):
+    """``det``: deterministic mode -- the fp32 scratch (>= ln_backward_det_scratch_bytes) ``dm`` is summed through in a fixed order."""
+    if det is not None:
+        check(_lib.load().c2w_ln_backward_det(_p(dy), _p(x), _p(m), _p(dres), _p(dx), _p(dm), npix, HW, C, ldm, eps, int(unbiased), _p(det),
+                                              _nbytes(det), dtype, _stream()), "c2w_ln_backward_det")
+        return
     check(_lib.load().c2w_ln_backward(_p(dy), _p(x), _p(m), _p(dres), _p(dx), _p(dm), npix, HW, C, ldm, eps, int(unbiased), dtype,
                                       _stream()), "c2w_ln_backward")
 
 
-def colsum(a, out, rows, C, lda, dtype):
+def colsum(a, out, rows, C, lda, dtype, det: Optional[torch.Tensor] = None):
+    if det is not None:
+        check(_lib.load().c2w_colsum_det(_p(a), _p(out), rows, C, lda, _p(det), _nbytes(det), dtype, _stream()), "c2w_colsum_det")
+        return
     check(_lib.load().c2w_colsum(_p(a), _p(out), rows, C, lda, dtype, _stream()), "c2w_colsum")
 
 
@@ -266,8 +324,14 @@ def nhwc_to_nchw(y, out, B, C, HW, ldc, dtype):
     check(_lib.load().c2w_nhwc_to_nchw(_p(y), _p(out), B, C, HW, ldc, dtype, _stream()), "c2w_nhwc_to_nchw")
 
 
-def mse_loss_grad(y, eps, dy, loss_sum, B, C, HW, ldc, gscale, dtype, scaler=None):
-    """``scaler``: the 4-float device state of the dynamic loss scale (fp16 training) or None."""
+def mse_loss_grad(y, eps, dy, loss_sum, B, C, HW, ldc, gscale, dtype, scaler=None, det: Optional[torch.Tensor] = None):
+    """``scaler``: the 4-float device state of the dynamic loss scale (fp16 training) or None.
+    ``det`` (here, in mse_loss_grad_noise and in sq_err): deterministic mode -- the fp32 scratch (>= loss_det_scratch_bytes) the waves'
+    sums go through in a fixed order."""
+    if det is not None:
+        check(_lib.load().c2w_mse_loss_grad_det(_p(y), _p(eps), _p(dy), _p(loss_sum), B, C, HW, ldc, gscale, _p(scaler), _p(det), _nbytes(det),
+                                                dtype, _stream()), "c2w_mse_loss_grad_det")
+        return
     check(_lib.load().c2w_mse_loss_grad_scaled(_p(y), _p(eps), _p(dy), _p(loss_sum), B, C, HW, ldc, gscale, _p(scaler), dtype, _stream()),
           "c2w_mse_loss_grad")
 
@@ -306,19 +370,27 @@ def windows_to_nhwc_noise(data, img_off, seed, musig, y, B, C, HW, ldc, dtype) -
     return True
 
 
-def mse_loss_grad_noise(y, seed, dy, loss_sum, B, C, HW, ldc, gscale, dtype, scaler=None) -> bool:
-    rc = _lib.load().c2w_mse_loss_grad_noise(_p(y), int(seed), _p(dy), _p(loss_sum), B, C, HW, ldc, gscale, _p(scaler), dtype, _stream())
+def mse_loss_grad_noise(y, seed, dy, loss_sum, B, C, HW, ldc, gscale, dtype, scaler=None, det: Optional[torch.Tensor] = None) -> bool:
+    if det is not None:
+        rc = _lib.load().c2w_mse_loss_grad_noise_det(_p(y), int(seed), _p(dy), _p(loss_sum), B, C, HW, ldc, gscale, _p(scaler), _p(det),
+                                                     _nbytes(det), dtype, _stream())
+    else:
+        rc = _lib.load().c2w_mse_loss_grad_noise(_p(y), int(seed), _p(dy), _p(loss_sum), B, C, HW, ldc, gscale, _p(scaler), dtype, _stream())
     if rc == -3:
         return False
     check(rc, "c2w_mse_loss_grad_noise")
     return True
 
 
-def sq_err(y, eps, out, loss_sum, B, C, HW, ldc, dtype) -> bool:
+def sq_err(y, eps, out, loss_sum, B, C, HW, ldc, dtype, det: Optional[torch.Tensor] = None) -> bool:
     """out (B,C,H,W) fp32 = (y - eps)^2 from NHWC rows ``y``; loss_sum[0] += its sum; ``eps``: an fp32 (B,C,H,W) tensor, or an int seed
     (the stream the *_noise launchers regenerate).  False if the shape is not supported (caller converts the layout and uses tensor
     arithmetic)."""
-    if isinstance(eps, int):
+    if det is not None and isinstance(eps, int):
+        rc = _lib.load().c2w_sq_err_noise_det(_p(y), int(eps), _p(out), _p(loss_sum), B, C, HW, ldc, _p(det), _nbytes(det), dtype, _stream())
+    elif det is not None:
+        rc = _lib.load().c2w_sq_err_det(_p(y), _p(eps), _p(out), _p(loss_sum), B, C, HW, ldc, _p(det), _nbytes(det), dtype, _stream())
+    elif isinstance(eps, int):
         rc = _lib.load().c2w_sq_err_noise(_p(y), int(eps), _p(out), _p(loss_sum), B, C, HW, ldc, dtype, _stream())
     else:
         rc = _lib.load().c2w_sq_err(_p(y), _p(eps), _p(out), _p(loss_sum), B, C, HW, ldc, dtype, _stream())

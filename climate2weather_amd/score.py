@@ -236,7 +236,7 @@ def _forward_loss(eng: Engine, x, t, dt: int, req: dict, tape: Optional[Tape]):
     y = eng.forward(x, tt, dt, tape=tape, noise=(eps, musig), nhwc_out=True)
     out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
     loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
-    if not ops.sq_err(y, eps, out, loss_sum, B, C, H * W, lay.cout_pad, dt):  # shape outside the fused kernel: layout pass + tensor arithmetic
+    if not ops.sq_err(y, eps, out, loss_sum, B, C, H * W, lay.cout_pad, dt, **eng.loss_det_kw()):  # shape outside the fused kernel: layout pass + tensor arithmetic
         yn = torch.empty_like(out)
         ops.nhwc_to_nchw(y, yn, B, C, H * W, lay.cout_pad, dt)
         out = (yn - _materialize_eps(eps, out)) ** 2
@@ -379,6 +379,9 @@ class ScoreUNet(torch.nn.Module):
         self.map_layer1 = torch.nn.Linear(embedding_dim, embedding_dim)
         self.precision = "auto"  # "auto" (the autocast dtype under torch.autocast, else fp32) | "fp32" | "bf16" | "fp16"
         self.ln_unbiased = True  # zuko.nn.LayerNorm uses torch.var_mean's default; see oracle/_shim/zuko/nn.py
+        # True / False: the engine's deterministic mode (bit-reproducible bias / modulation gradients and loss sum: Engine.deterministic)
+        # for forward + loss.backward() through this module; None: the engine's default (C2W_DETERMINISTIC)
+        self.deterministic = None
         self.__dict__["_engine"] = None
 
     # ---- engine plumbing (kept out of state_dict / pickles / deep copies)
@@ -389,6 +392,9 @@ class ScoreUNet(torch.nn.Module):
             self.__dict__["_engine"] = eng
         elif not eng.is_attached(self):
             eng.attach(self)  # parameters were replaced (.to(device), load via assign, dtype cast): re-flatten
+        det = self.__dict__.get("deterministic")
+        if det is not None:
+            eng.deterministic = bool(det)
         return eng
 
     def __getstate__(self):

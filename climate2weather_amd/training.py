@@ -58,7 +58,7 @@ class Trainer:
                  precision: str = "bf16", batch_size: Optional[int] = None, loss_scaling: float = 1.0,
                  process_group=None, bucket_mb: float = 25.0, init_scale: float = 65536.0, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, fused_noise: bool = True, seed: Optional[int] = None,
-                 allreduce_dtype: Optional[str] = None):
+                 allreduce_dtype: Optional[str] = None, deterministic: Optional[bool] = None):
         self.net = net
         self.pipeline = pipeline or SDAPipeline()
         self.lr, self.lr_fn = lr, lr_fn
@@ -80,6 +80,8 @@ class Trainer:
         self.step_count = 0
         eng = net._get_engine()
         self.eng = eng
+        if deterministic is not None:  # None: the engine's setting (C2W_DETERMINISTIC) stays; see Engine.deterministic
+            eng.deterministic = bool(deterministic)
         eng.ensure_grad_buffer(net, bind=True)
         n = eng.layout.numel
         dev = eng.flat.device
@@ -318,11 +320,12 @@ class Trainer:
             eng.backward(tape, y)
             return self.loss_sum[0] * (self.loss_scaling / n)
         dy = torch.empty_like(y)
-        if seed is None or not ops.mse_loss_grad_noise(y, seed, dy, self.loss_sum, B, C, H * W, lay.cout_pad, gs, self.dt, scaler=self.scaler):
+        if seed is None or not ops.mse_loss_grad_noise(y, seed, dy, self.loss_sum, B, C, H * W, lay.cout_pad, gs, self.dt, scaler=self.scaler,
+                                                        **eng.loss_det_kw()):
             if eps is None:  # shape outside the fused kernel: materialise the same stream
                 eps = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
                 ops.philox_normal(eps, eps.numel(), seed)
-            ops.mse_loss_grad(y, eps, dy, self.loss_sum, B, C, H * W, lay.cout_pad, gs, self.dt, scaler=self.scaler)
+            ops.mse_loss_grad(y, eps, dy, self.loss_sum, B, C, H * W, lay.cout_pad, gs, self.dt, scaler=self.scaler, **eng.loss_det_kw())
         eng.backward(tape, dy)
         return self.loss_sum[0] * (self.loss_scaling / n)
 

@@ -42,7 +42,17 @@ enum {
  * y = max(a, 0), y2 = (a > 0) -- the backward pass multiplies by y2 with C2W_MUL_PLAIN. */
 enum { C2W_ACT_NONE = 0, C2W_ACT_SILU = 1, C2W_ACT_SILU_PAIR = 2, C2W_ACT_RELU = 3, C2W_ACT_RELU_PAIR = 4 };
 enum { C2W_MUL_PLAIN = 0, C2W_MUL_DSILU = 1 };
-enum { C2W_CONV_POOL2 = 1, C2W_CONV_WPACKED = 2, C2W_CONV_NO_Y = 4 }; /* C2wConvArgs.flags (bit set) */
+enum { C2W_CONV_POOL2 = 1, C2W_CONV_WPACKED = 2, C2W_CONV_NO_Y = 4, C2W_CONV_DETERMINISTIC = 8 }; /* C2wConvArgs.flags (bit set) */
+/* Deterministic mode (opt-in, per call; the library keeps no mode state).  Most of a training step is bit-reproducible run to run
+ * as it is; the bias gradients, the LayerNorm modulation gradients and the loss scalar are summed with fp32 atomics whose order the
+ * hardware picks.  With C2W_CONV_DETERMINISTIC set in C2wConvArgs.flags (c2w_conv_wgrad, c2w_conv_wgrad_grouped, c2w_conv_forward with
+ * a fused LayerNorm backward or loss) and through the c2w_*_det siblings of the pointwise launchers, every workgroup that would issue
+ * such an atomic STORES its contribution into a slot of a caller-owned fp32 scratch -- the slot a pure function of the launch
+ * geometry, every slot read is written by the same call, nothing is zero-filled -- and a small launch behind it on the same stream
+ * adds the slots onto the destination (still accumulated into) in a fixed order.  Same arguments, same knob settings => same bits.
+ * Every other output of the call is bit-identical to the default mode's; the reduced values differ from it in summation order only.
+ * A missing or short scratch is C2W_ERR_BAD_ARG, never a fall-back to atomics.  One scratch per stream (contents undefined before
+ * and after a call), like c2w_conv_wgrad's workspace. */
 
 /* y[q][co] = act( sum_{tap,ci} w[co][tap][ci] * x[src(q,tap)][ci] + bias[co] ) (* mul' ) (+ res)
  * q runs over the B*Hout*Wout output pixels in NHWC raster order. */
@@ -130,6 +140,10 @@ typedef struct C2wConvArgs {
     float* splitk_ws;
     unsigned long long splitk_ws_bytes;
     int32_t splitk;           /* 0 / 1: no split; else exactly c2w_conv_splitk_plan's answer for these arguments */
+    /* Deterministic mode of c2w_conv_forward (flags & C2W_CONV_DETERMINISTIC with ln_dm or loss_sum): the scratch the fused epilogue's
+     * per-workgroup sums go through, at least c2w_conv_det_scratch_bytes() of it. */
+    float* det_ws;
+    unsigned long long det_ws_bytes;
 } C2wConvArgs;
 
 /* 1 when c2w_conv_forward / c2w_conv_wgrad run this geometry on the halo-patch kernels (3x3 stride-1, image tiled exactly
@@ -155,6 +169,9 @@ int c2w_conv_loss_supported(const C2wConvArgs* args, int dtype);
  * kernels, fused epilogues other than bias / activation / mul / res, or a launch that already has a workgroup per CU), and through
  * *ws_bytes (may be NULL) the scratch it then needs.  A pure function of the arguments' geometry, epilogue fields and the dtype. */
 int c2w_conv_splitk_plan(const C2wConvArgs* args, int dtype, unsigned long long* ws_bytes);
+/* Bytes of det_ws c2w_conv_forward needs for these arguments under C2W_CONV_DETERMINISTIC (0: no fused reduction in this call), or a
+ * negative C2W_ERR_* status.  A pure function of the arguments' geometry, fusion fields and the dtype. */
+long long c2w_conv_det_scratch_bytes(const C2wConvArgs* args, int dtype);
 
 /* Which kernel family c2w_conv_forward (naive == 0) / c2w_conv_wgrad run these arguments on -- a pure function of the geometry,
  * the dtype and the fusion fields; the parity tests assert with it that a case reaches the kernel it is meant to cover.
@@ -178,13 +195,18 @@ int c2w_conv_forward(const C2wConvArgs* args, int dtype, int naive, void* stream
  * workspace / workspace_bytes: caller-owned device scratch (16-byte aligned) for the split's partial sums, handed over PER CALL --
  * the library keeps no pointer, so the entry point is re-entrant: with it the workgroups store their partial tiles and a second
  * launch on the same stream reduces them in a fixed order (75 MB of coalesced stores + reads per launch instead of 75 MB of fp32
- * atomics; dw is then bit-reproducible run to run -- dbias is NOT: every split workgroup adds its column sums with fp32 atomics); NULL, or fewer bytes than c2w_conv_wgrad_workspace_bytes() asks for: fp32 atomics.
+ * atomics; dw is then bit-reproducible run to run -- dbias only with args->flags & C2W_CONV_DETERMINISTIC: by default every split workgroup adds its
+ * column sums with fp32 atomics; with the flag the workgroups' bias rows ride behind the partial tiles in the same workspace and a
+ * sibling of the reduce launch adds them in split order, or, without a split, one workgroup per channel updates dbias by plain
+ * read-modify-write); NULL, or fewer bytes than c2w_conv_wgrad_workspace_bytes() asks for: fp32 atomics -- under the flag
+ * C2W_ERR_BAD_ARG instead, as is C2W_WGRAD_ATOMICS=1.
  * Contents are undefined before and after the call.  One buffer must not be handed to launches that may run concurrently
  * (different streams without an ordering between them): give each stream its own.
  * Replaces autograd's weight/bias backward of every Conv2d/Conv1d/Linear cited above. */
 int c2w_conv_wgrad(const C2wConvArgs* args, float* dw, float* dbias, void* workspace, unsigned long long workspace_bytes, int dtype,
                    void* stream);
-/* Scratch bytes c2w_conv_wgrad uses for this geometry and dtype (0: no split), or a negative C2W_ERR_* status. */
+/* Scratch bytes c2w_conv_wgrad uses for this geometry and dtype (0: no split), or a negative C2W_ERR_* status.  With
+ * args->flags & C2W_CONV_DETERMINISTIC: including the bias rows. */
 long long c2w_conv_wgrad_workspace_bytes(const C2wConvArgs* args, int dtype);
 
 /* The weight gradients of n layers that share ONE geometry (`args`: the forward block of any of them; x / y are ignored) as one launch:
@@ -192,12 +214,12 @@ long long c2w_conv_wgrad_workspace_bytes(const C2wConvArgs* args, int dtype);
  * residual-block convs of a UNet level (model/nn.py:146-159: 6 or 12 layers of one shape) have their output gradients one after the
  * other during the backward pass and independent weight gradients; a launch per layer must split its pixel reduction over the whole
  * chip (at 8x8: 8 K tiles per workgroup, each followed by 295 KB of partial sums), together the layers fill it with a fraction of
- * the splits.  `items` is a HOST array, copied into the kernel arguments (nothing is kept).  The dw results are deterministic (dbias: fp32 atomics across the split workgroups, last-bit order noise) (a fixed
- * reduction order) but differ in rounding from n single calls (another split of the same sum).
+ * the splits.  `items` is a HOST array, copied into the kernel arguments (nothing is kept).  The dw results are deterministic (a fixed reduction order; dbias too with
+ * args->flags & C2W_CONV_DETERMINISTIC, by default fp32 atomics across the split workgroups: last-bit order noise) but differ in rounding from n single calls (another split of the same sum).
  * c2w_conv_wgrad_grouped_supported: 1 when the n layers run as one launch (2 <= n <= 16; the halo-patch geometries on
  * wgrad_patch_group_kernel, 1x1 layers -- the attention level's qkv / proj_out, model/nn.py:45,47 -- on wgrad_group_kernel); otherwise
  * the call returns C2W_ERR_UNSUPPORTED and the caller issues n c2w_conv_wgrad calls.  workspace must hold
- * c2w_conv_wgrad_grouped_workspace_bytes(args, n, dtype) bytes (0 when the plan does not split). */
+ * c2w_conv_wgrad_grouped_workspace_bytes(args, n, dtype) bytes (0 when the plan does not split; more under C2W_CONV_DETERMINISTIC). */
 typedef struct C2wWgradItem {
     const void* x;
     const void* dy;
@@ -214,12 +236,23 @@ int c2w_conv_wgrad_grouped(const C2wConvArgs* args, const C2wWgradItem* items, i
  * ldm == 0 -> one row shared by every pixel; m == NULL -> no add).  unbiased selects the N-1 variance. */
 int c2w_ln_forward(const void* x, const float* m, void* y, long long npix, int HW, int C, int ldm, float eps,
                    int unbiased, int dtype, void* stream);
-/* dx = dres + dLN(dy; x+m);  dm[b][c] += sum over the image's pixels of the LN part (fp32 atomics; dm may be NULL). */
+/* dx = dres + dLN(dy; x+m);  dm[b][c] += sum over the image's pixels of the LN part (fp32 atomics: c2w_ln_backward_det for a fixed
+ * order; dm may be NULL). */
 int c2w_ln_backward(const void* dy, const void* x, const float* m, const void* dres, void* dx, float* dm,
                     long long npix, int HW, int C, int ldm, float eps, int unbiased, int dtype, void* stream);
+/* Deterministic mode: the same with dm summed in a fixed order through `scratch` (>= c2w_ln_backward_det_scratch_bytes(); not read
+ * when dm == NULL); dx is bit-identical to c2w_ln_backward's. */
+int c2w_ln_backward_det(const void* dy, const void* x, const float* m, const void* dres, void* dx, float* dm,
+                        long long npix, int HW, int C, int ldm, float eps, int unbiased, float* scratch, unsigned long long scratch_bytes,
+                        int dtype, void* stream);
+long long c2w_ln_backward_det_scratch_bytes(long long npix, int HW, int C, int ldm);
 
 /* out[c] += sum_rows a[row][c]   (bias gradients; fp32 atomics) */
 int c2w_colsum(const void* a, float* out, long long rows, int C, int lda, int dtype, void* stream);
+/* Deterministic mode: a fixed summation order through `scratch` (>= c2w_colsum_det_scratch_bytes(rows, C)) */
+int c2w_colsum_det(const void* a, float* out, long long rows, int C, int lda, float* scratch, unsigned long long scratch_bytes, int dtype,
+                   void* stream);
+long long c2w_colsum_det_scratch_bytes(long long rows, int C);
 /* y = silu(x) ; dx = dy * silu'(x)   (the activation train.py:171 passes; model/nn.py:156, model/score.py:63,67) */
 int c2w_silu(const void* x, void* y, long long n, int dtype, void* stream);
 int c2w_silu_backward(const void* x, const void* dy, void* dx, long long n, int dtype, void* stream);
@@ -272,6 +305,19 @@ int c2w_mse_loss_grad_noise(const void* y, unsigned long long seed, void* dy, fl
 int c2w_sq_err(const void* y, const float* eps, float* out, float* loss_sum, int B, int C, int HW, int ldc, int dtype, void* stream);
 int c2w_sq_err_noise(const void* y, unsigned long long seed, float* out, float* loss_sum, int B, int C, int HW, int ldc, int dtype,
                      void* stream);
+/* Deterministic mode of the loss launchers: loss_sum += the waves' sums in a fixed order through `scratch` (>= c2w_loss_det_scratch_bytes(),
+ * one size for all of them); dy / out are bit-identical to the default launchers'.  c2w_mse_loss_grad_det covers c2w_mse_loss_grad and
+ * c2w_mse_loss_grad_scaled (scaler_state may be NULL). */
+long long c2w_loss_det_scratch_bytes(void);
+int c2w_mse_loss_grad_det(const void* y, const float* eps, void* dy, float* loss_sum, int B, int C, int HW, int ldc, float gscale,
+                          const float* scaler_state, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream);
+int c2w_mse_loss_grad_noise_det(const void* y, unsigned long long seed, void* dy, float* loss_sum, int B, int C, int HW, int ldc,
+                                float gscale, const float* scaler_state, float* scratch, unsigned long long scratch_bytes, int dtype,
+                                void* stream);
+int c2w_sq_err_det(const void* y, const float* eps, float* out, float* loss_sum, int B, int C, int HW, int ldc, float* scratch,
+                   unsigned long long scratch_bytes, int dtype, void* stream);
+int c2w_sq_err_noise_det(const void* y, unsigned long long seed, float* out, float* loss_sum, int B, int C, int HW, int ldc, float* scratch,
+                         unsigned long long scratch_bytes, int dtype, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
