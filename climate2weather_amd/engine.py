@@ -24,12 +24,12 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from . import ops
+from .forward import LN_EPS, ForwardPass
 from .nn import BlockSpec, LevelSpec
 from .ops import (ACT_NONE, ACT_RELU, ACT_RELU_PAIR, ACT_SILU, ACT_SILU_PAIR, CONV_1X1, CONV_S1, CONV_S2, CONV_TS2, CONV_UP, DTYPE_BF16, DTYPE_F16, DTYPE_F32, MUL_DSILU, MUL_PLAIN, TORCH_DTYPE)
 
 import weakref
 
-LN_EPS = 1e-5
 _ENGINE_BY_PARAM_ID: Dict[int, "weakref.ReferenceType"] = {}  # id(Parameter) -> weakref(Engine); nothing is stored ON the Parameter (they are pickled / deep-copied)
 
 
@@ -197,6 +197,18 @@ class Tape:
 
 class Engine:
     LINEAR_DGRAD_SPLIT_MIN_ROWS = 2048  # Linear layers at least this wide take the split-reduction input-gradient route
+    # A/B knobs that are class attributes (the others are set per engine in __init__); tests and experiments set them on the class or an engine
+    use_center_conv = os.environ.get("C2W_NO_CENTER_CONV") != "1"  # A/B knob (DESIGN.md section 10)
+    # Opt-in (C2W_LN_CHAIN=1 or the attribute): the chain form of a level side -- residual-block outputs that only the next block reads are
+    # not written, the next block rebuilds its residual from the LayerNorm rows this one emitted (forward.py: res_block).  Measured at B = 128, bf16
+    # (profiles/r06_experiments.md): -0.23 ms per step (five 128-channel launches lose their 537 / 134 MB store), but the rebuilt
+    # residual carries the rounding of h = LN(x + m) scaled by sigma -- 2^-9 |x + m - mean| instead of 2^-9 |x| -- and where the modulation
+    # dominates the block input that is MORE than rounding x itself: against the CPU oracle the worst gradient tensor moves from
+    # 8.7e-3 to 1.7e-2 relative L2 (bf16; fp16 5e-3 -> 8.5e-3 of the output scale).  Parity before 0.5 %: off.
+    chain_blocks = os.environ.get("C2W_LN_CHAIN") == "1"
+    use_splitk = os.environ.get("C2W_NO_SPLITK") is None  # A/B knob: under-filled inference convs as one workgroup per tile (rounds 1-5)
+    fuse_loss = os.environ.get("C2W_NO_LOSS_FUSION") is None  # A/B knob: the loss tail as its own pass (rounds 1-5); the library reads the same variable
+    use_gemv = os.environ.get("C2W_NO_GEMV") != "1"  # A/B knob: one-row Linear layers as matrix-vector products
 
     def __init__(self, net):
         self.layout = Layout(net)
@@ -654,9 +666,11 @@ class Engine:
 
     def loss_det_kw(self) -> dict:
         """Keyword arguments of the loss launchers (ops.mse_loss_grad, mse_loss_grad_noise, sq_err): nothing unless the mode is on."""
-        if not self.deterministic:
-            return {}
-        return dict(det=self.det_scratch(self._det_bytes(("loss",), ops.loss_det_scratch_bytes)))
+        return self._det_kw(("loss",), lambda: ops.loss_det_scratch_bytes())
+
+    def _det_kw(self, key: tuple, query) -> dict:
+        """``det=`` argument of a launch that reduces in a fixed order (``query``: its scratch size): nothing unless the mode is on"""
+        return dict(det=self.det_scratch(self._det_bytes(key, query))) if self.deterministic else {}
 
     @staticmethod
     def _gkey(g: dict) -> tuple:
@@ -675,7 +689,7 @@ class Engine:
         a pure function of geometry and knobs: remembered per geometry."""
         if not self.use_splitk or self.flat is None or not self.flat.is_cuda:
             return None
-        key = (g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"], g["wrows"], g["mode"], dt, act, ops.KNOBS_GENERATION)
+        key = self._gkey(g) + (dt, act, ops.KNOBS_GENERATION)
         plan = self._splitk_plans.get(key)
         if plan is None:
             plan = self._splitk_plans[key] = ops.conv_splitk_plan(g, dt, act)
@@ -700,6 +714,7 @@ class Engine:
             # (round 6, B = 64: 26.00 -> 25.84 ms per step; at B = 128 the same grouping costs 0.25 ms: profiles/r05_experiments.md)
             cap = 3
         if group and self.group_wgrads and cap > 1:
+            # (_gkey without ``wrows``, on purpose: these fields decide which layers share a grouped launch)
             key = (g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"], g["mode"], dt, ops.KNOBS_GENERATION)
             ok = self._wg_group_ok.get(key)
             if ok is None:
@@ -828,13 +843,8 @@ class Engine:
         With ``tape`` every op records its backward closure (training / exact guidance)."""
         lay = self.layout
         self.refresh_version()
-        T = TORCH_DTYPE[dt]
-        if x_nhwc is not None:  # rows already in the network's input layout (the sampler's fused window gather)
-            B, C, H, W = shape
-            dev = x_nhwc.device
-        else:
-            B, C, H, W = x.shape
-            dev = x.device
+        B, C, H, W = shape if x_nhwc is not None else x.shape  # x_nhwc: rows already in the network's input layout (the sampler's fused window gather)
+        dev = (x_nhwc if x_nhwc is not None else x).device
         L = len(lay.levels)
         if C != lay.in_channels:
             raise ValueError(f"expected {lay.in_channels} channels, got {C}")
@@ -844,7 +854,6 @@ class Engine:
         for lv in lay.levels:
             if lv.channels % ck:
                 raise ValueError(f"hidden_channels must be multiples of {ck} for this compute dtype")
-        train = tape is not None
         lazy = x_nhwc is None and hasattr(x, "materialize")  # data.WindowBatch: windows still inside the dataset array
         if x_nhwc is None and not lazy:
             x = x.contiguous().float()
@@ -853,365 +862,15 @@ class Engine:
         if Bt not in (1, B):
             raise ValueError("t must hold 1 or B values (model/score.py:60)")
         ldm = lay.sum_c if (Bt == B and B > 1) else 0
-
-        # ---- time embedding MLP + all modulation vectors (fp32)
-        pe = torch.empty((Bt, lay.noise_features), dtype=torch.float32, device=dev)
-        ops.timestep_embedding(tt, pe, Bt, lay.noise_features)
-        emb = self._mlp_layer("map_layer0", pe, Bt, tape, need_dx=False)
-        zf = None
-        if lay.forcing_dim:  # emb = silu(map_layer1(.) + map_forcing(forcing))  (model/score.py:64-67)
-            if forcing is None:
-                raise ValueError("forcing_dim > 0: the forcing vector is required")
-            rf = lay.convs["map_forcing"]
-            fr = forcing.reshape(-1, lay.forcing_dim).to(device=dev, dtype=torch.float32)
-            if fr.shape[0] not in (1, Bt) and not (Bt == 1 and fr.shape[0] == B):
-                raise ValueError(f"forcing has {fr.shape[0]} rows for {Bt} time values / {B} batch items")
-            if Bt == 1 and fr.shape[0] == B and B > 1:  # scalar t, per-item forcing: the embedding becomes per item
-                raise NotImplementedError("per-item forcing with a scalar t: pass t with one value per batch item")
-            fpad = torch.zeros((Bt, rf.kstride), dtype=torch.float32, device=dev)
-            fpad[:, : lay.forcing_dim] = fr if fr.shape[0] == Bt else fr.expand(Bt, -1)
-            zf = self._linear("map_forcing", fpad, Bt, ACT_NONE, None)  # not on the tape: its gradient is map_layer1's pre-activation gradient
-            g_f = self._geom(Bt, 1, 1, rf.kstride, 1, 1, rf.rows, rf.rows, rf.rows, CONV_1X1)
-
-            def forcing_bw(gz, rf=rf, fpad=fpad, g_f=g_f):
-                self._wgrad(rf, fpad, gz, g_f, DTYPE_F32)
-                tape.done(rf.w_off)
-        elif forcing is not None:
-            raise ValueError("forcing passed to a network built with forcing_dim == 0 (model/score.py:60)")
-        emb = self._mlp_layer("map_layer1", emb, Bt, tape, add=zf, add_bw=forcing_bw if zf is not None and tape is not None else None)
-        m_all = self._linear("proj", emb, Bt, ACT_NONE, tape)
-        if train:
-            dm_all = torch.zeros_like(m_all)
-            tape.meta["dm_all"] = dm_all
-        else:
-            dm_all = None
-
-        # ---- network input -> NHWC
-        loss_rows = None  # (noise rows, channel stride) the input conversion kept for the fused loss tail
-        if x_nhwc is not None:
-            x0 = x_nhwc
-        else:
-            x0 = torch.empty((B * H * W, lay.cin_pad), dtype=T, device=dev)
-            regen = noise is not None and isinstance(noise[0], int)  # regenerated noise: (seed, musig)
-            done = False
-            # Fused loss tail (round 6): where the output conv takes it (ops.conv_loss_supported), the input conversion KEEPS the noise it
-            # mixes in -- rounded to half precision, as NHWC rows -- and the output conv's epilogue reads it back: the generator runs
-            # once per step instead of twice and the prediction is never written.  The step's noise is then the rounded stream.
-            if loss is not None and train and nhwc_out and regen and self.fuse_loss and dt != DTYPE_F32 and lay.out_channels == C and (H * W) % 4 == 0:
-                rec_o = lay.convs["unet." + lay.levels[0].tail_key]
-                g_o = self._geom(B, H, W, rec_o.kstride, H, W, lay.cout_pad, lay.cout_pad, rec_o.rows, CONV_S1)
-                if ops.conv_loss_supported(g_o, dt):
-                    lde = _round_up(C, 8)
-                    erows = torch.empty((B * H * W, lde), dtype=torch.float16, device=dev)
-                    src, offs = (x.data, x.offsets()) if lazy else (x, None)
-                    if (not lazy or (x.data.is_contiguous() and x.data.dtype == torch.float32)) and \
-                            ops.nchw_to_nhwc_noise_rows(src, offs, noise[0], noise[1], x0, erows, B, C, H * W, lay.cin_pad, lde, dt):
-                        done = True
-                        loss_rows = (erows, lde)
-            if done:
-                pass
-            elif lazy:  # windows still inside the dataset array: convert them in place where the fused kernel takes the shape
-                done = regen and x.data.is_contiguous() and x.data.dtype == torch.float32 and \
-                    ops.windows_to_nhwc_noise(x.data, x.offsets(), noise[0], noise[1], x0, B, C, H * W, lay.cin_pad, dt)
-                if not done:
-                    x = x.materialize().contiguous().float()
-            if done:
-                pass
-            elif regen:
-                if not ops.nchw_to_nhwc_noise(x, noise[0], noise[1], x0, B, C, H * W, lay.cin_pad, dt):
-                    eps = torch.empty_like(x)
-                    ops.philox_normal(eps, eps.numel(), noise[0])
-                    ops.nchw_to_nhwc(x, eps, noise[1], x0, B, C, H * W, lay.cin_pad, dt)
-            else:
-                ops.nchw_to_nhwc(x, noise[0] if noise else None, noise[1] if noise else None, x0, B, C, H * W, lay.cin_pad, dt)
-
-        def conv3(name, xin, Hi, Wi, Ho, Wo, mode, act=ACT_NONE, res=None, ldy=None, cout=None, y2=None, want_ln=None, loss=None,
-                  resn=None, no_y=False):
-            """want_ln: None, or the consumer's LayerNorm to emit from this conv's epilogue: ("mod", modulation rows) for a
-            residual block, ("plain", None) for an up-block.  Returns (y, geometry, record[, LN output or None]).
-            The chain form (res_block): ``resn`` = dict(rstd, mean, m) -- ``res`` holds normalised rows and the residual is rebuilt from
-            them; ``no_y`` -- the result is not written (y is returned as None), the emitted LayerNorm keeps its mean next to its 1/sigma."""
-            rec = lay.convs[name]
-            ldy_ = ldy or rec.rows
-            y = torch.empty((B * Ho * Wo, ldy_), dtype=T, device=dev) if not no_y else None
-            g = self._geom(B, Hi, Wi, rec.kstride, Ho, Wo, cout or rec.rows, ldy_, rec.rows, mode)
-            hn = None
-            lnf = None
-            if want_ln is not None and act == ACT_NONE and y2 is None and ops.conv_lnfwd_supported(g, dt):
-                hn = torch.empty((B * Ho * Wo, ldy_), dtype=T, device=dev)
-                lnf = dict(y=hn, m=want_ln[1], ldm=ldm if want_ln[1] is not None else 0, eps=LN_EPS, unbiased=self.ln_unbiased)
-                if train and self.keep_ln_stats and want_ln[0] == "mod":
-                    # training: the epilogue also leaves every pixel row's 1/sigma; the block's backward then takes its LayerNorm
-                    # statistics from here and the normalised rows (kept anyway: conv1's input) instead of recomputing both (res_block)
-                    lnf["rstd"] = hn._c2w_rstd = torch.empty((B * Ho * Wo,), dtype=torch.float32, device=dev)
-                if no_y:
-                    lnf["mean"] = hn._c2w_mean = torch.empty((B * Ho * Wo,), dtype=torch.float32, device=dev)
-            if no_y or resn is not None:  # (the rebuilt residual lives in the LayerNorm-emitting epilogue; an output that is not written needs its statistics kept)
-                assert lnf is not None and (not no_y or "rstd" in lnf), "chain form without a fused LayerNorm (run_blocks decides both from the same answers)"
-            # padded operand (network input at C = 65: rows of 128 channels): channels >= rec.cin are zero in x and in w -- a promise the
-            # 16x16-tile kernel turns into fewer K steps
-            wop, wpk = self._conv_weights("f", rec, dt, g)
-            kw = {}
-            if loss is not None and self.deterministic:  # the workgroups' loss sums in a fixed order
-                kw["det"] = self.det_scratch(self._det_bytes(("conv_loss", self._gkey(g), dt), lambda: ops.conv_det_scratch_bytes(g, dt, loss=True)))
-            ops.conv(xin, wop, self._b(rec), y if y is not None else hn, g, dt, act=act, res=res, y2=y2, lnf=lnf,
-                     kvalid=rec.cin if rec.kstride != rec.cin else 0, wpacked=wpk, loss=loss, resn=resn, no_y=no_y, **kw,
-                     splitk=self._splitk(g, dt, act) if (not train and lnf is None and y2 is None and loss is None and not wpk) else None)
-            if self.debug_trace is not None and y is not None:
-                self.debug_trace.append((name, y, dict(x=xin, w=self._w(rec, dt), g=g, act=act, res=res)))
-                if hn is not None:
-                    self.debug_trace.append((name + " [LayerNorm emitted]", hn))
-            if want_ln is not None:
-                return y, g, rec, hn
-            return y, g, rec
-
-        def dgrad(rec, gy, Hi, Wi, Ho, Wo, mode, ld_out, mul=None, res=None, ln=None, mulmode=MUL_DSILU):
-            """input gradient = implicit GEMM over gy with the transposed (and flipped) weights; (Hi,Wi) = gy's grid.
-            ``ln``: LayerNorm-backward arguments to fuse into the epilogue; returns None when the kernel cannot fuse them."""
-            g = self._geom(B, Hi, Wi, rec.dg_ld, Ho, Wo, ld_out, ld_out, rec.cin, mode)
-            if ln is not None and not ops.conv_lnbwd_supported(g, dt):
-                return None
-            dx = torch.empty((B * Ho * Wo, ld_out), dtype=T, device=dev)
-            # output conv at C = 65: gy rows are padded to dg_ld = 128 channels, the padding is zero (mse_loss_grad) and so are the
-            # operand's columns there
-            wop, wpk = self._conv_weights("d", rec, dt, g, fused_ln_bwd=ln is not None)
-            kw = {}
-            if ln is not None and ln.get("dm") is not None and self.deterministic:  # the modulation gradient in a fixed order
-                kw["det"] = self.det_scratch(self._det_bytes(("conv_ln", self._gkey(g), dt, ln["ldm"]),
-                                                             lambda: ops.conv_det_scratch_bytes(g, dt, ln_ldm=ln["ldm"])))
-            ops.conv(gy, wop, None, dx, g, dt, res=res, mul=mul, mulmode=mulmode, ln=ln,
-                     kvalid=rec.rows if rec.dg_ld != rec.rows else 0, wpacked=wpk, **kw)
-            return dx
-
-        def res_block(b: BlockSpec, xin, Hc, Wc, h0=None, want_ln=None, elide=False):
-            """h0: LN(xin + m) if the producer of xin already emitted it; want_ln: the consumer's LayerNorm to emit from
-            conv2's epilogue (see conv3).  Returns (block output, consumer's LN input or None).
-            The chain form (round 6; training, 16-bit, 128-channel levels on the 16x16-tile kernel): ``xin`` None -- the previous block did
-            not write its output; this block's residual is rebuilt inside conv2's epilogue from h0 and the statistics that came with it
-            (x = h0 / rstd + mean - m); ``elide`` -- this block does not write ITS output either (returned as None): the next block of the
-            side is its only reader besides the LayerNorm emitted here."""
-            p = "unet." + b.key
-            Cc = b.channels
-            npix = B * Hc * Wc
-            m = m_all.view(-1)[b.mod_offset:]
-            rstd0 = getattr(h0, "_c2w_rstd", None) if h0 is not None else None
-            if xin is None:
-                assert rstd0 is not None and getattr(h0, "_c2w_mean", None) is not None
-            if h0 is None:
-                h0 = torch.empty((npix, Cc), dtype=T, device=dev)
-                ops.ln_forward(xin, m, h0, npix, Hc * Wc, Cc, ldm, LN_EPS, self.ln_unbiased, dt)
-            # training: conv1's epilogue writes silu(a) for the next conv and silu'(a) for the backward pass; the pre-activation
-            # itself is never stored
-            d1 = torch.empty((npix, Cc), dtype=T, device=dev) if train else None
-            mulmode = MUL_PLAIN
-            act_inf, act_train = (ACT_RELU, ACT_RELU_PAIR) if lay.activation == "relu" else (ACT_SILU, ACT_SILU_PAIR)
-            h1, g1, r1 = conv3(p + ".residue.1", h0, Hc, Wc, Hc, Wc, CONV_S1, act=act_train if train else act_inf, y2=d1)
-            if want_ln is not None:
-                resn = dict(rstd=rstd0, mean=h0._c2w_mean, m=m) if xin is None else None
-                out, g2, r2, hn = conv3(p + ".residue.3", h1, Hc, Wc, Hc, Wc, CONV_S1, res=xin if xin is not None else h0, want_ln=want_ln,
-                                        resn=resn, no_y=elide)
-            else:
-                (out, g2, r2), hn = conv3(p + ".residue.3", h1, Hc, Wc, Hc, Wc, CONV_S1, res=xin), None
-            if train:
-                def bw(gy):
-                    self._wg(h1, gy, r2, g2, dt, group=True)
-                    da1 = dgrad(r2, gy, Hc, Wc, Hc, Wc, CONV_S1, Cc, mul=d1, mulmode=mulmode)
-                    self._wg(h0, da1, r1, g1, dt, group=True)
-                    dm = dm_all.view(-1)[b.mod_offset:]
-                    # conv1's input gradient feeds LN's backward directly: fused into the conv epilogue where the kernel
-                    # holds whole channel rows (128-channel levels in bf16), a separate pass otherwise
-                    if rstd0 is not None:  # the producer's epilogue kept the statistics: h0 = the normalised rows, rstd0 their 1/sigma
-                        lnb = dict(x=h0, rstd=rstd0, m=None, dm=dm, ldm=ldm, eps=LN_EPS, unbiased=self.ln_unbiased)
-                    else:
-                        lnb = dict(x=xin, m=m, dm=dm, ldm=ldm, eps=LN_EPS, unbiased=self.ln_unbiased)
-                    dx = dgrad(r1, da1, Hc, Wc, Hc, Wc, CONV_S1, Cc, res=gy, ln=lnb)
-                    if dx is None:
-                        assert xin is not None, "chain form: the fused LayerNorm backward this block was built on is gone (knobs changed between forward and backward?)"
-                        dh0 = dgrad(r1, da1, Hc, Wc, Hc, Wc, CONV_S1, Cc)
-                        dx = torch.empty_like(dh0)
-                        kw = {}
-                        if self.deterministic:
-                            kw["det"] = self.det_scratch(self._det_bytes(("ln", npix, Hc * Wc, Cc, ldm),
-                                                                         lambda: ops.ln_backward_det_scratch_bytes(npix, Hc * Wc, Cc, ldm)))
-                        ops.ln_backward(dh0, xin, m, gy, dx, dm, npix, Hc * Wc, Cc, ldm, LN_EPS, self.ln_unbiased, dt, **kw)
-                    tape.done(r1.w_off)  # behind the block's last launch: "done" = gradients final AND weights (copies included) no longer read
-                    return dx
-                tape.steps.append(bw)
-            return out, hn
-
-        def attn_block(b: BlockSpec, xin, Hc, Wc):
-            p = "unet." + b.key
-            Cc = b.channels
-            Tn = Hc * Wc
-            npix = B * Tn
-            rq, rp = lay.convs[p + ".qkv"], lay.convs[p + ".proj_out"]
-            hl = torch.empty((npix, Cc), dtype=T, device=dev)
-            ops.ln_forward(xin, None, hl, npix, Tn, Cc, 0, LN_EPS, self.ln_unbiased, dt)
-            qkv = torch.empty((npix, 3 * Cc), dtype=T, device=dev)
-            gq = self._geom(npix, 1, 1, Cc, 1, 1, 3 * Cc, 3 * Cc, 3 * Cc, CONV_1X1)
-            ops.conv(hl, self._w(rq, dt), self._b(rq), qkv, gq, dt)
-            o = torch.empty((npix, Cc), dtype=T, device=dev)
-            lse = torch.empty((npix,), dtype=torch.float32, device=dev) if train else None
-            ops.attention_forward(qkv, o, lse, B, Tn, Cc, dt)
-            if self.debug_trace is not None:
-                self.debug_trace += [(p + " qkv", qkv), (p + " attention", o)]
-            out = torch.empty((npix, Cc), dtype=T, device=dev)
-            gp = self._geom(npix, 1, 1, Cc, 1, 1, Cc, Cc, Cc, CONV_1X1)
-            ops.conv(o, self._w(rp, dt), self._b(rp), out, gp, dt, res=xin)
-            if train:
-                def bw(gy):
-                    self._wg(o, gy, rp, gp, dt, group=True)  # the six proj_out / six qkv weight gradients of the level: one launch each
-                    do = torch.empty((npix, Cc), dtype=T, device=dev)
-                    ops.conv(gy, self._wT(rp, dt), None, do, self._geom(npix, 1, 1, Cc, 1, 1, Cc, Cc, Cc, CONV_1X1), dt)
-                    dqkv = torch.empty_like(qkv)
-                    delta = torch.empty((npix,), dtype=torch.float32, device=dev)
-                    ops.attention_backward(qkv, o, do, lse, delta, dqkv, B, Tn, Cc, dt)
-                    self._wg(hl, dqkv, rq, gq, dt, group=True)
-                    dhl = torch.empty((npix, Cc), dtype=T, device=dev)
-                    ops.conv(dqkv, self._wT(rq, dt), None, dhl, self._geom(npix, 1, 1, 3 * Cc, 1, 1, Cc, Cc, Cc, CONV_1X1), dt)
-                    tape.done(rq.w_off)
-                    dx = torch.empty_like(dhl)
-                    ops.ln_backward(dhl, xin, None, gy, dx, None, npix, Tn, Cc, 0, LN_EPS, self.ln_unbiased, dt)
-                    return dx
-                tape.steps.append(bw)
-            return out
-
-        # ---- descent
-        Hc, Wc = H, W
-        lv0 = lay.levels[0]
-        def mod_of(b: BlockSpec):
-            return ("mod", m_all.view(-1)[b.mod_offset:])
-
-        # the network-input conv emits the first residual block's LayerNorm input from its epilogue, like every block's second conv
-        first0 = lv0.descent[0] if lv0.descent else None
-        if first0 is not None and first0.kind == "res":
-            cur, g_h0, r_h0, hn0 = conv3("unet." + lv0.head_key, x0, H, W, H, W, CONV_S1, want_ln=mod_of(first0))
-        else:  # nothing consumes a LayerNorm of the head conv's output: do not ask the kernel for one
-            (cur, g_h0, r_h0), hn0 = conv3("unet." + lv0.head_key, x0, H, W, H, W, CONV_S1), None
-        if train:
-            def bw_head0(gy, x0=x0, g=g_h0, rec=r_h0):
-                self.flush_wgrad_groups()
-                self._wgrad(rec, x0, gy, g, dt)
-                dx0 = dgrad(rec, gy, H, W, H, W, CONV_S1, lay.cin_pad) if want_dx else None
-                tape.done(rec.w_off)
-                return dx0
-            tape.steps.append(bw_head0)
-        def chain_ok(Cc, Hc, Wc):
-            """Do conv2 (LayerNorm emission with lnf_mean / rebuilt residual / no output) and the next block's fused LayerNorm backward
-            exist for a residual block of this level?  One answer per level geometry."""
-            g = self._geom(B, Hc, Wc, Cc, Hc, Wc, Cc, Cc, Cc, CONV_S1)
-            return dt != DTYPE_F32 and ops.conv_lnfwd_chain_supported(g, dt) and ops.conv_lnbwd_supported(g, dt)
-
-        def run_blocks(blocks, cur, Hc, Wc, h0, tail_ln):
-            """The blocks of one level side in order.  Each residual block asks its producer -- the previous block's second
-            conv -- for its LayerNorm input; ``tail_ln`` is what the consumer after the last block wants.  Returns the
-            output and that consumer's LN input (None if it was not fused)."""
-            hn = h0
-
-            def want_of(j):  # the LayerNorm block j's second conv emits for its consumer
-                nb = blocks[j + 1] if j + 1 < len(blocks) else None
-                return (mod_of(nb) if nb.kind == "res" else None) if nb is not None else tail_ln
-            for j, b in enumerate(blocks):
-                if b.kind == "res":
-                    nb = blocks[j + 1] if j + 1 < len(blocks) else None
-                    want = want_of(j)
-                    # chain form: this block's output has no reader but the next block of the side (its LayerNorm comes out of this
-                    # block's conv2, its residual add can rebuild the sum) -- where the kernels exist, it is not written.  The rebuilding
-                    # lives in the LayerNorm-emitting epilogue, so the NEXT block's conv2 must emit one too (a side's last block does
-                    # only in front of an up-block)
-                    elide = train and self.chain_blocks and self.keep_ln_stats and nb is not None and nb.kind == "res" and \
-                        want_of(j + 1) is not None and chain_ok(b.channels, Hc, Wc)
-                    cur, hn = res_block(b, cur, Hc, Wc, h0=hn, want_ln=want, elide=elide)
-                else:
-                    cur, hn = attn_block(b, cur, Hc, Wc), None
-            return cur, hn
-
-        skips: List[torch.Tensor] = []
-        for i, lv in enumerate(lay.levels):
-            if i > 0:
-                xin = cur
-                Hp, Wp = Hc, Wc
-                Hc, Wc = Hc // 2, Wc // 2
-                cur, g_h, r_h = conv3("unet." + lv.head_key, xin, Hp, Wp, Hc, Wc, CONV_S2)
-                if train:
-                    def bw_head(gy, xin=xin, g=g_h, rec=r_h, Hp=Hp, Wp=Wp, Hc=Hc, Wc=Wc, lvl=i - 1):
-                        self.flush_wgrad_groups()  # the level below is complete: its residual-block weight gradients go out together
-                        self._wg(xin, gy, rec, g, dt)
-                        # dx of the stride-2 conv + the gradient that arrived through the skip connection (model/nn.py:238)
-                        dxs = dgrad(rec, gy, Hc, Wc, Hp, Wp, CONV_TS2, rec.cin, res=tape.gskip.pop(lvl))
-                        tape.done(rec.w_off)
-                        return dxs
-                    tape.steps.append(bw_head)
-            cur, _ = run_blocks(lv.descent, cur, Hc, Wc, hn0 if i == 0 else None, None)
-            if i < L - 1:
-                skips.append(cur)
-        # ---- ascent
-        h0_carry = None  # LN input of the level's first block when the up-conv below already produced it
-        for i in reversed(range(L)):
-            lv = lay.levels[i]
-            cur, hl_ready = run_blocks(lv.ascent, cur, Hc, Wc, h0_carry, ("plain", None) if i > 0 else None)
-            h0_carry = None
-            if i > 0:
-                xin = cur
-                Cc = lv.channels
-                npix = B * Hc * Wc
-                if hl_ready is not None:
-                    hl = hl_ready
-                else:
-                    hl = torch.empty((npix, Cc), dtype=T, device=dev)
-                    ops.ln_forward(xin, None, hl, npix, Hc * Wc, Cc, 0, LN_EPS, self.ln_unbiased, dt)
-                Hl, Wl = Hc, Wc
-                Hc, Wc = Hc * 2, Wc * 2
-                rec_t = lay.convs["unet." + lv.tail_key]
-                # Upsample(nearest, x2) is never materialised (model/nn.py:184): the halo-patch kernels fetch patch pixel (ih, iw) from
-                # (ih >> 1, iw >> 1) of the low-resolution map (conv and weight gradient alike); grids they do not tile go to the gather
-                # kernel, which folds the upsampling into its per-tap gather.
-                nxt = lay.levels[i - 1].ascent[0] if lay.levels[i - 1].ascent else None
-                if nxt is not None and nxt.kind == "res":  # the up-conv also emits the next level's first LayerNorm input
-                    cur, g_t, r_t, h0_carry = conv3("unet." + lv.tail_key, hl, Hl, Wl, Hc, Wc, CONV_UP, res=skips.pop(), want_ln=mod_of(nxt))
-                else:
-                    cur, g_t, r_t = conv3("unet." + lv.tail_key, hl, Hl, Wl, Hc, Wc, CONV_UP, res=skips.pop())
-                if train:
-                    def bw_tail(gy, xin=xin, hl=hl, g=g_t, rec=r_t, Hl=Hl, Wl=Wl, Hu=Hc, Wu=Wc, Cc=Cc, lvl=i - 1):
-                        self.flush_wgrad_groups()  # the ascent side of the level above is complete
-                        tape.gskip[lvl] = gy  # the skip operand receives the same gradient
-                        self._wg(hl, gy, rec, g, dt)
-                        # gradient w.r.t. the low-resolution map = 2x2 sums of the gradient w.r.t. its upsampling (adjoint of Upsample):
-                        # summed in the input-gradient kernel's epilogue where it supports that -- the full-resolution gradient is
-                        # then never written (537 MB at the top level) -- else a pooling pass behind it
-                        gd = self._geom(B, Hu, Wu, rec.dg_ld, Hu, Wu, Cc, Cc, rec.cin, CONV_S1)
-                        gl = torch.empty((B * Hl * Wl, Cc), dtype=T, device=dev)
-                        if ops.conv_pool2_supported(gd, dt):
-                            wop, wpk = self._conv_weights("d", rec, dt, gd)
-                            ops.conv(gy, wop, None, gl, gd, dt, pool2=True, wpacked=wpk)
-                        else:
-                            gu = dgrad(rec, gy, Hu, Wu, Hu, Wu, CONV_S1, Cc)
-                            ops.sumpool2(gu, gl, B, Hl, Wl, Cc, dt)
-                        dx = torch.empty_like(gl)
-                        ops.ln_backward(gl, xin, None, None, dx, None, B * Hl * Wl, Hl * Wl, Cc, 0, LN_EPS, self.ln_unbiased, dt)
-                        tape.done(rec.w_off)
-                        return dx
-                    tape.steps.append(bw_tail)
-            else:
-                xin = cur
-                if fold is not None and not train and nhwc_out and self._fold_output(fold, "unet." + lv.tail_key, xin, B, Hc, Wc, dt):
-                    return None
-                lfuse = None
-                if loss_rows is not None:
-                    lfuse = dict(sum=loss["sum"], gscale=loss["gscale"], scaler=loss.get("scaler"), eps=loss_rows[0], lde=loss_rows[1], C=lay.out_channels)
-                cur, g_t, r_t = conv3("unet." + lv.tail_key, xin, Hc, Wc, Hc, Wc, CONV_S1, ldy=lay.cout_pad, cout=lay.cout_pad, loss=lfuse)
-                if train:
-                    tape.meta["loss_fused"] = lfuse is not None
-                if train:
-                    def bw_tail0(gy, xin=xin, g=g_t, rec=r_t, Hc=Hc, Wc=Wc, Cc=lv.channels):
-                        gw = dict(g)
-                        gw["Cout"] = rec.rows
-                        self._wg(xin, gy, rec, gw, dt)
-                        dxt = dgrad(rec, gy, Hc, Wc, Hc, Wc, CONV_S1, Cc)
-                        tape.done(rec.w_off)
-                        return dxt
-                    tape.steps.append(bw_tail0)
-        if train:
+        fp = ForwardPass(self, tape, dt, dev, B, ldm, want_dx)  # the launches: forward.py
+        fp.embed(tt, Bt, forcing)
+        x0, loss_rows = (x_nhwc, None) if x_nhwc is not None else fp.to_nhwc(x, lazy, noise, C, H, W, loss, nhwc_out)
+        outs = fp.descend(x0, H, W)
+        cur = fp.ascend(outs, H >> (L - 1), W >> (L - 1))
+        cur = fp.output(cur, H, W, fold if nhwc_out else None, loss, loss_rows)
+        if cur is None:  # folded: the trajectories were written
+            return None
+        if tape is not None:
             tape.meta.update(B=B, C=C, H=H, W=W, dt=dt, out_nhwc=cur, ldm=ldm, Bt=Bt)
         if nhwc_out:
             return cur
@@ -1219,17 +878,6 @@ class Engine:
         ops.nhwc_to_nchw(cur, y, B, lay.out_channels, H * W, lay.cout_pad, dt)
         return y
 
-    use_center_conv = os.environ.get("C2W_NO_CENTER_CONV") != "1"  # A/B knob (DESIGN.md section 10)
-    # Opt-in (C2W_LN_CHAIN=1 or the attribute): the chain form of a level side -- residual-block outputs that only the next block reads are
-    # not written, the next block rebuilds its residual from the LayerNorm rows this one emitted (res_block).  Measured at B = 128, bf16
-    # (profiles/r06_experiments.md): -0.23 ms per step (five 128-channel launches lose their 537 / 134 MB store), but the rebuilt
-    # residual carries the rounding of h = LN(x + m) scaled by sigma -- 2^-9 |x + m - mean| instead of 2^-9 |x| -- and where the modulation
-    # dominates the block input that is MORE than rounding x itself: against the CPU oracle the worst gradient tensor moves from
-    # 8.7e-3 to 1.7e-2 relative L2 (bf16; fp16 5e-3 -> 8.5e-3 of the output scale).  Parity before 0.5 %: off.
-    chain_blocks = os.environ.get("C2W_LN_CHAIN") == "1"
-    use_splitk = os.environ.get("C2W_NO_SPLITK") is None  # A/B knob: under-filled inference convs as one workgroup per tile (rounds 1-5)
-    fuse_loss = os.environ.get("C2W_NO_LOSS_FUSION") is None  # A/B knob: the loss tail as its own pass (rounds 1-5); the library reads the same variable
-    use_gemv = os.environ.get("C2W_NO_GEMV") != "1"  # A/B knob: one-row Linear layers as matrix-vector products
 
     def _fold_output(self, fold: dict, name: str, xin: torch.Tensor, B: int, H: int, W: int, dt: int) -> bool:
         """The output convolution of a batch of trajectory windows, restricted to the frames fold() keeps (see forward).  False: not
@@ -1267,12 +915,10 @@ class Engine:
         z = self._linear(name, x, rows, ACT_NONE, None)
         if add is not None:
             z.add_(add)  # (rows, E) fp32: the one tensor-arithmetic line of the forward; its adjoint hands gz to both Linears unchanged
-        if tape is None:
-            h = torch.empty_like(z)
-            ops.silu(z, h, z.numel(), DTYPE_F32)
-            return h
         h = torch.empty_like(z)
         ops.silu(z, h, z.numel(), DTYPE_F32)
+        if tape is None:
+            return h
         rec = self.layout.convs[name]
         g = self._geom(rows, 1, 1, rec.kstride, 1, 1, rec.rows, rec.rows, rec.rows, CONV_1X1)
 

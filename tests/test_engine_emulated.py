@@ -377,7 +377,7 @@ def test_weight_gradients_of_a_level_go_out_together_and_done_waits_for_them(emu
 
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])
 def test_residual_blocks_whose_intermediate_outputs_are_never_written(emu, monkeypatch, precision):
-    """Round 6, the chain form of a level side (model/nn.py:27-28,146-159; engine.res_block): block k's second conv emits the next block's
+    """Round 6, the chain form of a level side (model/nn.py:27-28,146-159; forward.ForwardPass.res_block): block k's second conv emits the next block's
     normalised input with its mean and 1/sigma and does NOT write the block output; block k + 1 rebuilds its residual from them.  Against
     the written form (emu_ops.CHAIN off) on a three-block level: same loss and gradients up to the 16-bit rounding the written form
     applies to the intermediate outputs, and against the fp32 oracle inside the mode's usual tolerance; the launches are counted."""

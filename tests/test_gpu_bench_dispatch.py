@@ -566,7 +566,7 @@ def test_step_with_the_fused_loss_tail_equals_the_step_on_the_materialised_noise
     finally:
         ops.conv = real
     assert sum(1 for f in n_fused if f[0]) == 1 and not any(f[0] for f in n_plain)
-    # outputs not written at B = 16: the 128^2 level only (1024 workgroups: the 16x16-tile kernel), descent 1 + ascent 1 (engine.run_blocks;
+    # outputs not written at B = 16: the 128^2 level only (1024 workgroups: the 16x16-tile kernel), descent 1 + ascent 1 (forward.ForwardPass.run_blocks;
     # at the bench's B = 128 the 64^2 level adds descent 1 + ascent 2); each followed by a rebuilt residual
     assert sum(1 for f in n_plain if f[1]) == 2 and sum(1 for f in n_plain if f[2]) == 2 and not any(f[1] or f[2] for f in n_written)
     assert l_fused == pytest.approx(l_plain, rel=2e-5)
