@@ -40,6 +40,102 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
     }
 }
 
+// window_gather_kernel for an arbitrary list of windows: window j starts at frame first[j] of the flattened (members * L) frame array
+// (exact guidance evaluates only the windows whose kept frames are observed, and co-sampled members share a batch).
+template <typename T>
+__global__ __launch_bounds__(256) void window_gather_list_kernel(const float* __restrict__ x, T* __restrict__ y, const int* __restrict__ first,
+                                                                 int n, int CW, int HW, long long frame_stride, int ldc) {
+    constexpr int P = Elem<T>::PER16;
+    const int nvec = ldc / P;
+    const long long total = (long long)n * HW * nvec;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int pix = (int)(i % HW);
+        const long long r = i / HW;
+        const int vec = (int)(r % nvec);
+        const int j = (int)(r / nvec);
+        const float* src = x + (long long)first[j] * frame_stride;
+        float f[P];
+#pragma unroll
+        for (int e = 0; e < P; ++e) {
+            const int c = vec * P + e;
+            f[e] = (c < CW) ? src[(long long)c * HW + pix] : 0.f;
+        }
+        *(u32x4_t*)(y + ((size_t)j * HW + pix) * ldc + vec * P) = pack16<T>(f);
+    }
+}
+
+// The adjoint of fold for a list of windows: the output gradient of window j is delta on the slots fold keeps of it (the centre frame;
+// the leading k of a trajectory's first window, kind bit 0; the trailing k of its last, kind bit 1) where that frame is observed, and
+// zero everywhere else -- the padding channels of the row included.  delta: [members][nobs][F][HW] fp32, observation o = frame / t_step.
+template <typename T>
+__global__ __launch_bounds__(256) void window_cotangent_list_kernel(const float* __restrict__ delta, T* __restrict__ dy,
+                                                                    const int* __restrict__ first, const int* __restrict__ kind, int n, int L,
+                                                                    int F, int HW, int k, int t_step, int nobs, int ldc) {
+    constexpr int P = Elem<T>::PER16;
+    const int nvec = ldc / P;
+    const int CW = (2 * k + 1) * F;
+    const long long total = (long long)n * HW * nvec;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int pix = (int)(i % HW);
+        const long long r = i / HW;
+        const int vec = (int)(r % nvec);
+        const int j = (int)(r / nvec);
+        const int member = first[j] / L, i0 = first[j] % L, kd = kind[j];
+        float f[P];
+#pragma unroll
+        for (int e = 0; e < P; ++e) {
+            const int c = vec * P + e;
+            const int tau = c / F, frame = i0 + tau;
+            const bool kept = c < CW && (tau == k || (tau < k && (kd & 1)) || (tau > k && (kd & 2)));
+            const bool observed = frame % t_step == 0 && frame / t_step < nobs;
+            f[e] = (kept && observed) ? delta[(((long long)member * nobs + frame / t_step) * F + (c - tau * F)) * HW + pix] : 0.f;
+        }
+        *(u32x4_t*)(dy + ((size_t)j * HW + pix) * ldc + vec * P) = pack16<T>(f);
+    }
+}
+
+// The adjoint of the gather for a list of windows, in gather form: one thread owns V consecutive pixels of one plane (frame l, variable f)
+// of the trajectory and adds scale * (the sum, in ascending j, over the windows that contain frame l, of their input gradient at slot
+// l - first[j]) -- no atomics, a fixed order: the same bits launch after launch.  A block works on ONE frame, so the scan of the list
+// is uniform over the block.  dx: [n][w F][HW] fp32; frames l0 .. l0 + nl - 1 of the flattened (members * L) frame array are visited.
+template <int V>
+__global__ __launch_bounds__(256) void window_grad_fold_list_kernel(const float* __restrict__ dx, float* __restrict__ out,
+                                                                    const int* __restrict__ first, int n, int l0, int bpf, int F, int HW, int k,
+                                                                    float scale) {
+    const int l = l0 + (int)(blockIdx.x / bpf);
+    const int w = 2 * k + 1;
+    const int per_frame = F * HW / V;  // HW % V == 0: a vector never straddles two planes
+    for (int i = (int)(blockIdx.x % bpf) * blockDim.x + threadIdx.x; i < per_frame; i += bpf * blockDim.x) {
+        float s[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = 0.f;
+        bool any = false;
+        for (int j = 0; j < n; ++j) {
+            const int d = l - first[j];
+            if (d < 0 || d >= w) continue;
+            any = true;
+            const float* src = dx + ((long long)j * w + d) * F * HW + (long long)i * V;
+            if constexpr (V == 4) {
+                const f32x4_t v = *(const f32x4_t*)src;
+#pragma unroll
+                for (int e = 0; e < V; ++e) s[e] += v[e];
+            } else {
+                s[0] += src[0];
+            }
+        }
+        if (!any) continue;
+        float* dst = out + (long long)l * F * HW + (long long)i * V;
+        if constexpr (V == 4) {
+            f32x4_t o = *(f32x4_t*)dst;
+#pragma unroll
+            for (int e = 0; e < V; ++e) o[e] += scale * s[e];
+            *(f32x4_t*)dst = o;
+        } else {
+            dst[0] += scale * s[0];
+        }
+    }
+}
+
 // fold (src/thor/score.py:76-88 / _window_score :111-141): keep the centre frame of every window, the leading k frames of
 // the first window and the trailing k frames of the last one.
 // One thread per (window, pixel): the kept channels of a window are one contiguous run of its NHWC row -- [k F, (k+1) F) for an
@@ -102,9 +198,12 @@ __global__ __launch_bounds__(256) void correct_kernel(float* __restrict__ x, con
 //  gammav == nullptr: the scalar `gamma` for every variable)
 //   eps <- eps - sigma * (1/mu) * A^T(err/var)          (A^T spreads err/(var s^2) over the s x s cell)
 // one wave per (observed frame, channel, pooled cell)
+// DELTA: eps is only read and delta[o][c][H][W] (compact: observed frames only) = -corr is written instead -- what exact guidance puts on
+// the network's output gradient; eps + delta is then bit for bit the eps the in-place form leaves (a + (-b) == a - b).
+template <bool DELTA>
 __global__ __launch_bounds__(256) void guidance_kernel(const float* __restrict__ x, float* __restrict__ eps, const float* __restrict__ yobs,
-                                                       const float* __restrict__ stdv, const float* __restrict__ gammav, int nobs, int F, int H,
-                                                       int W, int s, int t_step, float mu, float sigma, float gamma) {
+                                                       const float* __restrict__ stdv, const float* __restrict__ gammav, float* __restrict__ delta, int nobs,
+                                                       int F, int H, int W, int s, int t_step, float mu, float sigma, float gamma) {
     const int lane = threadIdx.x & 63;
     const int PH = H / s, PW = W / s;
     const long long ncell = (long long)nobs * F * PH * PW;
@@ -128,9 +227,14 @@ __global__ __launch_bounds__(256) void guidance_kernel(const float* __restrict__
     const float var = sd * sd + (gammav != nullptr ? gammav[c] : gamma) * ratio * ratio;
     const float err = yobs[(((long long)o * F + c) * PH + ph) * PW + pw] - mean;
     const float corr = sigma * (err / var) / (mu * (float)(s * s));
-    for (int q = lane; q < s * s; q += 64) {
-        const long long idx = base + (long long)(ph * s + q / s) * W + pw * s + q % s;
-        eps[idx] -= corr;
+    if constexpr (DELTA) {
+        const long long dbase = ((long long)o * F + c) * H * W;
+        for (int q = lane; q < s * s; q += 64) delta[dbase + (long long)(ph * s + q / s) * W + pw * s + q % s] = -corr;
+    } else {
+        for (int q = lane; q < s * s; q += 64) {
+            const long long idx = base + (long long)(ph * s + q / s) * W + pw * s + q % s;
+            eps[idx] -= corr;
+        }
     }
 }
 
@@ -233,7 +337,8 @@ static int guidance_launch(const float* x, float* eps, const float* yobs, const 
     if (!x || !eps || !yobs || !stdv || nobs <= 0 || s_step <= 0 || H % s_step || W % s_step || t_step <= 0) return C2W_ERR_BAD_SHAPE;
     const long long ncell = (long long)nobs * F * (H / s_step) * (W / s_step);
     const long long blocks = (ncell + 3) / 4;
-    guidance_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(x, eps, yobs, stdv, gammav, nobs, F, H, W, s_step, t_step, mu, sigma, gamma);
+    guidance_kernel<false><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(x, eps, yobs, stdv, gammav, nullptr, nobs, F, H, W, s_step, t_step, mu,
+                                                                         sigma, gamma);
     return (int)hipGetLastError();
 }
 
@@ -246,6 +351,71 @@ extern "C" int c2w_guidance_per_variable(const float* x, float* eps, const float
                                          int H, int W, int s_step, int t_step, float mu, float sigma, void* stream) {
     if (!gammav) return C2W_ERR_BAD_ARG;
     return guidance_launch(x, eps, yobs, stdv, gammav, nobs, F, H, W, s_step, t_step, mu, sigma, 0.f, stream);
+}
+
+extern "C" int c2w_guidance_delta(const float* x, const float* eps, const float* yobs, const float* stdv, const float* gammav_or_null, float gamma,
+                                  float* delta, int nobs, int F, int H, int W, int s_step, int t_step, float mu, float sigma, void* stream) {
+    if (!x || !eps || !yobs || !stdv || !delta || nobs <= 0 || F <= 0 || s_step <= 0 || H % s_step || W % s_step || t_step <= 0)
+        return C2W_ERR_BAD_SHAPE;
+    const long long ncell = (long long)nobs * F * (H / s_step) * (W / s_step);
+    const long long blocks = (ncell + 3) / 4;
+    guidance_kernel<true><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(x, const_cast<float*>(eps), yobs, stdv, gammav_or_null, delta, nobs, F, H,
+                                                                        W, s_step, t_step, mu, sigma, gamma);
+    return (int)hipGetLastError();
+}
+
+extern "C" int c2w_window_gather_list(const float* x, void* y, const int* first, int n, int F, int HW, int k, int ldc, int dtype, void* stream) {
+    const int CW = (2 * k + 1) * F;
+    const int P = dtype == C2W_DTYPE_F32 ? 4 : 8;
+    if (!x || !y || !first || n <= 0 || F <= 0 || HW <= 0 || k < 0 || ldc < CW || ldc % P) return C2W_ERR_BAD_SHAPE;
+    const long long total = (long long)n * HW * (ldc / P);
+    if (dtype == C2W_DTYPE_F32)
+        window_gather_list_kernel<float><<<grid_for(total), 256, 0, (hipStream_t)stream>>>(x, (float*)y, first, n, CW, HW, (long long)F * HW, ldc);
+    else if (dtype == C2W_DTYPE_BF16)
+        window_gather_list_kernel<bf16_t><<<grid_for(total), 256, 0, (hipStream_t)stream>>>(x, (bf16_t*)y, first, n, CW, HW, (long long)F * HW, ldc);
+    else if (dtype == C2W_DTYPE_F16)
+        window_gather_list_kernel<f16_t><<<grid_for(total), 256, 0, (hipStream_t)stream>>>(x, (f16_t*)y, first, n, CW, HW, (long long)F * HW, ldc);
+    else
+        return C2W_ERR_BAD_ARG;
+    return (int)hipGetLastError();
+}
+
+extern "C" int c2w_window_cotangent_list(const float* delta, void* dy, const int* first, const int* kind, int n, int L, int F, int HW, int k,
+                                         int t_step, int nobs, int ldc, int dtype, void* stream) {
+    const int P = dtype == C2W_DTYPE_F32 ? 4 : 8;
+    if (!delta || !dy || !first || !kind || n <= 0 || L < 2 * k + 1 || F <= 0 || HW <= 0 || k < 0 || t_step <= 0 || nobs <= 0 ||
+        (long long)(nobs - 1) * t_step >= L || ldc < (2 * k + 1) * F || ldc % P)
+        return C2W_ERR_BAD_SHAPE;
+    const long long total = (long long)n * HW * (ldc / P);
+    if (dtype == C2W_DTYPE_F32)
+        window_cotangent_list_kernel<float><<<grid_for(total), 256, 0, (hipStream_t)stream>>>(delta, (float*)dy, first, kind, n, L, F, HW, k, t_step,
+                                                                                              nobs, ldc);
+    else if (dtype == C2W_DTYPE_BF16)
+        window_cotangent_list_kernel<bf16_t><<<grid_for(total), 256, 0, (hipStream_t)stream>>>(delta, (bf16_t*)dy, first, kind, n, L, F, HW, k,
+                                                                                               t_step, nobs, ldc);
+    else if (dtype == C2W_DTYPE_F16)
+        window_cotangent_list_kernel<f16_t><<<grid_for(total), 256, 0, (hipStream_t)stream>>>(delta, (f16_t*)dy, first, kind, n, L, F, HW, k, t_step,
+                                                                                              nobs, ldc);
+    else
+        return C2W_ERR_BAD_ARG;
+    return (int)hipGetLastError();
+}
+
+extern "C" int c2w_window_grad_fold_list(const float* dx, float* out, const int* first, int n, int l0, int nl, int F, int HW, int k, float scale,
+                                         void* stream) {
+    if (!dx || !out || !first || n <= 0 || l0 < 0 || nl <= 0 || F <= 0 || HW <= 0 || k < 0) return C2W_ERR_BAD_SHAPE;
+    const int V = HW % 4 == 0 ? 4 : 1;
+    const long long per_frame = (long long)F * HW / V;
+    if (per_frame > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    long long bpf = (per_frame + 1023) / 1024;  // a thread owns up to four vectors of its frame
+    if (bpf > 64) bpf = 64;
+    if (bpf * nl > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    const unsigned grid = (unsigned)(bpf * nl);
+    if (V == 4)
+        window_grad_fold_list_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(dx, out, first, n, l0, (int)bpf, F, HW, k, scale);
+    else
+        window_grad_fold_list_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(dx, out, first, n, l0, (int)bpf, F, HW, k, scale);
+    return (int)hipGetLastError();
 }
 
 extern "C" int c2w_pool_stride(const float* x, float* y, int nobs, int F, int H, int W, int s_step, int t_step, void* stream) {

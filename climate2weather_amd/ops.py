@@ -540,6 +540,33 @@ def guidance(x, eps, yobs, stdv, nobs, F, H, W, s_step, t_step, mu, sigma, gamma
           "c2w_guidance")
 
 
+def guidance_delta(x, eps, yobs, stdv, delta, nobs, F, H, W, s_step, t_step, mu, sigma, gamma):
+    """delta (nobs, F, H, W) fp32 = what ``guidance`` adds to eps on the observed frames; eps is only read.  ``gamma`` as in ``guidance``."""
+    gv, gs = (gamma, 0.0) if isinstance(gamma, torch.Tensor) else (None, float(gamma))
+    check(_lib.load().c2w_guidance_delta(_p(x), _p(eps), _p(yobs), _p(stdv), _p(gv), gs, _p(delta), nobs, F, H, W, s_step, t_step, mu, sigma,
+                                         _stream()), "c2w_guidance_delta")
+
+
+def window_gather_list(x, y, first, n, F, HW, k, ldc, dtype):
+    """``window_gather`` for the windows that start at the frames ``first[:n]`` (int32 device tensor) of the flattened (members * L) frames."""
+    check(_lib.load().c2w_window_gather_list(_p(x), _p(y), _p(first), n, F, HW, k, ldc, dtype, _stream()), "c2w_window_gather_list")
+
+
+def window_cotangent_list(delta, dy, first, kind, n, L, F, HW, k, t_step, nobs, ldc, dtype):
+    """The adjoint of fold: NHWC output-gradient rows ``dy`` of the windows ``first[:n]`` from delta (members, nobs, F, H, W); ``kind``: bit 0 /
+    bit 1 = the window is its trajectory's first / last (include/c2w_hip.h)."""
+    check(_lib.load().c2w_window_cotangent_list(_p(delta), _p(dy), _p(first), _p(kind), n, L, F, HW, k, t_step, nobs, ldc, dtype, _stream()),
+          "c2w_window_cotangent_list")
+
+
+def window_grad_fold_list(dx, out, first, n, l0, nl, F, HW, k, scale):
+    """The adjoint of the gather: out[l] += scale * (sum of the windows' input gradients dx (n, w F, H, W) at frame l), frames l0 <= l < l0 + nl
+    of the flattened (members * L) frames, in a fixed order."""
+    if (l0 + nl) * F * HW > out.numel() or n * (2 * k + 1) * F * HW > dx.numel():
+        raise ValueError("window_grad_fold_list: frame range or window count outside the tensors")
+    check(_lib.load().c2w_window_grad_fold_list(_p(dx), _p(out), _p(first), n, l0, nl, F, HW, k, scale, _stream()), "c2w_window_grad_fold_list")
+
+
 def pool_stride(x, y, nobs, F, H, W, s_step, t_step):
     check(_lib.load().c2w_pool_stride(_p(x), _p(y), nobs, F, H, W, s_step, t_step, _stream()), "c2w_pool_stride")
 

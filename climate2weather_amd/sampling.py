@@ -30,7 +30,8 @@ def run_ensemble(net, pipeline: Optional[SDAPipeline] = None, *, length: int, n_
                  A=None, y=None, std=None, gamma: float = 1e-2, exact_grad: bool = False, seed: int = 0, rank: Optional[int] = None,
                  world: Optional[int] = None, device=None, precision: Optional[str] = "bf16",
                  on_sample: Optional[Callable[[int, torch.Tensor], None]] = None, show_progressbar: bool = False,
-                 members_per_batch: Optional[int] = None, rng: str = "reference") -> List[Tuple[int, torch.Tensor]]:
+                 members_per_batch: Optional[int] = None, rng: str = "reference",
+                 exact_streamed: Optional[bool] = None) -> List[Tuple[int, torch.Tensor]]:
     rank = int(os.environ.get("RANK", "0")) if rank is None else rank
     world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
     assert num_samples % world == 0, "Number of samples must be divisible by the number of devices."  # exp/downscaling.py:96-98
@@ -56,6 +57,7 @@ def run_ensemble(net, pipeline: Optional[SDAPipeline] = None, *, length: int, n_
             return None
         return ((draw() if n_members == 1 else torch.stack([draw() for _ in range(n_members)], 0)) for _ in range(steps * corrections))
     score_fn = BatchedScoreFunction(net, markov_order=markov_order, batch_size=batch_size, device=device, noise_process=pipeline)
+    score_fn.exact_streamed = exact_streamed  # exact_grad=True window by window: None = beyond exact_tape_windows (score_fn.py)
     if A is not None:
         score_fn.condition_on(A=A, y=y, std=std, gamma=gamma, exact_grad=exact_grad)
     out = []

@@ -18,6 +18,7 @@ from typing import Optional
 import torch
 
 from . import ops
+from .engine import Tape
 from .ops import TORCH_DTYPE
 
 
@@ -56,6 +57,31 @@ def per_channel_std(std, y) -> Optional[torch.Tensor]:
 per_channel = per_channel_std  # the same rule serves gamma
 
 
+def exact_window_list(M: int, L: int, k: int, t_step: int, nobs: int):
+    """The windows exact guidance has to differentiate: ([first], [kind]) in ascending order over M co-sampled members of L frames.
+    log p sums over the observed frames (l % t_step == 0 and l // t_step < nobs) and fold keeps, of window i, frame i + k -- plus frames
+    0 .. k-1 of window 0 and nwin+k .. L-1 of window nwin - 1 -- so a window none of whose kept frames is observed gets a zero output
+    gradient and is left out.  first = m * L + i (the window's first frame in the flattened (M * L) frames), kind = bit 0: the
+    trajectory's first window, bit 1: its last."""
+    w = 2 * k + 1
+    nwin = L - w + 1
+    if nwin < 1:
+        raise ValueError(f"trajectory of {L} frames is shorter than the window {w}")
+
+    def observed(lo, hi):
+        o = -(-lo // t_step)  # first multiple of t_step at or above lo
+        return o * t_step < hi and o < nobs
+
+    first, kind = [], []
+    for i in range(nwin):
+        lo = 0 if i == 0 else i + k
+        hi = L if i == nwin - 1 else i + k + 1
+        if observed(lo, hi):
+            first.append(i)
+            kind.append((1 if i == 0 else 0) | (2 if i == nwin - 1 else 0))
+    return [m * L + i for m in range(M) for i in first], kind * M
+
+
 class AbstractScoreFunction:
     device_resident = True
 
@@ -65,6 +91,7 @@ class AbstractScoreFunction:
         self.unet_kwargs = unet_kwargs if unet_kwargs is not None else {}
         self.likelihood = None
         self._fused_guidance = None
+        self._exact_stream = None
         self.unet.eval()
 
     @property
@@ -79,6 +106,8 @@ class AbstractScoreFunction:
             return self.score_fn(x, t)
         if self._fused_guidance is not None:
             return self._guided_fused(x, t)
+        if self._exact_streamed_wanted(x):
+            return self._guided_exact_streamed(x, t)
         if x.dim() == 5:  # co-sampled members: log p sums over members, its gradient is per member -- member by member
             return torch.stack([self(xm, t) for xm in x], 0)
         # eps - sigma * d(log p)/dx  (src/thor/score.py:24-35).  log p is a scalar, so its Jacobian is one reverse pass:
@@ -111,23 +140,37 @@ class AbstractScoreFunction:
 
         self.likelihood = log_p
         self._fused_guidance = None
-        if isinstance(A, PoolStrideOperator) and not exact_grad:
+        self._exact_stream = None
+        if isinstance(A, PoolStrideOperator):
             std_c, gam_c = per_channel_std(std, y), per_channel(gamma, y)
             if std_c is not None and gam_c is not None:  # any other broadcastable std / gamma (per pixel, per observation, ...) takes the autograd path above
-                self._fused_guidance = dict(A=A, y=y, std=std_c, gamma=float(gam_c) if gam_c.numel() == 1 else gam_c)
+                g = dict(A=A, y=y, std=std_c, gamma=float(gam_c) if gam_c.numel() == 1 else gam_c)
+                if exact_grad:
+                    self._exact_stream = g  # the window-streamed exact gradient (_WindowScore._guided_exact_streamed), where it is eligible and wanted
+                else:
+                    self._fused_guidance = g
         return self
 
-    def _guided_fused(self, x, t):
-        g = self._fused_guidance
-        dev = getattr(self, "device", x.device)
-        xd = x.to(device=dev, dtype=torch.float32).contiguous()
-        L, F, H, W = xd.shape[-4:]
+    def _exact_streamed_wanted(self, x) -> bool:
+        return False  # only the sliding-window score functions have the route
+
+    @staticmethod
+    def _guidance_operands(g, dev, F):
+        """The observation, std and gamma of a fused / streamed guidance record on ``dev`` (moved once)."""
         if g.get("dev") != dev:
             g["y_dev"] = g["y"].to(device=dev, dtype=torch.float32).contiguous()
             std = g["std"].to(dev)
             g["std_dev"] = (std.expand(F) if std.numel() == 1 else std).contiguous()
             g["gamma_dev"] = g["gamma"].to(dev).contiguous() if isinstance(g["gamma"], torch.Tensor) else g["gamma"]  # one per variable, or a float
             g["dev"] = dev
+        return g
+
+    def _guided_fused(self, x, t):
+        g = self._fused_guidance
+        dev = getattr(self, "device", x.device)
+        xd = x.to(device=dev, dtype=torch.float32).contiguous()
+        L, F, H, W = xd.shape[-4:]
+        self._guidance_operands(g, dev, F)
         eps = self.score_fn(xd, t)
         mu, sigma = self.noise_process._mu_sigma_f(float(t))
         nobs = g["y_dev"].shape[0]
@@ -155,6 +198,100 @@ class _WindowScore(AbstractScoreFunction):
         self.num_streams = int(os.environ.get("C2W_SCORE_STREAMS", type(self).num_streams))
         if "C2W_WINDOW_BATCH_FLOOR" in os.environ:
             self.window_batch_floor = int(os.environ["C2W_WINDOW_BATCH_FLOOR"])
+
+    # ---- exact guidance, window by window ("Exact guidance, streamed").  The autograd route above keeps the tape of EVERY window
+    # alive until its one backward and differentiates all of them; here the unguided score comes from the inference evaluation, and only the
+    # windows whose kept frames are observed are re-run with a tape, ``batch_size`` at a time, each tape consumed before the next is made.
+    exact_streamed = None  # None: when M * nwin > exact_tape_windows and the route is eligible; True: always (ValueError if not eligible); False: never
+    exact_tape_windows = 1024  # ~150 GB of bf16 tape at 52 x 128 x 128: half the device; every shorter run keeps the autograd route
+
+    def _exact_stream_blocker(self, x) -> Optional[str]:
+        """Why the streamed exact-gradient route cannot serve this call (None: it can)."""
+        if self._exact_stream is None:
+            return "condition_on(exact_grad=True) with a PoolStrideOperator and a scalar or per-variable std / gamma has not been called"
+        if not _engine_ready(self.unet):
+            return "the network is not engine-backed"
+        if any(p.requires_grad for p in self.unet.parameters()):
+            return "a parameter of the network requires a gradient"
+        if type(x) is not torch.Tensor or _wrapped(x):
+            return "the state is not a plain tensor"
+        if x.requires_grad:
+            return "the state requires a gradient"
+        if x.dim() not in (4, 5):
+            return "the state is neither (L, F, H, W) nor (M, L, F, H, W)"
+        if self.device.type != "cuda" and not ops.EMULATED:
+            return "the score function's device is not a GPU"
+        return None
+
+    def _exact_streamed_wanted(self, x) -> bool:
+        mode = self.exact_streamed
+        if mode is False or (mode is None and self._exact_stream is None):
+            return False
+        why = self._exact_stream_blocker(x)
+        if mode:
+            if why is not None:
+                raise ValueError(f"exact_streamed=True, but {why}")
+            return True
+        if why is not None:
+            return False
+        M = x.shape[0] if x.dim() == 5 else 1
+        return M * (x.shape[-4] - 2 * self.markov_order) > int(self.exact_tape_windows)
+
+    def _guided_exact_streamed(self, x, t):
+        """eps - sigma d(log p)/dx (src/thor/score.py:24-35, exact_grad=True) = eps_raw + delta - sigma J_net:
+        delta = d(log p)/d(eps) on the observed frames (ops.guidance_delta: the fused guidance term), J_net = the overlap-add of the
+        selected windows' vector-Jacobian products with delta placed on the output channels fold keeps."""
+        g = self._exact_stream
+        dev = self.device
+        k = self.markov_order
+        w = 2 * k + 1
+        xd = x.to(device=dev, dtype=torch.float32).contiguous()
+        M = xd.shape[0] if xd.dim() == 5 else 1
+        L, F, H, W = xd.shape[-4:]
+        HW = H * W
+        self._guidance_operands(g, dev, F)
+        A = g["A"]
+        nobs = int(g["y_dev"].shape[0])
+        if (nobs - 1) * A.t_step >= L:
+            raise ValueError(f"{nobs} observations every {A.t_step} frames do not fit a trajectory of {L} frames")
+        with torch.no_grad():
+            eps = self.score_fn(xd, t)  # the inference evaluation: side streams, centre-frame output convolution, co-sampled members
+        mu, sigma = self.noise_process._mu_sigma_f(float(t))
+        delta = torch.empty((M, nobs, F, H, W), dtype=torch.float32, device=dev)
+        xs, es = xd.view(M, L, F, H, W), eps.view(M, L, F, H, W)
+        for m in range(M):  # the same observation guides every member, frame-locally
+            ops.guidance_delta(xs[m], es[m], g["y_dev"], g["std_dev"], delta[m], nobs, F, H, W, A.s_step, A.t_step, mu, sigma, g["gamma_dev"])
+        for m in range(M):  # eps + delta, by the kernel exact_grad=False runs: the same bits
+            ops.guidance(xs[m], es[m], g["y_dev"], g["std_dev"], nobs, F, H, W, A.s_step, A.t_step, mu, sigma, g["gamma_dev"])
+        key = (M, L, k, A.t_step, nobs, dev)
+        lists = g.get("lists")
+        if lists is None or lists[0] != key:
+            first, kind = exact_window_list(M, L, k, A.t_step, nobs)
+            lists = g["lists"] = (key, first, torch.tensor(first, dtype=torch.int32, device=dev), torch.tensor(kind, dtype=torch.int32, device=dev))
+        _, first, first_dev, kind_dev = lists
+        n = len(first)
+        if n == 0:
+            return eps if x.device == dev else eps.to(x.device)
+        eng = self.unet._get_engine()
+        dt = self.unet.compute_dtype()
+        lay = eng.layout
+        if lay.in_channels != w * F:
+            raise ValueError(f"network expects {lay.in_channels} channels, window gives {w * F}")
+        td = torch.as_tensor(t).to(dev)
+        bs = min(self.batch_size or n, n)
+        # one stream, eager launches (never a captured graph): eps is read-modify-written by every batch, in launch order
+        for a in range(0, n, bs):
+            nb = min(bs, n - a)
+            xin = torch.empty((nb * HW, lay.cin_pad), dtype=TORCH_DTYPE[dt], device=dev)
+            ops.window_gather_list(xd, xin, first_dev[a:], nb, F, HW, k, lay.cin_pad, dt)
+            tape = Tape()
+            eng.forward(None, td, dt, x_nhwc=xin, shape=(nb, w * F, H, W), nhwc_out=True, tape=tape, want_dx=True)
+            dy = torch.empty((nb * HW, lay.cout_pad), dtype=TORCH_DTYPE[dt], device=dev)
+            ops.window_cotangent_list(delta, dy, first_dev[a:], kind_dev[a:], nb, L, F, HW, k, A.t_step, nobs, lay.cout_pad, dt)
+            dx = eng.backward(tape, dy, want_dx=True, want_dw=False)
+            ops.window_grad_fold_list(dx, eps, first_dev[a:], nb, first[a], first[a + nb - 1] + w - first[a], F, HW, k, -sigma)
+            del tape, dx, dy, xin  # one batch's tape at a time, whatever L is
+        return eps if x.device == dev else eps.to(x.device)
 
     # reference-compatible helpers (src/thor/score.py:68-88)
     def unfold(self, x):

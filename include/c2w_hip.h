@@ -415,6 +415,25 @@ int c2w_guidance(const float* x, float* eps, const float* yobs, const float* std
  * list-valued `likelihood_gamma` (a (1, C, 1, 1) tensor that src/thor/score.py:55 broadcasts against err) */
 int c2w_guidance_per_variable(const float* x, float* eps, const float* yobs, const float* stdv, const float* gammav, int nobs,
                               int F, int H, int W, int s_step, int t_step, float mu, float sigma, void* stream);
+/* ---- exact guidance (src/thor/score.py:24-35 with exact_grad=True) streamed over the windows whose kept frames are observed.  A batch of
+ * n such windows is two device lists: first[j] = index of the window's first frame in the flattened [members * L] frame array (m * L + i),
+ * kind[j] = bit 0: its trajectory's first window, bit 1: its last. ---- */
+/* c2w_guidance / c2w_guidance_per_variable (gammav_or_null: one gamma per variable, else the scalar `gamma`) with eps only READ:
+ * delta[nobs][F][H][W] = the term those add to eps on the observed frames (eps[o * t_step] + delta[o] reproduces them bit for bit) */
+int c2w_guidance_delta(const float* x, const float* eps, const float* yobs, const float* stdv, const float* gammav_or_null, float gamma,
+                       float* delta, int nobs, int F, int H, int W, int s_step, int t_step, float mu, float sigma, void* stream);
+/* c2w_window_gather for a list: y[j*HW + p][tau*F + f] = x[first[j] + tau][f][p], channels >= (2k+1) F zero */
+int c2w_window_gather_list(const float* x, void* y, const int* first, int n, int F, int HW, int k, int ldc, int dtype, void* stream);
+/* adjoint of fold: dy[j*HW + p][tau*F + f] = delta[first[j] / L][frame / t_step][f][p] where slot tau of window j is kept (tau == k; tau < k
+ * with kind bit 0; tau > k with kind bit 1) and frame = first[j] % L + tau is observed (frame % t_step == 0, frame / t_step < nobs); every
+ * other element of the row, padding included, is zero.  delta: [members][nobs][F][HW] fp32; rows in the compute type */
+int c2w_window_cotangent_list(const float* delta, void* dy, const int* first, const int* kind, int n, int L, int F, int HW, int k,
+                              int t_step, int nobs, int ldc, int dtype, void* stream);
+/* adjoint of the gather: out[l][f][p] += scale * sum_j dx[j][(l - first[j]) F + f][p] over the j with first[j] <= l <= first[j] + 2k, added in
+ * ascending j by the one thread that owns the element (no atomics: bit-identical launch to launch), for the frames l0 <= l < l0 + nl;
+ * frames no window of the list contains are left untouched.  dx: [n][(2k+1) F][HW] fp32 */
+int c2w_window_grad_fold_list(const float* dx, float* out, const int* first, int n, int l0, int nl, int F, int HW, int k, float scale,
+                              void* stream);
 /* the measurement operator itself: y[o][c][ph][pw] = mean of the s x s cell of x[o*t_step][c] (exp/downscaling.py:129-132) */
 int c2w_pool_stride(const float* x, float* y, int nobs, int F, int H, int W, int s_step, int t_step, void* stream);
 /* per-variable affine map over (planes = L*F) planes of HW values: y = x * scale[c] + shift[c], c = plane % F -- the quantile
