@@ -92,6 +92,11 @@ _PROTOS = {
                                     c_int, c_void_p],
     "c2w_sq_err_det": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ulonglong, c_int, c_void_p],
     "c2w_sq_err_noise_det": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ulonglong, c_int, c_void_p],
+    "c2w_sq_err_levels_scratch_bytes": [c_int, c_int, c_int],
+    "c2w_sq_err_levels": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_ulonglong,
+                          c_int, c_void_p],
+    "c2w_sq_err_levels_noise": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                c_ulonglong, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

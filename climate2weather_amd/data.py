@@ -208,6 +208,13 @@ class DeviceWindowFeed:
             parts.append(perm[steps + off])
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
+    def ordered_batch(self, first: int, count: int) -> WindowBatch:
+        """Windows first .. first + count - 1 in DATASET order as a lazy WindowBatch (held-out validation: evaluation.evaluate).  The
+        sampler's cursor and permutations are not consulted: training resumes on the batch it would have drawn anyway."""
+        if first < 0 or count <= 0 or first + count > self.data.shape[0] - self.window + 1:
+            raise IndexError(f"windows {first} .. {first + count - 1} of {self.data.shape[0] - self.window + 1}")
+        return WindowBatch(self.data, torch.arange(first, first + count, dtype=torch.int64, device=self.data.device), self.window)
+
     def next_batch(self, batch: int, lazy: bool = False):
         """``lazy``: return a WindowBatch (indices only) instead of the gathered (B, w*F, H, W) tensor; Trainer.step takes either."""
         idx = self._indices(batch)

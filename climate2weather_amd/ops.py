@@ -400,6 +400,30 @@ def sq_err(y, eps, out, loss_sum, B, C, HW, ldc, dtype, det: Optional[torch.Tens
     return True
 
 
+def sq_err_levels_scratch_bytes(B, C, HW) -> int:
+    n = int(_lib.load().c2w_sq_err_levels_scratch_bytes(B, C, HW))
+    if n < 0:
+        check(n, "c2w_sq_err_levels_scratch_bytes")
+    return n
+
+
+def sq_err_levels(y, eps, t, table, count, per_image, B, C, HW, ldc, K, scratch, dtype) -> bool:
+    """table (K, C) float64 += per-bin, per-channel sums of (y - eps)^2 from NHWC rows ``y``; count (K,) int64 += images per bin;
+    per_image (B,) fp32 or None (include/c2w_hip.h::c2w_sq_err_levels: the fp32 bin rule, the fixed summation order).  ``eps``: an fp32
+    (B,C,H,W) tensor (every shape), or an int seed (the stream the *_noise launchers regenerate; False if the shape is not supported --
+    the caller materialises the stream with philox_normal).  ``scratch``: fp32, >= sq_err_levels_scratch_bytes(B, C, HW)."""
+    if isinstance(eps, int):
+        rc = _lib.load().c2w_sq_err_levels_noise(_p(y), int(eps), _p(t), _p(table), _p(count), _p(per_image), B, C, HW, ldc, K, _p(scratch),
+                                                 _nbytes(scratch), dtype, _stream())
+        if rc == -3:
+            return False
+    else:
+        rc = _lib.load().c2w_sq_err_levels(_p(y), _p(eps), _p(t), _p(table), _p(count), _p(per_image), B, C, HW, ldc, K, _p(scratch),
+                                           _nbytes(scratch), dtype, _stream())
+    check(rc, "c2w_sq_err_levels")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

@@ -342,6 +342,50 @@ class Trainer:
     def loss_scale(self) -> float:
         return float(self.scaler[0].item()) if self.scaler is not None else 1.0
 
+    # ------------------------------------------------------------------ held-out validation
+    def validate(self, data, *, weights="ema", batch: Optional[int] = None, bins: int = 10, seed: int = 0, max_items: Optional[int] = None,
+                 t="stratified", eps: Optional[torch.Tensor] = None, window: Optional[int] = None):
+        """evaluation.evaluate over ``data`` (the pass the reference's loop announces and skips, training_loop.py:327-330) in the trainer's
+        precision; returns the evaluation.LevelLoss (all-reduced over the process group, each rank evaluating its contiguous shard).
+        ``weights``: "ema" (the first rate), a rate of ``ema_rates``, or "net" (the live weights).
+        The weights are evaluated through a COPY of the module built at the first call (copy.deepcopy: its own engine, buffers, caches
+        and scratch), whose flat parameter buffer receives the chosen flat buffer before every validation.  Nothing of the training
+        state is written: parameters, gradients, moments, EMA buffers, the loss-scale state, the progress counters and both of the
+        trainer's generators are bit-for-bit what they were, so a run with validations trains to the same bits as one without.
+        ``t`` / ``eps`` / ``window``: as in evaluation.evaluate (tests inject the draws)."""
+        import copy
+        from . import evaluation
+        if isinstance(weights, str) and weights == "net":
+            src = self.eng.flat
+        elif isinstance(weights, str) and weights == "ema":
+            if not self.ema_flats:
+                raise ValueError("this trainer keeps no EMA (ema_rates is empty): validate(weights='net')")
+            src = self.ema_flats[0]
+        else:
+            hits = [f for r, f in zip(self.ema_rates, self.ema_flats) if float(r) == float(weights)]
+            if not hits:
+                raise ValueError(f"weights must be 'net', 'ema' or one of ema_rates = {self.ema_rates}, got {weights!r}")
+            src = hits[0]
+        vnet = self.__dict__.get("_valid_net")
+        if vnet is None:
+            vnet = copy.deepcopy(self.net)
+            for p in vnet.parameters():
+                p.grad = None
+            self.__dict__["_valid_net"] = vnet
+        veng = vnet._get_engine()
+        if veng.flat.numel() != src.numel():
+            raise RuntimeError("the validation copy's parameter layout differs from the trainer's")
+        with torch.no_grad():
+            veng.flat.copy_(src)
+        veng.weights_changed()
+        precision = {DTYPE_F32: "fp32", DTYPE_BF16: "bf16", DTYPE_F16: "fp16"}[self.dt]
+        if batch is None:
+            batch = max(1, (self.batch_size or 32 * self.world) // self.world)
+        dist_on = self.world > 1 and dist.is_available() and dist.is_initialized()
+        res = evaluation.evaluate(vnet, self.pipeline, data, batch=batch, bins=bins, seed=seed, precision=precision,
+                                  shard=(self.rank, self.world) if dist_on else (0, 1), max_items=max_items, t=t, eps=eps, window=window)
+        return res.all_reduce(self.pg) if dist_on else res
+
     # ------------------------------------------------------------------ EMA access / state
     def ema_state_dicts(self):
         """[(rate, state_dict)] with the reference's key names (snapshot export, training_loop.py:250-265)."""

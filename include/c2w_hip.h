@@ -318,6 +318,29 @@ int c2w_sq_err_det(const void* y, const float* eps, float* out, float* loss_sum,
                    unsigned long long scratch_bytes, int dtype, void* stream);
 int c2w_sq_err_noise_det(const void* y, unsigned long long seed, float* out, float* loss_sum, int B, int C, int HW, int ldc, float* scratch,
                          unsigned long long scratch_bytes, int dtype, void* stream);
+/* Held-out validation: the same squared error resolved by noise-level bin x output channel, never written as a (B,C,H,W) tensor.
+ *   table[bin(t_b)][c] (double [K][C])  += sum over the pixels of image b of (y[b][px][c] - eps[b][c][px])^2,  c < C only (the padding
+ *                                          channels C .. ldc-1 of the rows are never read into a sum)
+ *   count[bin(t_b)]    (int64 [K])      += 1 per image
+ *   per_image[b]       (fp32 [B], may be NULL) = the image's sum over its C channels
+ * table and count ACCUMULATE across calls (zero them once; the host need not synchronise between batches).  eps is read from memory
+ * (fp32 NCHW, any shape and alignment) or regenerated from the Philox stream of `seed` addressed by the dense NCHW index, bit-identical
+ * to c2w_philox_normal -- on a 16-byte aligned tensor of that stream both forms give the same bits.
+ * THE BIN RULE is part of the interface:  bin = min(K - 1, (int)floorf(t_b * (float)K))  with t_b clamped to [0, 1] and ONE fp32
+ * multiply.  An fp64 evaluation of the same formula gives another bin at ordinary values (K = 10: t = 0.7f -> 7 here, 6 in double;
+ * 0.9f -> 9 here, 8 in double); host code that predicts a bin must use fp32 arithmetic.
+ * Two launches, no atomics: each image is cut into slabs of whole 64-pixel tiles, their number a function of (B, HW) only (about 2048
+ * workgroups in all, never a slab across two images); a workgroup stores its slab's per-channel sums into `scratch` (plain fp32 stores,
+ * every slot read is written by the same call), then ONE workgroup walks the images in ascending order, adds an image's slabs in
+ * ascending order (fp32) and adds that sum onto the table in double.  Same operands => same bits, whatever else runs.
+ * scratch must hold c2w_sq_err_levels_scratch_bytes(B, C, HW) bytes; NULL or fewer is C2W_ERR_BAD_ARG, never a fall-back to atomics.
+ * C2W_ERR_UNSUPPORTED (seed form only): HW % 4 != 0 or rows too wide for the LDS tile -- materialise the stream with
+ * c2w_philox_normal and call the tensor form, which takes every shape. */
+long long c2w_sq_err_levels_scratch_bytes(int B, int C, int HW);
+int c2w_sq_err_levels(const void* y, const float* eps, const float* t, double* table, long long* count, float* per_image, int B, int C, int HW,
+                      int ldc, int K, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream);
+int c2w_sq_err_levels_noise(const void* y, unsigned long long seed, const float* t, double* table, long long* count, float* per_image, int B,
+                            int C, int HW, int ldc, int K, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
