@@ -144,23 +144,8 @@ def exported_symbols():
     return list(_PROTOS) + ["c2w_target", "c2w_sources_sha256", "c2w_knobs_reload"]
 
 
-# Knob defaults of the HOST side where they differ from the library's own (csrc/knobs.h).  C2W_CONV_S2_PATCH: the stride-2 forward kernel on
-# the parity planes of the halo patch is correct -- bit-reproducible launch by launch, parity-green, and within ONE bf16 rounding step of the
-# gather kernel on every one of 3600 launches checked INSIDE training steps -- but its last-bit differences put the toy training of
-# tests/test_gpu_host.py::test_bf16_and_fp16_training_track_fp32_training (lr 2e-3, a hard batch at step 28) on the wrong side of a knife edge
-# in ~4 % of runs (0 of 270 with the gather kernel's rounding): that gate test would flake.  Worth 0.04 ms of the step, so the host keeps it
-# OFF unless the environment says otherwise (profiles/r06_experiments.md section 10d).
-HOST_KNOB_DEFAULTS = {"C2W_CONV_S2_PATCH": "0"}
-
-
-def apply_host_knob_defaults() -> None:
-    for k, v in HOST_KNOB_DEFAULTS.items():
-        os.environ.setdefault(k, v)  # the library reads its knobs with getenv at its first launch and at c2w_knobs_reload()
-
-
 def load() -> ctypes.CDLL:
     global _lib
-    apply_host_knob_defaults()
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):

@@ -351,30 +351,15 @@ int launch_dtype(const C2wConvArgs& a, int naive, hipStream_t st) {
 // ---- run-time knobs (knobs.h): read once, re-read on request
 namespace {
 C2wKnobs read_knobs() {
-    auto off0 = [](const char* n) { const char* v = getenv(n); return v != nullptr && atoi(v) == 0; };  // "NAME=0" switches a default-on path off
     C2wKnobs k;
     k.force_gather = getenv("C2W_FORCE_GATHER") != nullptr;
     k.conv_t3 = getenv("C2W_CONV_T3") ? atoi(getenv("C2W_CONV_T3")) : -1;
-    k.conv_pair = !off0("C2W_CONV_PAIR");
-    k.conv_ts2_patch = !off0("C2W_CONV_TS2_PATCH");
-    k.conv_s2_patch = getenv("C2W_CONV_S2_PATCH") ? atoi(getenv("C2W_CONV_S2_PATCH")) : 1;
-    k.ts2_one_launch = getenv("C2W_TS2_FOUR_LAUNCHES") == nullptr;
-    k.ts2_pairs = !off0("C2W_TS2_PAIRS");
-    k.up_patch = getenv("C2W_NO_UP_PATCH") == nullptr;
-    k.wgrad_narrow = getenv("C2W_NO_NARROW") == nullptr;
-    k.wpacked = getenv("C2W_NO_WPACKED") == nullptr;
-    k.wgrad_wgs = getenv("C2W_WGRAD_WGS") && atoi(getenv("C2W_WGRAD_WGS")) > 0 ? atoi(getenv("C2W_WGRAD_WGS")) : 256;
-    k.pool2 = getenv("C2W_NO_POOL2") == nullptr;
-    k.ln_fusion = getenv("C2W_NO_LN_FUSION") == nullptr;
-    k.lnf = getenv("C2W_NO_LNF") == nullptr;
+    k.conv_s2_patch = getenv("C2W_CONV_S2_PATCH") ? atoi(getenv("C2W_CONV_S2_PATCH")) : 0;
+    k.ts2_pairs = !(getenv("C2W_TS2_PAIRS") && atoi(getenv("C2W_TS2_PAIRS")) == 0);
     k.wgrad_atomics = getenv("C2W_WGRAD_ATOMICS") != nullptr;
     k.loss_fusion = getenv("C2W_NO_LOSS_FUSION") == nullptr;
-    k.ln_chain = getenv("C2W_NO_LN_CHAIN") == nullptr;
-    k.splitk = getenv("C2W_NO_SPLITK") == nullptr;
     k.half8 = getenv("C2W_NO_HALF8") == nullptr;
     k.half8_db = !(getenv("C2W_HALF8_DB") && atoi(getenv("C2W_HALF8_DB")) == 0);
-    k.half8_max_wgs = getenv("C2W_HALF8_MAX_WGS") && atoi(getenv("C2W_HALF8_MAX_WGS")) > 0 ? atoi(getenv("C2W_HALF8_MAX_WGS")) : 0;
-    k.conv_t3_min_wgs = getenv("C2W_CONV_T3_MIN_WGS") && atoi(getenv("C2W_CONV_T3_MIN_WGS")) > 0 ? atoi(getenv("C2W_CONV_T3_MIN_WGS")) : 512;
     k.attn_valu = getenv("C2W_ATTN_VALU") != nullptr;
     return k;
 }
@@ -393,19 +378,19 @@ extern "C" int c2w_conv_pool2_supported(const C2wConvArgs* a, int dtype) {
     if (a == nullptr || a->mode != C2W_CONV_S1 || a->res != nullptr || a->mul != nullptr || a->y2 != nullptr || a->act != C2W_ACT_NONE ||
         a->ln_x != nullptr || a->lnf_y != nullptr)
         return 0;
-    return c2w_conv_patch_eligible(*a) && !c2w_conv_pair_eligible(*a) && !c2w_knobs().force_gather && c2w_knobs().pool2 ? 1 : 0;
+    return c2w_conv_patch_eligible(*a) && !c2w_conv_pair_eligible(*a) && !c2w_knobs().force_gather ? 1 : 0;
 }
 
 extern "C" int c2w_conv_lnfwd_supported(const C2wConvArgs* a, int dtype) {
     if (a == nullptr || (dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16)) return 0;
     if (a->Cout != 128 || a->ldy != 128 || a->mul != nullptr || a->y2 != nullptr || a->act != C2W_ACT_NONE || a->ln_x != nullptr) return 0;
-    return c2w_conv_patch_eligible(*a) && !c2w_knobs().force_gather && c2w_knobs().ln_fusion && c2w_knobs().lnf ? 1 : 0;
+    return c2w_conv_patch_eligible(*a) && !c2w_knobs().force_gather ? 1 : 0;
 }
 
 extern "C" int c2w_conv_lnbwd_supported(const C2wConvArgs* a, int dtype) {
     if (a == nullptr || (dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16)) return 0;
     if (a->Cout != 128 || a->ldy != 128 || a->mul != nullptr || a->y2 != nullptr || a->act != C2W_ACT_NONE) return 0;
-    return c2w_conv_patch_eligible(*a) && !c2w_knobs().force_gather && c2w_knobs().ln_fusion ? 1 : 0;
+    return c2w_conv_patch_eligible(*a) && !c2w_knobs().force_gather ? 1 : 0;
 }
 
 int c2w_conv_splitk_plan_impl(const C2wConvArgs& a, int dtype, unsigned long long* ws_bytes);  // conv_patch.hip
@@ -416,7 +401,7 @@ extern "C" int c2w_conv_splitk_plan(const C2wConvArgs* a, int dtype, unsigned lo
 
 extern "C" int c2w_conv_lnfwd_chain_supported(const C2wConvArgs* a, int dtype) {
     if (!c2w_conv_lnfwd_supported(a, dtype)) return 0;
-    return c2w_knobs().ln_chain && a->mode == C2W_CONV_S1 && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
+    return a->mode == C2W_CONV_S1 && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
 }
 
 extern "C" int c2w_conv_loss_supported(const C2wConvArgs* a, int dtype) {
@@ -428,7 +413,7 @@ extern "C" int c2w_conv_loss_supported(const C2wConvArgs* a, int dtype) {
                                    a->loss_lde > 128))
         return 0;
     const C2wKnobs& k = c2w_knobs();
-    return !k.force_gather && k.loss_fusion && k.wgrad_narrow && c2w_conv_patch_eligible(*a) && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
+    return !k.force_gather && k.loss_fusion && c2w_conv_patch_eligible(*a) && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
 }
 
 // Deterministic mode: the scratch behind the fused reductions of c2w_conv_forward.  LayerNorm backward: a row of 128 floats per
@@ -452,7 +437,7 @@ extern "C" long long c2w_conv_det_scratch_bytes(const C2wConvArgs* a, int dtype)
 
 extern "C" int c2w_conv_wpacked_supported(const C2wConvArgs* a, int dtype) {
     if (a == nullptr || (dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16)) return 0;
-    return !c2w_knobs().force_gather && c2w_knobs().wpacked && c2w_conv_patch_eligible(*a) && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
+    return !c2w_knobs().force_gather && c2w_conv_patch_eligible(*a) && c2w_conv_patch3_wanted(*a, dtype) ? 1 : 0;
 }
 
 extern "C" int c2w_conv_dispatch(const C2wConvArgs* a, int dtype) {

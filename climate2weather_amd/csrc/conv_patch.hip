@@ -1,6 +1,6 @@
 // Halo-patch implicit GEMM for the 3x3 stride-1 convolutions (the 60 res-block convs and their input gradients:
 // 98.8 of the 116 GFLOP forward, model/nn.py:155,157) on gfx950 -- the 8x16-pixel-tile kernels: fp32 mode, 16-bit launches below
-// 512 workgroups of the 16x16-tile kernel (conv_patch3.hip; C2W_CONV_T3_MIN_WGS), 8-pixel-wide images (two per tile), the stride-2 input
+// 512 workgroups of the 16x16-tile kernel (conv_patch3.hip), 8-pixel-wide images (two per tile), the stride-2 input
 // gradient per output-parity class (conv_patch_ts2_*) and the stride-2 forward on the parity planes of its patch (conv_patch_s2_kernel).
 // Four-wave form conv_patch_half_kernel (rounds 1-5; fp32 above 256 workgroups), eight-wave form conv_patch_half8_kernel (round 6).
 //
@@ -1097,19 +1097,6 @@ __global__ __launch_bounds__(H_NTHR, 2) void conv_patch_ts2_pairs_kernel(const C
     else conv_patch_ts2_pair<T, 1, PIPE>(p, smem, L);
 }
 
-// One kernel per class (four launches): with the four bodies in one kernel the register allocation of the 4-tap class governs
-// all of them and the merged code spilled 144 VGPRs.
-template <typename T, int CLS>
-__global__ __launch_bounds__(H_NTHR, 2) void conv_patch_ts2_kernel(const C2wConvArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int L;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7, q = nblk >> 3, r = nblk & 7;
-        L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    conv_patch_ts2_class<T, CLS>(p, smem, L);
-}
-
 // All four classes in ONE launch (round 4): a workgroup still computes one class of one tile -- the class is picked per workgroup, so the
 // register allocation is the maximum over the four bodies, not their sum -- and the four classes of a tile sit next to each other
 // on the same XCD (blockIdx = 8 * (4 * tile-in-XCD + class slot) + XCD), so that they find the tile's dy patch and their common
@@ -1144,19 +1131,6 @@ int launch_ts2_all(const C2wConvArgs& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-template <typename T, int CLS>
-int launch_ts2_class(const C2wConvArgs& a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_ts2_kernel<T, CLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        attr = true;
-    }
-    const int nN = (a.Cout + 127) / 128;
-    const int nM = a.B * (a.Hin >> 3) * (a.Win >> 4);
-    conv_patch_ts2_kernel<T, CLS><<<nM * nN, H_NTHR, H_LDS, st>>>(a);
-    return (int)hipGetLastError();
-}
-
 template <typename T>
 int launch_ts2_pairs(const C2wConvArgs& a, hipStream_t st) {
     static bool attr = false;
@@ -1172,16 +1146,11 @@ int launch_ts2_pairs(const C2wConvArgs& a, hipStream_t st) {
 }
 
 template <typename T>
-int launch_ts2(const C2wConvArgs& a, hipStream_t st) {  // largest class first
+int launch_ts2(const C2wConvArgs& a, hipStream_t st) {
     if constexpr (sizeof(T) == 2) {  // bf16: 249 registers with the deferred K half; fp16: without it (PIPE); two fp32 accumulator sets are out of the question
-        if (c2w_knobs().ts2_pairs && c2w_knobs().ts2_one_launch) return launch_ts2_pairs<T>(a, st);
+        if (c2w_knobs().ts2_pairs) return launch_ts2_pairs<T>(a, st);
     }
-    if (c2w_knobs().ts2_one_launch) return launch_ts2_all<T>(a, st);
-    int rc = launch_ts2_class<T, 3>(a, st);
-    if (rc == 0) rc = launch_ts2_class<T, 1>(a, st);
-    if (rc == 0) rc = launch_ts2_class<T, 2>(a, st);
-    if (rc == 0) rc = launch_ts2_class<T, 0>(a, st);
-    return rc;
+    return launch_ts2_all<T>(a, st);
 }
 
 // Second launch of a split-K convolution: adds the `splitk` partial tiles in a fixed order and applies the epilogue of EpiStore::finish --
@@ -1261,11 +1230,10 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const C2wConv
 // that the two forms are within 0.1 ms per step of each other (profiles/r06t_ab_half8_max_wgs_*.txt: B = 128 46.40-46.46 ms with every launch
 // on eight waves against 46.47-46.58 with the 256-workgroup limit; B = 64 and the sampler: equal) -- the 16-bit builds fit two
 // workgroups per CU (114-125 registers), so they take it everywhere; the fp32 builds (131-132 registers: one workgroup per CU) only
-// where there is one per CU anyway.  C2W_HALF8_MAX_WGS=N overrides.
+// where there is one per CU anyway.
 template <typename T>
 static inline bool half8_wanted(long long wgs) {
-    const int lim = c2w_knobs().half8_max_wgs;
-    return c2w_knobs().half8 && (lim > 0 ? wgs <= lim : (sizeof(T) == 2 || wgs <= 256));
+    return c2w_knobs().half8 && (sizeof(T) == 2 || wgs <= 256);
 }
 
 template <typename T, bool PAIR, bool SPLITK, bool DB>
@@ -1349,7 +1317,7 @@ int launch_pair(const C2wConvArgs& a, hipStream_t st) {
 // output tile's K chunks are dealt to (1: no split) and the scratch the partial tiles need.
 int c2w_conv_splitk_plan_impl(const C2wConvArgs& a, int dtype, unsigned long long* ws_bytes) {
     if (ws_bytes != nullptr) *ws_bytes = 0;
-    if (!c2w_knobs().splitk || c2w_knobs().force_gather) return 1;
+    if (c2w_knobs().force_gather) return 1;
     if (a.y2 != nullptr || a.ln_x != nullptr || a.lnf_y != nullptr || a.loss_sum != nullptr || (a.flags & (C2W_CONV_POOL2 | C2W_CONV_NO_Y | C2W_CONV_WPACKED)) != 0) return 1;
     if (a.act != C2W_ACT_NONE && a.act != C2W_ACT_SILU && a.act != C2W_ACT_RELU) return 1;
     const bool pair = c2w_conv_pair_eligible(a);
@@ -1374,7 +1342,7 @@ int c2w_conv_splitk_plan_impl(const C2wConvArgs& a, int dtype, unsigned long lon
 // workgroup is only 18 stages long -- measured per launch against the gather kernel (profiles/r06x_ab_s2_forward.txt): 256 -> 384 @32^2 -> 16^2
 // 88 -> 64 us at B = 128 and 34 -> 22 us at B = 37; 128 -> 256 @64^2 -> 32^2 113 -> 112 / 50 -> 40 us; 128 -> 128 @128^2 -> 64^2 244 -> 251 us at
 // B = 128 (4096 workgroups: slower) but 79 -> 73 us at B = 37 (1184).  So: from four K chunks on, or up to 2048 workgroups
-// (C2W_CONV_S2_PATCH=0: never; =2: wherever the geometry allows).
+// with C2W_CONV_S2_PATCH=1; =2: wherever the geometry allows; unset or 0 (the default): never, the gather kernel.
 bool c2w_conv_s2_patch_eligible(const C2wConvArgs& a, int dtype) {
     const int knob = c2w_knobs().conv_s2_patch;
     const bool pair = a.Wout == 8;  // 8-pixel-wide output: two images per tile
@@ -1407,9 +1375,9 @@ int c2w_conv_patch_s2(const C2wConvArgs& a, int dtype, hipStream_t st) {
     return C2W_ERR_BAD_ARG;
 }
 
-// input gradient of the stride-2 convs per output-parity class on the halo patch (conv_patch_ts2_kernel)
+// input gradient of the stride-2 convs per output-parity class on the halo patch (conv_patch_ts2_pairs_kernel / conv_patch_ts2_all_kernel)
 bool c2w_conv_ts2_patch_eligible(const C2wConvArgs& a) {
-    return c2w_knobs().conv_ts2_patch && a.mode == C2W_CONV_TS2 && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && (a.Hin & 7) == 0 && (a.Win & 15) == 0 &&
+    return a.mode == C2W_CONV_TS2 && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && (a.Hin & 7) == 0 && (a.Win & 15) == 0 &&
            a.ln_x == nullptr && a.lnf_y == nullptr && a.y2 == nullptr && a.act == C2W_ACT_NONE &&
            (long long)a.B * (a.Hin >> 3) * (a.Win >> 4) * ((a.Cout + 127) / 128) * 4 < (1ll << 31);
 }
@@ -1423,7 +1391,7 @@ int c2w_conv_patch_ts2(const C2wConvArgs& a, int dtype, hipStream_t st) {
 
 // 8-pixel-wide images: two of them per 8x16 tile (conv_patch_half_kernel<T, PAIR>); no fused LayerNorm epilogues in that mode
 bool c2w_conv_pair_eligible(const C2wConvArgs& a) {
-    return c2w_knobs().conv_pair && a.mode == C2W_CONV_S1 && a.Hin == a.Hout && a.Win == a.Wout && a.Win == 8 && (a.Hin & 7) == 0 && a.ln_x == nullptr &&
+    return a.mode == C2W_CONV_S1 && a.Hin == a.Hout && a.Win == a.Wout && a.Win == 8 && (a.Hin & 7) == 0 && a.ln_x == nullptr &&
            a.lnf_y == nullptr && (long long)((a.B + 1) >> 1) * (a.Hin >> 3) * ((a.Cout + 127) / 128) < (1ll << 31);
 }
 
@@ -1436,7 +1404,7 @@ int c2w_conv_patch_pair(const C2wConvArgs& a, int dtype, hipStream_t st) {
 
 bool c2w_conv_patch_eligible(const C2wConvArgs& a) {  // OUTPUT grids that 8 x 16-pixel tiles cover exactly; stride 1, or x2 upsampling folded in
     const bool geom = (a.mode == C2W_CONV_S1 && a.Hin == a.Hout && a.Win == a.Wout) ||
-                      (a.mode == C2W_CONV_UP && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && c2w_knobs().up_patch);
+                      (a.mode == C2W_CONV_UP && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win);
     return geom && (a.Hout & 7) == 0 && (a.Wout & 15) == 0 &&
            (long long)a.B * (a.Hout >> 3) * (a.Wout >> 4) * ((a.Cout + 127) / 128) < (1ll << 31);
 }

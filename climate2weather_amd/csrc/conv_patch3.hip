@@ -442,7 +442,7 @@ int t3_launch(const C2wConvArgs& a, hipStream_t st) {
         if (a.lnf_y != nullptr) return a.res_rstd != nullptr ? t3_launch_as<16, T, NW, 8>(a, st) : t3_launch_as<16, T, NW, 2>(a, st);  // 8: the residual rebuilt from normalised rows
         if (a.ln_x != nullptr) return a.ln_rstd != nullptr ? t3_launch_as<16, T, NW, 6>(a, st) : t3_launch_as<16, T, NW, 3>(a, st);
         if (a.loss_sum != nullptr) return t3_launch_as<16, T, NW, 7>(a, st);  // (c2w_conv_loss_supported: the narrow form's conditions)
-        if (a.wrows <= 80 && a.Cout <= 128 && c2w_knobs().wgrad_narrow) return t3_launch_as<16, T, NW, 5>(a, st);  // the output conv: 65 weight rows
+        if (a.wrows <= 80 && a.Cout <= 128) return t3_launch_as<16, T, NW, 5>(a, st);  // the output conv: 65 weight rows
         return t3_launch_as<16, T, NW, 4>(a, st);
     }
     if ((a.flags & C2W_CONV_DETERMINISTIC) != 0 && a.ln_x != nullptr) return C2W_ERR_UNSUPPORTED;  // the all-in-one kernel carries no fixed-order reduction
@@ -456,12 +456,13 @@ int t3_launch(const C2wConvArgs& a, hipStream_t st) {
 // Knob C2W_CONV_T3 = 0 disables it, = 16 forces it wherever the image is tiled by 16x16 (knobs.h).
 // Round 6: from 512 workgroups (one full round of two per CU) instead of 1024 -- what the 32^2 level has at the 8-GPU strong-scaling
 // batch of 64 windows per GPU (step 26.16 -> 26.00 ms) and the 64^2 level of a one-member sampler step at L = 49 (37 windows: 6.36 k ->
-// 6.64 k window-forwards/s); 256 is behind again (26.97 against 26.90 ms at B = 64).  C2W_CONV_T3_MIN_WGS overrides.
+// 6.64 k window-forwards/s); 256 is behind again (26.97 against 26.90 ms at B = 64).
+constexpr long long T3_MIN_WGS = 512;
 bool c2w_conv_patch3_wanted(const C2wConvArgs& a, int dtype) {
     const int mode = c2w_knobs().conv_t3;
     if ((dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16) || mode == 0 || (a.Hout & 15) != 0 || (a.Wout & 15) != 0) return false;
     const long long wgs = (long long)a.B * (a.Hout >> 4) * (a.Wout >> 4) * ((a.Cout + 127) / 128);
-    return mode == 16 || wgs >= c2w_knobs().conv_t3_min_wgs;
+    return mode == 16 || wgs >= T3_MIN_WGS;
 }
 
 int c2w_conv_patch3(const C2wConvArgs& a, int dtype, hipStream_t st) {

@@ -557,12 +557,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const WpGroupAr
 // split of the K (pixel-tile) range over workgroups: one resident workgroup per CU and ONE round: tilesMN * nsplit <= 256 (rounding
 // up gave 270 workgroups for 384 -> 384 -- a second round for 14 of them: 155 us instead of one round's ~90 at 16x16); every workgroup
 // costs 295 KB of partial sums
+constexpr int WGRAD_WGS = 256;  // one per CU
 template <int ESZ, bool PAIR>
 static void split_plan(const C2wConvArgs& a, int& ktiles, int& tilesMN, int& nsplit, int& ktiles_per_split) {
     constexpr int COT = 256 / ESZ, CIB = 128 / ESZ;
     ktiles = PAIR ? ((a.B + 1) >> 1) * (a.Hout >> 3) : a.B * (a.Hout >> 3) * (a.Wout >> 4);
     tilesMN = ((a.Cout + COT - 1) / COT) * (a.Cin / CIB);
-    nsplit = c2w_knobs().wgrad_wgs / tilesMN;
+    nsplit = WGRAD_WGS / tilesMN;
     if (nsplit > ktiles) nsplit = ktiles;
     if (nsplit < 1) nsplit = 1;
     ktiles_per_split = (ktiles + nsplit - 1) / nsplit;
@@ -697,7 +698,7 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
 
 // One grouped launch serves these layers: halo-patch geometry, 2 ... WP_MAX_ITEMS of them, not the narrow-M form of the output conv
 bool c2w_wgrad_patch_group_eligible(const C2wConvArgs& a, int n, int dtype) {
-    const bool narrow = dtype != C2W_DTYPE_F32 && !c2w_wgrad_patch_pair(a) && a.Cout <= 80 && c2w_knobs().wgrad_narrow;  // c2w_wgrad_patch's rule
+    const bool narrow = dtype != C2W_DTYPE_F32 && !c2w_wgrad_patch_pair(a) && a.Cout <= 80;  // c2w_wgrad_patch's rule
     return c2w_wgrad_patch_eligible(a) && n >= 2 && n <= WP_MAX_ITEMS && !narrow && !c2w_knobs().wgrad_atomics;
 }
 
@@ -721,12 +722,12 @@ size_t c2w_wgrad_patch_group_ws_bytes(const C2wConvArgs& a, int n, int dtype) {
 }
 
 bool c2w_wgrad_patch_pair(const C2wConvArgs& a) {  // 8-pixel-wide images: two per K tile
-    return c2w_knobs().conv_pair && a.mode == C2W_CONV_S1 && a.Win == 8 && a.Hin == 8;
+    return a.mode == C2W_CONV_S1 && a.Win == 8 && a.Hin == 8;
 }
 
 bool c2w_wgrad_patch_eligible(const C2wConvArgs& a) {
     if (a.mode == C2W_CONV_UP)  // nearest-neighbour x2 upsampling folded into the patch load
-        return a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && (a.Hout & 7) == 0 && (a.Wout & 15) == 0 && c2w_knobs().up_patch;
+        return a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && (a.Hout & 7) == 0 && (a.Wout & 15) == 0;
     return a.mode == C2W_CONV_S1 && a.Hin == a.Hout && a.Win == a.Wout && (a.Hin & 7) == 0 && ((a.Win & 15) == 0 || c2w_wgrad_patch_pair(a));
 }
 
@@ -738,7 +739,7 @@ int c2w_wgrad_patch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_
         return C2W_ERR_BAD_ARG;
     }
     if (dtype == C2W_DTYPE_F32) return launch<float, false>(a, dw, db, ws, ws_bytes, st);
-    const bool narrow = a.Cout <= 80 && c2w_knobs().wgrad_narrow;  // the output conv (65 channels)
+    const bool narrow = a.Cout <= 80;  // the output conv (65 channels)
     if (dtype == C2W_DTYPE_BF16) return narrow ? launch<bf16_t, false, true>(a, dw, db, ws, ws_bytes, st) : launch<bf16_t, false>(a, dw, db, ws, ws_bytes, st);
     if (dtype == C2W_DTYPE_F16) return narrow ? launch<f16_t, false, true>(a, dw, db, ws, ws_bytes, st) : launch<f16_t, false>(a, dw, db, ws, ws_bytes, st);
     return C2W_ERR_BAD_ARG;

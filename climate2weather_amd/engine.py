@@ -197,8 +197,8 @@ class Tape:
 
 class Engine:
     LINEAR_DGRAD_SPLIT_MIN_ROWS = 2048  # Linear layers at least this wide take the split-reduction input-gradient route
-    # A/B knobs that are class attributes (the others are set per engine in __init__); tests and experiments set them on the class or an engine
-    use_center_conv = os.environ.get("C2W_NO_CENTER_CONV") != "1"  # A/B knob
+    # switches that are class attributes (the others are set per engine in __init__); tests set them on the class or an engine
+    use_center_conv = True  # the sampler's output conv computes the kept centre-frame rows only (c2w_conv_center) instead of all w * F channels
     # Opt-in (C2W_LN_CHAIN=1 or the attribute): the chain form of a level side -- residual-block outputs that only the next block reads are
     # not written, the next block rebuilds its residual from the LayerNorm rows this one emitted (forward.py: res_block).  Measured at B = 128, bf16
     # (profiles/r06_experiments.md): -0.23 ms per step (five 128-channel launches lose their 537 / 134 MB store), but the rebuilt
@@ -206,9 +206,7 @@ class Engine:
     # dominates the block input that is MORE than rounding x itself: against the CPU oracle the worst gradient tensor moves from
     # 8.7e-3 to 1.7e-2 relative L2 (bf16; fp16 5e-3 -> 8.5e-3 of the output scale).  Parity before 0.5 %: off.
     chain_blocks = os.environ.get("C2W_LN_CHAIN") == "1"
-    use_splitk = os.environ.get("C2W_NO_SPLITK") is None  # A/B knob: under-filled inference convs as one workgroup per tile (rounds 1-5)
-    fuse_loss = os.environ.get("C2W_NO_LOSS_FUSION") is None  # A/B knob: the loss tail as its own pass (rounds 1-5); the library reads the same variable
-    use_gemv = os.environ.get("C2W_NO_GEMV") != "1"  # A/B knob: one-row Linear layers as matrix-vector products
+    fuse_loss = os.environ.get("C2W_NO_LOSS_FUSION") is None  # off: the loss tail as its own pass (rounds 1-5); the library reads the same variable
 
     def __init__(self, net):
         self.layout = Layout(net)
@@ -230,40 +228,20 @@ class Engine:
         self._pk_want: Dict[tuple, dict] = {}   # (kind, dtype) -> {name of a matrix that is kept packed: weight version of its copy}
         self._pk_desc: Dict[tuple, torch.Tensor] = {}  # ((kind, dtype), names) -> descriptor table of one pack launch
         self._pk_sync: Dict[tuple, list] = {}  # (kind, dtype) -> [(event behind a pack launch, ids of the streams ordered behind it)]
-        self.use_packed_weights = os.environ.get("C2W_NO_WPACKED") is None
+        self.use_packed_weights = True
         self._gwpad: Dict[str, torch.Tensor] = {}  # name -> padded fp32 weight-gradient scratch
         self._manual_ver = 0
         self._wg_stream = None  # second HIP stream for the weight-gradient launches (see _wg)
-        # Input-gradient operands rebuilt on the side stream beside the next forward: part of the two-stream mode (C2W_WGRAD_STREAM=1; round
-        # 4: -0.2 ms there).  On one stream -- the default -- a second active queue costs more than the 0.18 ms of passes it hides
-        # (46.74-46.83 against 46.91-47.01 ms per step): off unless C2W_DG_PREFETCH=1; C2W_NO_DG_PREFETCH=1 switches it off in either mode.
-        self.prefetch_dgrad = os.environ.get("C2W_NO_DG_PREFETCH") is None and \
-            (os.environ.get("C2W_WGRAD_STREAM", "0") == "1" or os.environ.get("C2W_DG_PREFETCH") == "1")
-        self._dg_ready = None  # event behind input-gradient operands that were rebuilt on the gradient stream (prefetch_backward_operands)
-        # C2W_WGRAD_STREAM=0 (read once, here; or set the attribute): weight gradients on the caller's stream, every kernel alone on the
-        # chip -- what bench.py's by_kernel pass and the serialised rocprof runs use
-        # Round 5: OFF by default.  With the weight gradients of a level grouped into one launch (below) every kernel fills the chip on its
-        # own, and two queues whose kernels cannot share a CU only cost each other (B = 128: 46.2 against 46.7 ms; B = 16 ... 64, 52
-        # channels, fp16 and the 256x256 variant: 0.1-0.45 ms per step, profiles/r05_experiments.md section 8).  Rounds 1-4 (per-layer
-        # launches) gained 2.4 ms from the second queue.  C2W_WGRAD_STREAM=1 restores it.
+        # C2W_WGRAD_STREAM=1 (read once, here; or set the attribute): the two-stream mode -- weight gradients on a second stream.  Off by
+        # default: every kernel alone on the chip, on the caller's stream (profiles/r05_experiments.md section 8).
         self.use_grad_stream = os.environ.get("C2W_WGRAD_STREAM", "0") == "1"
-        # A/B knob: gradient-stream launches are enqueued N calls late (1: behind the layer's own input gradient; 2: a
-        # residual block's two weight gradients during the next block; ...)
-        self._wgrad_behind = max(0, int(os.environ.get("C2W_WGRAD_BEHIND", "0") or 0))
-        self._wg_pending = []
-        # Weight gradients of the residual-block convs are collected per geometry during the backward and launched together at the
-        # level boundaries (ops.conv_wgrad_grouped: the 6 or 12 layers of a level side share one shape).  C2W_WGRAD_GROUP=0: one
-        # launch per layer (rounds 1-4); =N: only levels whose grid is at most N pixels high (default 64); =1: every level.
-        # Measured at B = 128 (profiles/r05_experiments.md section 2): 64 is 0.32 ms per step ahead of 0 -- below 128x128 the per-layer
-        # launches were mostly hidden beside the other queue's; grouped, they need a third of the launches and of the partial sums.
-        # At 128x128 a group is neutral when it is launched at the level boundary and costs 0.9 ms when it is enqueued in front of
-        # the side's last input gradient (252 workgroups that hold their CUs for 3 ms).
-        self.keep_ln_stats = os.environ.get("C2W_NO_LN_STATS") != "1"  # A/B knob: fused LayerNorms hand their 1/sigma to the backward
-        _grp = os.environ.get("C2W_WGRAD_GROUP", "64")
-        self.group_wgrads = _grp != "0"
-        self.group_wgrads_max_side = int(_grp) if _grp.isdigit() and int(_grp) > 1 else 1 << 30
-        # above that side: groups of at most this many layers (1 = one launch per layer); C2W_WGRAD_GROUP_TOP (A/B)
-        self.group_wgrads_top = max(1, int(os.environ.get("C2W_WGRAD_GROUP_TOP", "1")))
+        # part of the two-stream mode: input-gradient operands rebuilt on the side stream beside the next forward (prefetch_backward_operands)
+        self.prefetch_dgrad = self.use_grad_stream
+        self._dg_ready = None  # event behind input-gradient operands that were rebuilt on the gradient stream (prefetch_backward_operands)
+        # Weight gradients of the residual-block convs are collected per geometry during the backward and launched together at the level
+        # boundaries (ops.conv_wgrad_grouped), on levels whose grid is at most group_wgrads_max_side pixels high at the reference's batch (_wg)
+        self.group_wgrads = True
+        self.group_wgrads_max_side = 64
         self._wg_groups: Dict[tuple, list] = {}  # (geometry, dtype) -> [(x, dY, record, geometry)] not launched yet
         self._wg_group_ok: Dict[tuple, bool] = {}
         self._done_releases: list = []  # one callback per live backward_steps generator: hands on the "done" offsets it held back while a group was pending
@@ -581,9 +559,7 @@ class Engine:
             return None
         if self._wg_stream is None or self._wg_stream.device != self.flat.device:
             from .streams import independent_stream
-            # on another hardware queue than the caller's stream (streams.py); C2W_GRAD_STREAM_PRIORITY: A/B knob (HIP: -1 high, 0 normal,
-            # 1 low where the runtime offers it)
-            self._wg_stream = independent_stream(self.flat.device, priority=int(os.environ.get("C2W_GRAD_STREAM_PRIORITY", "0")))
+            self._wg_stream = independent_stream(self.flat.device)  # on another hardware queue than the caller's stream (streams.py)
         return self._wg_stream
 
     def publish(self, scalar: torch.Tensor):
@@ -608,15 +584,6 @@ class Engine:
         if side is None:
             fn()
             return
-        if self._wgrad_behind:  # experiment knob: this launch is enqueued N calls later, i.e. behind the input gradients issued in between
-            self._wg_pending.append((fn, tensors))
-            while len(self._wg_pending) > self._wgrad_behind:
-                self._issue_on(side, *self._wg_pending.pop(0))
-            return
-        self._issue_on(side, fn, tensors)
-
-    @staticmethod
-    def _issue_on(side, fn, tensors) -> None:
         side.wait_stream(torch.cuda.current_stream())
         for t in tensors:
             t.record_stream(side)
@@ -628,8 +595,6 @@ class Engine:
         self.flush_wgrad_groups()
         side = self.grad_stream()
         if side is not None:
-            while self._wg_pending:
-                self._issue_on(side, *self._wg_pending.pop(0))
             torch.cuda.current_stream().wait_stream(side)
 
     def workspace(self, min_bytes: int = 0) -> Optional[torch.Tensor]:
@@ -687,7 +652,7 @@ class Engine:
         """(scratch, workgroups per tile) if this inference launch should deal its K chunks to several workgroups (ops.conv_splitk_plan:
         fewer output tiles than the chip has CUs -- the deep levels of a sampler step on a short trajectory), else None.  The plan is
         a pure function of geometry and knobs: remembered per geometry."""
-        if not self.use_splitk or self.flat is None or not self.flat.is_cuda:
+        if self.flat is None or not self.flat.is_cuda:
             return None
         key = self._gkey(g) + (dt, act, ops.KNOBS_GENERATION)
         plan = self._splitk_plans.get(key)
@@ -708,11 +673,10 @@ class Engine:
         # the deep variant's 128x128 level at B = 32 is the default network's 64x64 level at B = 128)
         npx = g["B"] * g["Hout"] * g["Wout"]
         small = npx <= 128 * self.group_wgrads_max_side ** 2
-        cap = 16 if small else self.group_wgrads_top
-        if not small and cap == 1 and npx <= 256 * self.group_wgrads_max_side ** 2:
-            # one size up -- the 128x128 level at 64 windows per GPU, the reference's global batch of 512 on 8 GPUs: groups of three
-            # (round 6, B = 64: 26.00 -> 25.84 ms per step; at B = 128 the same grouping costs 0.25 ms: profiles/r05_experiments.md)
-            cap = 3
+        # one size up -- the 128x128 level at 64 windows per GPU, the reference's global batch of 512 on 8 GPUs: groups of three
+        # (round 6, B = 64: 26.00 -> 25.84 ms per step; at B = 128 the same grouping costs 0.25 ms: profiles/r05_experiments.md);
+        # above that one launch per layer
+        cap = 16 if small else 3 if npx <= 256 * self.group_wgrads_max_side ** 2 else 1
         if group and self.group_wgrads and cap > 1:
             # (_gkey without ``wrows``, on purpose: these fields decide which layers share a grouped launch)
             key = (g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"], g["mode"], dt, ops.KNOBS_GENERATION)
@@ -786,7 +750,7 @@ class Engine:
         model/nn.py:149)."""
         rec = self.layout.convs[name]
         y = torch.empty((rows, rec.rows), dtype=torch.float32, device=x.device)
-        if rows == 1 and tape is None and self.use_gemv and act in (ACT_NONE, ACT_SILU, ACT_RELU):
+        if rows == 1 and tape is None and act in (ACT_NONE, ACT_SILU, ACT_RELU):
             # one t for the whole batch (the sampler): a matrix-vector product instead of a 16-pixel MFMA tile with one live column
             ops.gemv_f32(x, self._w(rec, DTYPE_F32), self._b(rec), y, rec.rows, rec.cin, rec.kstride, act)
             return y

@@ -110,7 +110,7 @@ class ForwardPass:
         if want_ln is not None and act == ACT_NONE and y2 is None and ops.conv_lnfwd_supported(g, dt):
             rows = torch.empty((npix, ldy_), dtype=T, device=dev)
             lnf = dict(y=rows, m=want_ln[1], ldm=self.ldm if want_ln[1] is not None else 0, eps=LN_EPS, unbiased=eng.ln_unbiased)
-            if train and eng.keep_ln_stats and want_ln[0] == "mod":
+            if train and want_ln[0] == "mod":
                 # training: the epilogue also leaves every pixel row's 1/sigma; the block's backward then takes its LayerNorm
                 # statistics from here and the normalised rows (kept anyway: conv1's input) instead of recomputing both (res_block)
                 lnf["rstd"] = torch.empty((npix,), dtype=torch.float32, device=dev)
@@ -267,7 +267,7 @@ class ForwardPass:
                 # block's conv2, its residual add can rebuild the sum) -- where the kernels exist, it is not written.  The rebuilding
                 # lives in the LayerNorm-emitting epilogue, so the NEXT block's conv2 must emit one too (a side's last block does
                 # only in front of an up-block)
-                elide = self.train and eng.chain_blocks and eng.keep_ln_stats and nb is not None and nb.kind == "res" and \
+                elide = self.train and eng.chain_blocks and nb is not None and nb.kind == "res" and \
                     want_of(j + 1) is not None and self.chain_ok(b.channels, Hc, Wc)
                 cur, hn = self.res_block(b, cur, Hc, Wc, ln0=hn, want_ln=want_of(j), elide=elide)
             else:

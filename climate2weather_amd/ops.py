@@ -107,7 +107,7 @@ KNOBS_GENERATION = 0  # bumped by knobs_reload(): callers that memoise dispatch 
 def knobs_reload() -> None:
     """Re-read the library's run-time knobs (C2W_* dispatch overrides) from the environment: it reads them once, at load."""
     global KNOBS_GENERATION
-    _lib.load().c2w_knobs_reload()  # (load() re-applies the host's knob defaults: a test that deleted a variable gets the HOST default back)
+    _lib.load().c2w_knobs_reload()
     KNOBS_GENERATION += 1
 
 
@@ -252,9 +252,8 @@ def conv_wgrad_grouped(items, g: dict, dtype: int, workspace: Optional[torch.Ten
           "c2w_conv_wgrad_grouped")
 
 
-# covers every layer of the default network at any batch (75.5 MB per launch, independent of the batch size); C2W_WORKSPACE_MB: A/B runs
-# that raise the number of splits (C2W_WGRAD_WGS)
-WORKSPACE_BYTES = int(__import__("os").environ.get("C2W_WORKSPACE_MB", "96")) << 20
+# covers every layer of the default network at any batch (75.5 MB per launch, independent of the batch size)
+WORKSPACE_BYTES = 96 << 20
 
 
 def new_workspace(device, nbytes: int = WORKSPACE_BYTES) -> torch.Tensor:

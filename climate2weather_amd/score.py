@@ -11,7 +11,6 @@ own arithmetic type; the default / bfloat16 -> bf16).  ``net.precision = "fp32" 
 """
 from __future__ import annotations
 
-import os
 
 from typing import Optional
 
@@ -344,7 +343,7 @@ _SCALAR_KEEP = (torch.Tensor.mul, torch.mul, torch.Tensor.__mul__, torch.Tensor.
 
 
 def _as_loss_scalar(t: torch.Tensor, eng, pub=None) -> torch.Tensor:
-    if eng is None or not t.is_cuda or t.dim() != 0 or t.dtype != torch.float32 or os.environ.get("C2W_NO_EARLY_ITEM") == "1":  # the knob: A/B only
+    if eng is None or not t.is_cuda or t.dim() != 0 or t.dtype != torch.float32:
         return t
     if pub is None:  # produced by a launch just enqueued on the current stream: publish behind it
         pub = eng.publish(t.detach())
@@ -481,18 +480,14 @@ class ScoreUNet(torch.nn.Module):
 
     # Parameter gradients delivered in this many segments during the backward pass (_GradSegment) instead of all at its end: None =
     # 8 when torch.distributed runs more than one rank (a DistributedDataParallel wrapper can then all-reduce its buckets under the
-    # pass), else 1; C2W_GRAD_SEGMENTS or the attribute override it.
+    # pass), else 1; the attribute overrides it.
     grad_segments = None
 
     def _segments(self, params, x) -> int:
         n = self.grad_segments
         if n is None:
-            env = os.environ.get("C2W_GRAD_SEGMENTS")
-            if env is not None:
-                n = int(env)
-            else:
-                import torch.distributed as dist
-                n = 8 if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else 1
+            import torch.distributed as dist
+            n = 8 if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else 1
         if n <= 1 or not torch.is_grad_enabled() or not all(p.requires_grad for p in params) or _in_functorch_transform(x):
             return 1
         return int(n)

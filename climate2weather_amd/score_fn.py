@@ -193,9 +193,6 @@ class _WindowScore(AbstractScoreFunction):
             except StopIteration:  # pragma: no cover
                 device = torch.device("cuda")
         self.device = torch.device(device)
-        # window batches of one score evaluation alternate between this many HIP streams (1: the caller's stream only);
-        # C2W_SCORE_STREAMS (read once, here) or the attribute
-        self.num_streams = int(os.environ.get("C2W_SCORE_STREAMS", type(self).num_streams))
         if "C2W_WINDOW_BATCH_FLOOR" in os.environ:
             self.window_batch_floor = int(os.environ["C2W_WINDOW_BATCH_FLOOR"])
 

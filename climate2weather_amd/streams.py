@@ -10,7 +10,6 @@ sampler's window-batch streams, a test suite) may not be so lucky and would lose
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -84,7 +83,7 @@ def independent_stream(device, avoid=(), tries: int = 8, priority: int = 0) -> "
     backward at 56 instead of 47 ms/step although this probe had cleared its gradient stream (profiles/r04_experiments.md section 16)."""
     device = torch.device(device)
     with torch.cuda.device(device):
-        if os.environ.get("C2W_PLAIN_STREAMS") == "1" or torch.cuda.is_current_stream_capturing():
+        if torch.cuda.is_current_stream_capturing():
             return torch.cuda.Stream(device=device, priority=priority)
         others, seen = [], set()
         for st in [torch.cuda.current_stream(device)] + [a for a in avoid if a is not None]:
@@ -104,6 +103,4 @@ def independent_stream(device, avoid=(), tries: int = 8, priority: int = 0) -> "
             warnings.warn(f"climate2weather_amd: none of {max(1, tries)} new HIP streams runs next to the current one (all share its hardware "
                           "queue): launches meant to overlap (weight gradients beside input gradients, window batches) will serialise",
                           RuntimeWarning, stacklevel=2)
-        if os.environ.get("C2W_STREAM_DEBUG") == "1":
-            print("independent_stream: %d rejected, %d to avoid, verdict %s" % (len(rejected), len(others), ok), flush=True)
         return s

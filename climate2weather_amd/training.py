@@ -108,7 +108,6 @@ class Trainer:
             for e in self.ema_flats:
                 e.copy_(eng.flat)
         # all-reduce buckets over the flat gradient buffer, last bucket = first finalised
-        bucket_mb = float(os.environ.get("C2W_BUCKET_MB", bucket_mb))  # env: diagnostic sweep
         per = max(int(bucket_mb * (1 << 20) // 4), 1)
         self.buckets: List[tuple] = []
         end = n
@@ -117,10 +116,10 @@ class Trainer:
             self.buckets.append((start, end))
             end = start
         # Wire format of the gradient all-reduce: None / "fp32" = the flat fp32 gradients themselves (288 MB per step, what DDP moves
-        # for the reference); "bf16" (or C2W_ALLREDUCE_DTYPE=bf16) = each finished bucket is cast to bfloat16, summed over the ranks
+        # for the reference); "bf16" = each finished bucket is cast to bfloat16, summed over the ranks
         # in bfloat16 and cast back: 144 MB on the xGMI links, gradients carry bf16's 8 mantissa bits across the sum (the
         # compression DDP's bf16_compress_hook applies) while weights, moments and the local gradients stay fp32.
-        allreduce_dtype = os.environ.get("C2W_ALLREDUCE_DTYPE", allreduce_dtype) or "fp32"
+        allreduce_dtype = allreduce_dtype or "fp32"
         if allreduce_dtype not in ("fp32", "bf16"):
             raise ValueError(f"allreduce_dtype must be fp32 or bf16, got {allreduce_dtype!r}")
         self.wire = torch.empty(n, dtype=torch.bfloat16, device=dev) if (allreduce_dtype == "bf16" and self.sync_grads) else None
@@ -131,9 +130,7 @@ class Trainer:
         # not before step k - 2 has finished -- further ahead, the blocks the gradient stream still holds (record_stream) are not
         # reusable yet and the caching allocator answers every request with a fresh, synchronising hipMalloc (measured: 210 ms/step).
         self._step_done: List[torch.cuda.Event] = []
-        # Opt-in (C2W_CHASE_OPT=1 or the attribute): measured on one MI355X it buys nothing -- 50.8-50.9 ms per step either way; the step is
-        # bound by the clock the chip holds under the MFMA load, and the update's HBM stream next to it lowers that clock further.
-        self.chase_optimizer = os.environ.get("C2W_CHASE_OPT", "0") == "1"
+        self.chase_optimizer = False  # opt-in (the attribute): the optimizer update chases the backward bucket by bucket; buys nothing on one MI355X
 
     # ------------------------------------------------------------------ all-reduce and optimizer, both chasing the backward
     # The flat gradient buffer is laid out in reverse finalisation order, so what backward has finished is a growing SUFFIX.  Per
@@ -158,18 +155,16 @@ class Trainer:
         gs = self.eng.grad_stream()
         if gs is not None:
             return gs
-        if os.environ.get("C2W_COMM_ON_COMPUTE") == "1":  # A/B knob: round 5's behaviour (everything issued from the compute stream)
-            return None
         # fp32 wire without the chased update: the collectives are asynchronous (RCCL runs them on its own stream behind an event of
         # the issuing stream) and nothing waits for them before _finish_allreduce -- issued from the compute stream itself they cost
         # no stream hop (one rank, same box: 46.70 against 46.81 ms per step through the communication stream).  Anything with a
         # stream-side wait inside the backward (bf16 wire: cast -> sum -> WAIT -> cast back; chased update: WAIT -> AdamW) goes to the
-        # communication stream.  C2W_COMM_STREAM=1 sends the fp32 wire there as well.
+        # communication stream.
         return self.eng.side_stream() if self._wants_comm_stream() else None
 
     def _wants_comm_stream(self) -> bool:
         """Does the per-bucket sequence of this step contain a stream-side wait (see _comm_stream)?"""
-        return self.sync_grads and (self.wire is not None or self._chase is not None or os.environ.get("C2W_COMM_STREAM") == "1")
+        return self.sync_grads and (self.wire is not None or self._chase is not None)
 
     def _on_progress(self, off: int) -> None:
         if not (self._next_bucket < len(self.buckets) and self.buckets[self._next_bucket][0] >= off):
@@ -192,7 +187,7 @@ class Trainer:
                     if _EMULATED_COLLECTIVE_CYCLES and wb.is_cuda:
                         # measurement knob (one-rank runs: RCCL's all-reduce over a single rank launches no kernel at all): the stream that
                         # waits for the collective is held for the time a 25-MB bucket takes over xGMI -- on the communication stream
-                        # that time must not show in the step, on the compute stream (C2W_COMM_ON_COMPUTE=1) all of it does
+                        # that time must not show in the step
                         torch.cuda._sleep(_EMULATED_COLLECTIVE_CYCLES)
                     self.eng.flat_grad[s:e].copy_(wb)
                     work = None
@@ -227,22 +222,7 @@ class Trainer:
 
     # ------------------------------------------------------------------ one optimizer step
     def step(self, batches, t: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One optimizer step (``_step``).  C2W_MAIN_PRIORITY=-1 (A/B knob, read per call): the whole step runs on a high-priority HIP
-        stream of the trainer's own, so that the forward / input-gradient chain wins CUs over the weight-gradient stream."""
-        if os.environ.get("C2W_MAIN_PRIORITY") == "-1" and self.eng.flat.is_cuda:
-            hp = self.__dict__.get("_hp_stream")
-            if hp is None:
-                hp = self.__dict__["_hp_stream"] = torch.cuda.Stream(device=self.eng.flat.device, priority=-1)
-            cur = torch.cuda.current_stream()
-            hp.wait_stream(cur)
-            with torch.cuda.stream(hp):
-                loss = self._step(batches, t, eps)
-            cur.wait_stream(hp)
-            return loss
-        return self._step(batches, t, eps)
-
-    def _step(self, batches, t: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``batches``: one (B,C,H,W) fp32 GPU tensor (or data.WindowBatch), or a list of them = gradient-accumulation rounds
+        """One optimizer step.  ``batches``: one (B,C,H,W) fp32 GPU tensor (or data.WindowBatch), or a list of them = gradient-accumulation rounds
         (training_loop.py:373-378: gradients of the rounds are summed, only the last round synchronises).
         ``t`` (B,) and ``eps`` (B,C,H,W) may be injected (tests); otherwise drawn as src/thor/pipelines.py:29-31 does.
         Returns the last round's loss (device scalar, like the value the reference logs)."""

@@ -176,9 +176,9 @@ long long c2w_conv_det_scratch_bytes(const C2wConvArgs* args, int dtype);
 /* Which kernel family c2w_conv_forward (naive == 0) / c2w_conv_wgrad run these arguments on -- a pure function of the geometry,
  * the dtype and the fusion fields; the parity tests assert with it that a case reaches the kernel it is meant to cover.
  * GATHER: conv_igemm / wgrad gather kernels; PATCH_8X16: conv_patch_half_kernel / wgrad_patch_kernel; PATCH_16X16:
- * conv_patch_t3_kernel<16> (16-bit launches of >= 512 workgroups of that tile, C2W_CONV_T3_MIN_WGS); PATCH_PAIR: 8-pixel-wide images, two per tile; PATCH_TS2: the
+ * conv_patch_t3_kernel<16> (16-bit launches of >= 512 workgroups of that tile); PATCH_PAIR: 8-pixel-wide images, two per tile; PATCH_TS2: the
  * stride-2 input gradient per output-parity class; PATCH_S2: the stride-2 FORWARD on the parity planes of the halo patch (16-bit; output
- * tiled by 8x16 pixels, or 8 pixels wide with two images per tile; from four K chunks on or up to 2048 workgroups). */
+ * tiled by 8x16 pixels, or 8 pixels wide with two images per tile; only with C2W_CONV_S2_PATCH=1, from four K chunks on or up to 2048 workgroups, or =2, wherever the geometry allows). */
 enum { C2W_KERNEL_GATHER = 0, C2W_KERNEL_PATCH_8X16 = 1, C2W_KERNEL_PATCH_16X16 = 2, C2W_KERNEL_PATCH_PAIR = 3, C2W_KERNEL_PATCH_TS2 = 4, C2W_KERNEL_PATCH_S2 = 5 };
 int c2w_conv_dispatch(const C2wConvArgs* args, int dtype);
 int c2w_conv_wgrad_dispatch(const C2wConvArgs* args, int dtype);
@@ -465,8 +465,8 @@ int c2w_affine_channels(const float* x, float* y, const float* scale, const floa
                         void* stream);
 
 /* library identity: returns the gfx target string the kernels were compiled for ("gfx950") */
-/* Run-time knobs (dispatch overrides for tests and A/B measurements: C2W_FORCE_GATHER, C2W_CONV_T3, C2W_CONV_PAIR, C2W_CONV_TS2_PATCH,
- * C2W_NO_UP_PATCH, C2W_NO_POOL2, C2W_NO_LN_FUSION, C2W_NO_LNF, C2W_WGRAD_ATOMICS, C2W_ATTN_VALU; csrc/knobs.h) are
+/* Run-time knobs (dispatch overrides for tests and opt-in modes: C2W_FORCE_GATHER, C2W_CONV_T3, C2W_CONV_S2_PATCH, C2W_TS2_PAIRS,
+ * C2W_WGRAD_ATOMICS, C2W_ATTN_VALU, C2W_NO_LOSS_FUSION, C2W_NO_HALF8, C2W_HALF8_DB; csrc/knobs.h) are
  * read from the environment once, when the library is loaded; this re-reads them. */
 void c2w_knobs_reload(void);
 

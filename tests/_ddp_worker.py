@@ -58,7 +58,7 @@ def run(rank: int, world: int, port: int, golden_dir: str, out_dir: str, bucket_
 
 
 def run_chase(rank: int, world: int, port: int, golden_dir: str, out_dir: str, backend: str = "gloo"):
-    """Two optimizer steps with the update chasing the backward per finished bucket (Trainer.chase_optimizer / C2W_CHASE_OPT=1: the
+    """Two optimizer steps with the update chasing the backward per finished bucket (Trainer.chase_optimizer: the
     all-reduce AND the fused AdamW + EMA of a bucket are issued while the rest of the backward still runs) and two with the update
     behind the whole backward, from the same initial weights, several buckets: the weights must be the same."""
     dev = _init(rank, world, port, backend)

@@ -197,7 +197,7 @@ def test_conv_kernels_at_the_bench_dispatch(case, dt):
         _run_conv_case(case, dt, ep)
 
 
-# the four down-convs at the bench's batch on the parity-plane halo kernel (C2W_CONV_S2_PATCH=1: opt-in, see _lib.HOST_KNOB_DEFAULTS)
+# the four down-convs at the bench's batch on the parity-plane halo kernel (C2W_CONV_S2_PATCH=1: opt-in, csrc/knobs.h)
 S2_FWD_CASES = [
     ("down 128->128 128^2->64^2", S2P, S2, 16, 128, 128, 128, 128, 128, ["bias"]),
     ("down 128->256 64^2->32^2 (two output-channel tiles)", S2P, S2, 128, 64, 128, 256, 256, 128, ["bias", "bias+silu", "bias+res"]),
@@ -223,14 +223,14 @@ def test_stride2_forward_kernel_at_the_bench_dispatch(case, dt, s2_patch_on):
 
 
 def test_stride2_forward_dispatch_rule(monkeypatch):
-    """Off unless C2W_CONV_S2_PATCH says otherwise (host default); with =1 the parity-plane kernel is taken from four K chunks on or up to 2048 workgroups (one workgroup per CU: short chains in big launches
+    """Off unless C2W_CONV_S2_PATCH says otherwise (the library's default, csrc/knobs.h: unset means 0 for every caller of the C ABI); with =1 the parity-plane kernel is taken from four K chunks on or up to 2048 workgroups (one workgroup per CU: short chains in big launches
     lose to the gather kernel, profiles/r06x_ab_s2_forward.txt); C2W_CONV_S2_PATCH=2 takes it wherever the geometry allows, =0 never."""
     big = geom(128, 128, 128, 128, 64, 64, 128, 128, 128, S2)    # 4096 workgroups, two K chunks
     deep = geom(128, 32, 32, 256, 16, 16, 384, 384, 256, S2)     # four K chunks
     mid = geom(128, 64, 64, 128, 32, 32, 256, 256, 128, S2)      # 2048 workgroups
     narrow = geom(128, 16, 16, 384, 8, 8, 512, 512, 384, S2)     # 8-pixel-wide output: two images per tile, six K chunks
     odd = geom(128, 24, 24, 128, 12, 12, 128, 128, 128, S2)      # 12-pixel-wide output: no tiling covers it
-    assert [ops.conv_dispatch(g, BF16) for g in (big, deep, mid, narrow, odd)] == [GATHER] * 5  # the host's default: off (_lib.HOST_KNOB_DEFAULTS)
+    assert [ops.conv_dispatch(g, BF16) for g in (big, deep, mid, narrow, odd)] == [GATHER] * 5  # the library's default: off
     try:
         monkeypatch.setenv("C2W_CONV_S2_PATCH", "1")
         ops.knobs_reload()

@@ -68,7 +68,7 @@ def test_training_step_over_rccl_two_ranks_equals_single_process(golden_dir, tmp
 
 @pytest.mark.parametrize("world", [1, pytest.param(2, marks=two_gpus)])
 def test_optimizer_chasing_the_backward_over_rccl(golden_dir, tmp_path, world):
-    """Trainer.chase_optimizer (C2W_CHASE_OPT=1) through RCCL: all-reduce + fused AdamW + EMA per finished bucket on the gradient
+    """Trainer.chase_optimizer through RCCL: all-reduce + fused AdamW + EMA per finished bucket on the gradient
     stream while the backward runs, against the update behind the backward: same weights after two steps."""
     import torch.multiprocessing as mp
     from _ddp_worker import run_chase

@@ -193,7 +193,7 @@ def test_ddp_two_ranks_gloo_equals_single_process(golden_dir, tmp_path, bucket_m
 
 
 def test_optimizer_chasing_the_backward_equals_the_update_behind_it_two_ranks_gloo(golden_dir, tmp_path):
-    """C2W_CHASE_OPT / Trainer.chase_optimizer with several buckets on two ranks: all-reduce + fused AdamW + EMA per finished bucket,
+    """Trainer.chase_optimizer with several buckets on two ranks: all-reduce + fused AdamW + EMA per finished bucket,
     issued from inside the backward, against the whole-buffer update behind it -- same weights and EMA after two steps, on both
     ranks; the chasing run really updated bucket by bucket."""
     import torch.multiprocessing as mp

@@ -64,7 +64,6 @@ x = torch.randn(4, 6, 32, 32, device=dev)
 for wire in ("bf16", None):
     tr = Trainer(net, precision="bf16", ema_rates=(), allreduce_dtype=wire, bucket_mb=0.05)
     tr.eng._wg_stream = None
-    os.environ["C2W_COMM_STREAM"] = "1"
     tr.step(x); torch.cuda.synchronize()
     E = tr.eng.side_stream()
     pattern(E, f"b1 engine side stream after ONE trainer step (wire {wire})")

@@ -6,7 +6,7 @@ A kernel with a timing-dependent LDS race shows up here; summation order cannot 
     python tools/stress_kernel_determinism.py [N]"""
 import math, os, sys
 sys.path.insert(0, os.getcwd())
-os.environ.setdefault("C2W_CONV_S2_PATCH", "1")  # the host keeps the stride-2 forward kernel off by default (_lib.HOST_KNOB_DEFAULTS); this tool is about it
+os.environ.setdefault("C2W_CONV_S2_PATCH", "1")  # the stride-2 forward kernel is off by default (csrc/knobs.h); this tool is about it
 import torch
 from climate2weather_amd import ops, _lib
 
