@@ -97,6 +97,8 @@ _PROTOS = {
                           c_int, c_void_p],
     "c2w_sq_err_levels_noise": [c_void_p, c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                 c_ulonglong, c_int, c_void_p],
+    "c2w_rapsd_supported": [c_int, c_int],
+    "c2w_rapsd": [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

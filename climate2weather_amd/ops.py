@@ -423,6 +423,21 @@ def sq_err_levels(y, eps, t, table, count, per_image, B, C, HW, ldc, K, scratch,
     return True
 
 
+def rapsd_supported(H: int, W: int) -> bool:
+    return bool(_lib.load().c2w_rapsd_supported(H, W))
+
+
+def rapsd(x, spec, n_fields, H, W) -> bool:
+    """spec (n_fields, H/2) fp32 = the un-normalised radial spectra of the dense fp32 fields x (n_fields, H, W), 16-byte aligned
+    (include/c2w_hip.h::c2w_rapsd: the definition, the fixed summation order).  False if the shape is not supported -- nothing is
+    written and the caller takes the general definition (spectra.rapsd)."""
+    rc = _lib.load().c2w_rapsd(_p(x), _p(spec), n_fields, H, W, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_rapsd")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

@@ -1,0 +1,210 @@
+"""Ensemble spectra on the device: the radially averaged power spectral density (RAPSD) of every field of a sampled ensemble, the mean
+absolute log ratio of a member's spectrum to the truth's (MELR), and the per-variable report the reference's ``exp/metrics.py`` saves.
+
+The reference loops in Python over every time and member of a netCDF array on the host and calls a radar library's ``rapsd`` on each
+field (exp/metrics.py:50-112); ``run_ensemble`` leaves ``(M, L, F, H, W)`` on the device, and here it stays there: one HIP kernel
+(csrc/spectrum.hip) reads each field once and writes its ``H / 2`` bin means, nothing else touches global memory.
+
+**The definition**, in this project's words (recalled from that library's 1.x ``utils.spectral.rapsd``, which is not available to
+check against -- README, "statements every number here rests on").  For a field ``x`` of ``m x n`` values, ``l = max(m, n)``:
+
+* ``P[u][v] = |sum_ij x[i][j] exp(-2 pi i (u i / m + v j / n))|^2 / (m n)``;
+* ``ku``, ``kv`` are the centred integer wavenumbers of ``u`` and ``v``, as after an ``fftshift``: ``-floor(m / 2) ...``, which is
+  ``-m/2 .. m/2 - 1`` at an even size;
+* ``r = round(sqrt(ku^2 + kv^2))``.  A sum of two squares is never ``(k + 1/2)^2``, so there is no tie and the integer rule
+  ``k^2 - k < ku^2 + kv^2 <= k^2 + k  <=>  r = k`` is exact;
+* bins are ``r = 0 .. l/2 - 1`` (``l`` even) or ``0 .. floor(l / 2)`` (``l`` odd); ``S[r]`` is the mean of ``P`` over the cells with that
+  ``r``; cells with a larger ``r`` are dropped;
+* ``normalize=True`` divides ``S`` by ``sum_r S[r]``;
+* the frequencies are ``fftfreq(l, d)[r]`` and the wavelengths ``1 / freq``, ``inf`` at ``r = 0`` as in the reference.
+
+Nothing here synchronises.  A NaN in a field gives that field a NaN spectrum; the reference's library raises on one instead.  The
+reference scores DE-NORMALISED fields (``QuantileNormalizer.unnormalize`` first, exp/exputil.py): do the same before calling this.
+
+Out of scope: the SSIM and sliced-Wasserstein scores of exp/metrics.py (the latter draws its projections inside a library this
+project does not have), and collectives -- members are rank-local, gathering a report across ranks is the caller's.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+
+FFT_CHUNK_ELEMS = 1 << 23  # complex values per fallback chunk (64 MiB of complex64)
+_TABLES: Dict[tuple, torch.Tensor] = {}
+
+
+def num_bins(H: int, W: int) -> int:
+    l = max(H, W)
+    return l // 2 if l % 2 == 0 else l // 2 + 1
+
+
+def cell_bins(H: int, W: int) -> np.ndarray:
+    """(H, W) int64: the bin r of every cell of the unshifted transform by the integer rule, -1 where r is beyond the last bin."""
+    # fftfreq(n) * n is -n/2 .. n/2 - 1 (n even) or -(n-1)/2 .. (n-1)/2 (n odd) in the transform's own order
+    ku, kv = np.rint(np.fft.fftfreq(H) * H).astype(np.int64), np.rint(np.fft.fftfreq(W) * W).astype(np.int64)
+    s = ku[:, None] ** 2 + kv[None, :] ** 2
+    r = np.floor(np.sqrt(s.astype(np.float64))).astype(np.int64)
+    r = np.where(s > r * r + r, r + 1, r)      # k^2 - k < s <= k^2 + k  <=>  r = k
+    r = np.where((r > 0) & (s <= r * r - r), r - 1, r)  # (guards the float sqrt at perfect squares; s = 0 is bin 0)
+    return np.where(r < num_bins(H, W), r, -1)
+
+
+def frequencies(H: int, W: int, d: float = 1.0) -> np.ndarray:
+    """fftfreq(l, d)[r] for the bins r, float64 (bin 0 is frequency 0: its wavelength is inf)"""
+    return np.fft.fftfreq(max(H, W), d=d)[:num_bins(H, W)]
+
+
+def wavelengths(H: int, W: int, d: float = 1.0) -> np.ndarray:
+    with np.errstate(divide="ignore"):
+        return 1.0 / frequencies(H, W, d)
+
+
+def _on_device(x: torch.Tensor) -> bool:
+    return x.is_cuda
+
+
+def _bin_table(H: int, W: int, device) -> torch.Tensor:
+    """(H * W, R) float64: 1 / (cells of bin r) where the cell belongs to bin r -- a dense product with it is the bin mean"""
+    key = (H, W, str(device))
+    if key not in _TABLES:
+        r = cell_bins(H, W).reshape(-1)
+        R = num_bins(H, W)
+        t = np.zeros((H * W, R), dtype=np.float64)
+        keep = r >= 0
+        cnt = np.bincount(r[keep], minlength=R).astype(np.float64)
+        t[np.nonzero(keep)[0], r[keep]] = 1.0 / cnt[r[keep]]
+        _TABLES[key] = torch.from_numpy(t).to(device)
+    return _TABLES[key]
+
+
+def _rapsd_general(x: torch.Tensor, out: torch.Tensor) -> None:
+    """The definition for any (H, W) on any device: fp32 torch.fft in chunks of bounded size, power, and a dense float64 product with
+    the cell-to-bin table (no index_add_: its order is not fixed on the GPU).  Like the kernel it takes the mean off first and forms
+    bin 0, which is the cell P[0][0] alone, from the field's float64 sum."""
+    n, H, W = x.shape
+    table = _bin_table(H, W, x.device)
+    step = max(1, FFT_CHUNK_ELEMS // (H * W))
+    for i in range(0, n, step):
+        c = x[i:i + step]
+        total = c.sum(dim=(-2, -1), dtype=torch.float64)
+        z = torch.fft.fft2(c - (total / (H * W)).to(torch.float32)[:, None, None])
+        p = (z.real.double() ** 2 + z.imag.double() ** 2).reshape(c.shape[0], H * W) / (H * W)
+        s = p @ table
+        s[:, 0] = total * total / (H * W)
+        out[i:i + step] = s.to(torch.float32)
+
+
+def rapsd(fields: torch.Tensor, normalize: bool = True, d: float = 1.0, return_freq: bool = False):
+    """``fields (..., H, W)`` of any float dtype and any strides -> ``(..., R)`` fp32 spectra on the same device (module docstring: the
+    definition).  Square fields of 8, 16, 32, 64 or 128 on the GPU take the fused kernel; every other shape -- rectangular, odd, larger
+    (the deep variant's 256 x 256) -- and CPU tensors take the same definition through torch.fft.  ``return_freq``: also the float64
+    frequencies ``fftfreq(max(H, W), d)[r]`` as a NumPy array."""
+    if fields.dim() < 2:
+        raise ValueError("rapsd needs (..., H, W)")
+    H, W = int(fields.shape[-2]), int(fields.shape[-1])
+    lead, R = tuple(fields.shape[:-2]), num_bins(H, W)
+    x = fields
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = torch.empty(fields.shape, dtype=torch.float32, device=fields.device).copy_(fields)  # the one copy: dense and fp32 at once
+    if x.data_ptr() % 16 != 0:
+        x = x.clone()
+    x = x.view(-1, H, W)
+    n = x.shape[0]
+    spec = torch.empty((n, R), dtype=torch.float32, device=x.device)
+    if n > 0 and not (_on_device(x) and ops.rapsd(x, spec, n, H, W)):
+        _rapsd_general(x, spec)
+    if normalize:
+        spec = (spec.double() / spec.sum(dim=-1, keepdim=True, dtype=torch.float64)).to(torch.float32)
+    spec = spec.view(*lead, R)
+    return (spec, frequencies(H, W, d)) if return_freq else spec
+
+
+def melr(sample_spec: torch.Tensor, truth_spec: torch.Tensor, mode: str = "mean") -> torch.Tensor:
+    """Mean absolute log ratio of each member's spectrum to the truth's (exp/metrics.py:153-181): ``sample_spec (M, T, ..., R)``,
+    ``truth_spec (T, ..., R)`` -> ``(M, ...)`` float64.  Per time ``|log(S_sample / S_truth)|`` over ALL bins, r = 0 included, combined
+    with equal weights (``"mean"``), with weights ``S_truth / sum S_truth`` (``"weighted"``, the reference's do_weighted) or taken at the
+    bin of largest truth energy only (``"max"``, do_max); then the mean over time."""
+    if mode not in ("mean", "weighted", "max"):
+        raise ValueError(f"melr mode {mode!r}: one of 'mean', 'weighted', 'max'")
+    if sample_spec.shape[1:] != truth_spec.shape:
+        raise ValueError(f"sample_spec {tuple(sample_spec.shape)} is not (M,) + truth_spec {tuple(truth_spec.shape)}")
+    t = truth_spec.double()
+    ratio = (sample_spec.double() / t).log().abs()
+    if mode == "max":
+        idx = t.argmax(dim=-1, keepdim=True)
+        per_time = ratio.gather(-1, idx.expand(sample_spec.shape[0], *idx.shape)).squeeze(-1)
+    elif mode == "weighted":
+        per_time = (ratio * (t / t.sum(dim=-1, keepdim=True))).sum(dim=-1)
+    else:
+        per_time = ratio.sum(dim=-1) / ratio.shape[-1]
+    return per_time.mean(dim=1)
+
+
+MELR_MODES = ("mean", "weighted", "max")
+
+
+class SpectralReport:
+    """Per variable, the dictionary the reference's ``rapsd()`` saves (exp/metrics.py:104-110) as device tensors --
+    ``wavelengths (R,)``, ``obs_wavelengths``, ``sample_rapsd_over_time (M, T, R)``, ``gt_rapsd_over_time (T, R)``,
+    ``obs_rapsd_over_time (T, R_obs)`` (the two ``obs_*`` entries are None without observations) -- plus ``melr``: ``{mode: (M,)}``."""
+
+    def __init__(self, names: Sequence[str], variables: List[dict]):
+        self.names, self.variables = list(names), variables
+
+    def __getitem__(self, name: str) -> dict:
+        return self.variables[self.names.index(name)]
+
+    def __iter__(self):
+        return iter(zip(self.names, self.variables))
+
+    def as_dict(self, prefix: str = "spectra") -> dict:
+        """flat ``{name: float}`` for a logger (one device-to-host copy): per variable and mode the mean and the standard deviation of
+        MELR over the members, as the reference prints them (exp/metrics.py:291: numpy's population std)"""
+        stack = torch.stack([v["melr"][m] for v in self.variables for m in MELR_MODES]).cpu().numpy()
+        out, i = {}, 0
+        for name in self.names:
+            for m in MELR_MODES:
+                out[f"{prefix}/{name}/melr_{m}"] = float(stack[i].mean())
+                out[f"{prefix}/{name}/melr_{m}_std"] = float(stack[i].std())
+                i += 1
+        return out
+
+
+def spectral_report(samples: torch.Tensor, truth: torch.Tensor, obs: Optional[torch.Tensor] = None, *, t_step: int = 1,
+                    s_step: Optional[int] = None, d: float = 6.0, names: Optional[Sequence[str]] = None) -> SpectralReport:
+    """Spectra and MELR of an ensemble ``samples (M, L, F, H, W)`` against ``truth (L, F, H, W)``, normalised spectra as the reference
+    computes them (``normalize=True``, grid spacing ``d = 6`` km).  ``t_step`` keeps every t_step-th frame of both, as the reference
+    restricts its scores to the observation times (exp/metrics.py:239-240).  ``obs (T, F, h, w)``, one field per kept frame, gets its own
+    spectra at the spacing ``d * s_step`` (``s_step`` defaults to ``H // h``; the reference's is 16).  The fields are expected
+    DE-NORMALISED, as the reference's are (``QuantileNormalizer.unnormalize`` first).  ``names``: one per variable, default ``var0 ...``."""
+    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
+        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    M, L, F, H, W = samples.shape
+    names = [f"var{f}" for f in range(F)] if names is None else list(names)
+    if len(names) != F:
+        raise ValueError(f"{len(names)} names for {F} variables")
+    t_step = int(t_step)
+    if t_step < 1:
+        raise ValueError("t_step >= 1")
+    s_spec = rapsd(samples[:, ::t_step])  # (M, T, F, R)
+    g_spec = rapsd(truth[::t_step])       # (T, F, R)
+    T = g_spec.shape[0]
+    wl = torch.from_numpy(wavelengths(H, W, d)).to(samples.device)
+    o_spec = o_wl = None
+    if obs is not None:
+        if obs.dim() != 4 or obs.shape[0] != T or obs.shape[1] != F:
+            raise ValueError(f"obs {tuple(obs.shape)} must be (T = {T}, F = {F}, h, w)")
+        h, w = int(obs.shape[-2]), int(obs.shape[-1])
+        s_step = max(1, H // h) if s_step is None else int(s_step)
+        o_spec = rapsd(obs)               # (T, F, R_obs)
+        o_wl = torch.from_numpy(wavelengths(h, w, d * s_step)).to(samples.device)
+    scores = {m: melr(s_spec, g_spec, m) for m in MELR_MODES}  # (M, F)
+    variables = []
+    for f in range(F):
+        variables.append(dict(wavelengths=wl, obs_wavelengths=o_wl, sample_rapsd_over_time=s_spec[:, :, f], gt_rapsd_over_time=g_spec[:, f],
+                              obs_rapsd_over_time=None if o_spec is None else o_spec[:, f], melr={m: scores[m][:, f] for m in MELR_MODES}))
+    return SpectralReport(names, variables)

@@ -341,6 +341,22 @@ int c2w_sq_err_levels(const void* y, const float* eps, const float* t, double* t
                       int ldc, int K, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream);
 int c2w_sq_err_levels_noise(const void* y, unsigned long long seed, const float* t, double* table, long long* count, float* per_image, int B,
                             int C, int HW, int ldc, int K, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream);
+/* Ensemble spectra: the radially averaged power spectral density of n_fields dense fp32 fields x[n_fields][H][W] (16-byte aligned),
+ * spec[n_fields][H/2] fp32, un-normalised.  The definition is the radial spectrum the reference's scores take from a radar library
+ * (exp/metrics.py:67), restated here from memory of that library and not checked against it:
+ *   P[u][v]  = |sum_ij x[i][j] exp(-2 pi i (u i / H + v j / W))|^2 / (H W)
+ *   ku, kv   = the centred integer wavenumbers of u and v (-H/2 .. H/2 - 1 at an even size, as after an fftshift)
+ *   r        = round(sqrt(ku^2 + kv^2)); a sum of two squares is never (k + 1/2)^2, so  k^2 - k < ku^2 + kv^2 <= k^2 + k  <=>  r = k
+ *   spec[k]  = the mean of P over the cells with r = k,  k = 0 .. H/2 - 1; cells with a larger r are dropped.
+ * bin 0 is the single cell P[0][0] = (sum x)^2 / (H W), formed from the field's sum in double; the mean is taken off before the
+ * transform, so a large mean never enters an fp32 butterfly.  Frequencies, wavelengths and the division by sum_k spec[k] are the caller's.
+ * One launch, one read of each field, nothing else in global memory, no scratch, no allocation, no atomics: a field is transformed in
+ * LDS (two real rows per complex row transform, column transforms over the H/2 columns that can reach a bin, twiddles rounded from
+ * double) and every sum has one order fixed by H, so a field's H/2 outputs are the same bits wherever it lies in the batch.  A NaN in
+ * a field gives that field a NaN spectrum.  Fields of 8, 16 and 32 share a workgroup (16, 8, 4 of them); rows of spec past n_fields
+ * are never written.  Supported: H == W in {8, 16, 32, 64, 128}; everything else returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_rapsd_supported(int H, int W); /* 1 or 0 */
+int c2w_rapsd(const float* x, float* spec, long long n_fields, int H, int W, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`

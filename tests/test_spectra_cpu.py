@@ -1,0 +1,291 @@
+"""CPU checks of the ensemble spectra (climate2weather_amd.spectra): known answers of the definition through both routes of
+spectra.rapsd -- the general torch.fft one and the launcher's, with tests/emu_spectrum_ops.py standing in for the HIP kernel -- the bin
+table, the half-spectrum shortcut against the cell-by-cell definition, MELR against a line-by-line restatement of the reference, the
+report's layout, the kernel's own arithmetic compiled for the host (csrc/spectrum_core.h), and the C declarations against the ctypes
+prototypes."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import emu_spectrum_ops
+import fp64_spectrum_ref as R
+from climate2weather_amd import _lib
+from climate2weather_amd import ops as c2w_ops
+from climate2weather_amd import spectra
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNEL_SIZES = (8, 16, 32, 64, 128)
+
+
+@pytest.fixture(params=["general", "launcher"])
+def route(request, monkeypatch):
+    """both branches of spectra.rapsd on CPU tensors"""
+    if request.param == "launcher":
+        emu_spectrum_ops.install(monkeypatch, c2w_ops, spectra)
+    return request.param
+
+
+def _raw(x):
+    return spectra.rapsd(torch.as_tensor(x), normalize=False).double().numpy()
+
+
+# ------------------------------------------------------------------------------------------------------------------ known answers
+
+@pytest.mark.parametrize("N", [8, 16, 32])
+def test_impulse_is_flat(route, N):
+    S = _raw(R.impulse(N))
+    assert S.shape == (N // 2,)
+    assert np.allclose(S, 1.0 / (N * N), rtol=1e-6, atol=0.0)
+
+
+@pytest.mark.parametrize("N", [8, 16, 64])
+def test_constant_is_bin_zero_only(route, N):
+    c = 0.75
+    S = _raw(np.full((N, N), c, dtype=np.float32))
+    assert S[0] == pytest.approx(c * c * N * N, rel=1e-6)
+    assert np.all(np.abs(S[1:]) <= 1e-12 * S[0])
+
+
+@pytest.mark.parametrize("N,a,b", [(8, 1, 2), (16, 3, 4), (32, -5, 2), (32, 0, 15), (64, 31, 0), (16, 7, -1)])
+def test_plane_wave_lands_in_its_bin(route, N, a, b):
+    k = int(round(np.hypot(a, b)))
+    assert k < N // 2
+    S = _raw(R.plane_wave(N, a, b))
+    want = np.zeros(N // 2)
+    want[k] = N * N / 2.0 / R.bin_counts(N, N)[k]
+    assert np.allclose(S, want, rtol=2e-6, atol=1e-9 * want[k])
+
+
+@pytest.mark.parametrize("N,a,b", [(8, 4, 0), (16, 8, 0), (32, -16, 3), (16, 0, 8)])
+def test_nyquist_wave_lands_in_no_bin(route, N, a, b):
+    S = _raw(R.plane_wave(N, a, b))
+    assert np.all(np.abs(S) <= 1e-9)  # the wave's cell holds N^2 / 2 or N^2
+
+
+def test_launcher_route_reaches_the_launcher_and_the_general_route_does_not(monkeypatch):
+    emu_spectrum_ops.install(monkeypatch, c2w_ops, spectra)
+    spectra.rapsd(torch.zeros(3, 2, 16, 16))
+    spectra.rapsd(torch.zeros(2, 24, 20))  # asked, answered "unsupported", general route taken
+    assert emu_spectrum_ops.CALLS == [(6, 16, 16), (2, 24, 20)]
+
+
+# ------------------------------------------------------------------------------------------------------------------ bins
+
+@pytest.mark.parametrize("N", KERNEL_SIZES + (256,))
+def test_bin_counts_start_1_8_12_16(N):
+    bins = spectra.cell_bins(N, N)
+    cnt = np.bincount(bins[bins >= 0], minlength=N // 2)
+    assert list(cnt[:4]) == [1, 8, 12, 16]
+    assert np.array_equal(cnt, R.bin_counts(N, N))
+    assert np.array_equal(np.where(bins >= 0, bins, 0), np.where(R.radius(N, N) < N // 2, R.radius(N, N), 0))  # integer rule == np.rint
+
+
+@pytest.mark.parametrize("m,n", [(24, 20), (15, 15), (9, 14), (7, 7)])
+def test_bins_of_odd_and_rectangular_sizes(m, n):
+    bins, r = spectra.cell_bins(m, n), R.radius(m, n)
+    assert spectra.num_bins(m, n) == R.n_bins(m, n)
+    assert np.array_equal(bins >= 0, r < R.n_bins(m, n)) and np.array_equal(bins[bins >= 0], r[bins >= 0])
+
+
+@pytest.mark.parametrize("N", [8, 16, 32])
+def test_half_spectrum_weighting_equals_the_cell_by_cell_definition(N):
+    x = np.stack([R.white(N, 5), R.power_law(N, 6)])
+    full, half = R.rapsd64(x), R.rapsd_half64(x)
+    assert np.abs(half / full - 1.0).max() < 1e-12
+    out = torch.empty(2, N // 2)
+    assert emu_spectrum_ops.rapsd(torch.as_tensor(x), out, 2, N, N)
+    assert np.abs(out.double().numpy() / full - 1.0).max() < 1e-6
+
+
+def test_frequencies_and_wavelengths():
+    S, f = spectra.rapsd(torch.randn(16, 16), d=6.0, return_freq=True)
+    assert S.shape == (8,) and np.array_equal(f, np.fft.fftfreq(16, d=6.0)[:8])
+    w = spectra.wavelengths(16, 16, 6.0)
+    assert np.isinf(w[0]) and np.allclose(w[1:], 96.0 / np.arange(1, 8))
+    assert spectra.frequencies(24, 20).shape == (12,) and spectra.frequencies(15, 15).shape == (8,)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the general route
+
+@pytest.mark.parametrize("m,n", [(24, 20), (15, 15), (256, 256)])
+def test_general_route_against_float64(m, n):
+    x = (0.5 + np.random.default_rng(m).standard_normal((2, m, n))).astype(np.float32)
+    S64 = R.rapsd64(x)
+    S = _raw(x)
+    assert S.shape == S64.shape == (2, R.n_bins(m, n))
+    e, b = R.e_log(S, S64), R.bound_log(x, S64)
+    print(f"{m}x{n}: e_log {e} bound {b}")
+    assert np.all(e <= b)
+    Sn = spectra.rapsd(torch.as_tensor(x)).double().numpy()
+    assert np.allclose(Sn.sum(-1), 1.0, atol=1e-6) and np.allclose(Sn, R.rapsd64(x, normalize=True), rtol=1e-5)
+
+
+def test_any_dtype_any_strides_any_leading_shape(route):
+    base = torch.randn(3, 2, 16, 32, dtype=torch.float64)
+    view = base[..., ::2]  # (3, 2, 16, 16), strided
+    want = R.rapsd64(view.numpy(), normalize=True)
+    got = spectra.rapsd(view)
+    assert got.shape == (3, 2, 8) and got.dtype == torch.float32
+    assert np.allclose(got.double().numpy(), want, rtol=1e-5)
+    off = torch.randn(16 * 16 + 1)[1:].view(16, 16)  # 4-byte aligned only
+    assert np.allclose(spectra.rapsd(off).double().numpy(), R.rapsd64(off.numpy(), normalize=True), rtol=1e-5)
+    half = spectra.rapsd(view.to(torch.float16))
+    assert half.dtype == torch.float32 and np.allclose(half.double().numpy(), R.rapsd64(view.to(torch.float16).double().numpy(), normalize=True), rtol=1e-5)
+    assert spectra.rapsd(torch.zeros(0, 16, 16)).shape == (0, 8)
+
+
+def test_nan_field_gives_nan_spectrum_and_spares_its_neighbours(route):
+    x = torch.randn(3, 16, 16)
+    x[1, 4, 4] = float("nan")
+    S = spectra.rapsd(x)
+    assert torch.isnan(S[1]).all() and torch.isfinite(S[0]).all() and torch.isfinite(S[2]).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ melr
+
+@pytest.mark.parametrize("mode,kw", [("mean", {}), ("weighted", dict(do_weighted=True)), ("max", dict(do_max=True))])
+def test_melr_against_the_reference_loop(mode, kw):
+    rng = np.random.default_rng(11)
+    s, g = rng.uniform(0.1, 2.0, (3, 5, 16)), rng.uniform(0.1, 2.0, (5, 16))
+    got = spectra.melr(torch.as_tensor(s), torch.as_tensor(g), mode)
+    assert got.dtype == torch.float64 and got.shape == (3,)
+    assert np.allclose(got.numpy(), R.melr_reference(s, g, **kw), rtol=1e-13, atol=0.0)
+
+
+def test_melr_keeps_the_dimensions_between_time_and_bins():
+    rng = np.random.default_rng(12)
+    s, g = rng.uniform(0.1, 2.0, (3, 5, 2, 16)), rng.uniform(0.1, 2.0, (5, 2, 16))
+    for mode, kw in (("mean", {}), ("weighted", dict(do_weighted=True)), ("max", dict(do_max=True))):
+        got = spectra.melr(torch.as_tensor(s), torch.as_tensor(g), mode).numpy()
+        assert got.shape == (3, 2)
+        for f in range(2):
+            assert np.allclose(got[:, f], R.melr_reference(s[:, :, f], g[:, f], **kw), rtol=1e-13)
+    with pytest.raises(ValueError):
+        spectra.melr(torch.as_tensor(s), torch.as_tensor(g), "median")
+    with pytest.raises(ValueError):
+        spectra.melr(torch.as_tensor(s), torch.as_tensor(g[:4]), "mean")
+
+
+# ------------------------------------------------------------------------------------------------------------------ report
+
+def _ensemble(M=2, L=5, F=2, N=16, seed=4):
+    rng = np.random.default_rng(seed)
+    truth = np.stack([np.stack([R.power_law(N, 100 + 10 * l + f) + 0.3 for f in range(F)]) for l in range(L)])
+    samples = truth[None] + 0.1 * rng.standard_normal((M, L, F, N, N)).astype(np.float32)
+    return samples.astype(np.float32), truth.astype(np.float32)
+
+
+def report_reference(samples, truth, obs, t_step):
+    """per variable: the reference's dictionary and the three MELRs, float64, with its loops"""
+    out = []
+    s, g = samples[:, ::t_step], truth[::t_step]
+    for f in range(truth.shape[1]):
+        sr, gr = R.rapsd64(s[:, :, f], normalize=True), R.rapsd64(g[:, f], normalize=True)
+        d = dict(sample_rapsd_over_time=sr, gt_rapsd_over_time=gr, obs_rapsd_over_time=None if obs is None else R.rapsd64(obs[:, f], normalize=True))
+        d["melr"] = dict(mean=R.melr_reference(sr, gr), weighted=R.melr_reference(sr, gr, do_weighted=True), max=R.melr_reference(sr, gr, do_max=True))
+        out.append(d)
+    return out
+
+
+@pytest.mark.parametrize("t_step", [1, 2])
+def test_report_layout_t_step_and_obs(route, t_step):
+    samples, truth = _ensemble()
+    T = len(range(0, 5, t_step))
+    obs = truth[::t_step].reshape(T, 2, 4, 4, 4, 4).mean(axis=(3, 5)).astype(np.float32)  # (T, F, 4, 4): odd one out, general route
+    rep = spectra.spectral_report(torch.as_tensor(samples), torch.as_tensor(truth), torch.as_tensor(obs), t_step=t_step, names=["tas", "psl"])
+    want = report_reference(samples, truth, obs, t_step)
+    assert rep.names == ["tas", "psl"]
+    for f, (name, v) in enumerate(rep):
+        assert set(v) == {"wavelengths", "obs_wavelengths", "sample_rapsd_over_time", "gt_rapsd_over_time", "obs_rapsd_over_time", "melr"}
+        assert v["sample_rapsd_over_time"].shape == (2, T, 8) and v["gt_rapsd_over_time"].shape == (T, 8) and v["obs_rapsd_over_time"].shape == (T, 2)
+        assert np.allclose(v["wavelengths"].numpy()[1:], 6.0 * 16 / np.arange(1, 8)) and bool(torch.isinf(v["wavelengths"][0]))
+        assert np.allclose(v["obs_wavelengths"].numpy()[1:], [6.0 * 4 * 4]) and v["obs_wavelengths"].shape == (2,)
+        for key in ("sample_rapsd_over_time", "gt_rapsd_over_time", "obs_rapsd_over_time"):
+            assert np.allclose(v[key].double().numpy(), want[f][key], rtol=2e-5), key
+        for mode in spectra.MELR_MODES:
+            assert v["melr"][mode].shape == (2,) and v["melr"][mode].dtype == torch.float64
+            assert np.allclose(v["melr"][mode].numpy(), want[f]["melr"][mode], rtol=0.0, atol=1e-5), mode
+        assert rep[name] is v
+    flat = rep.as_dict("eval")
+    assert set(flat) == {f"eval/{n}/melr_{m}{s}" for n in ("tas", "psl") for m in spectra.MELR_MODES for s in ("", "_std")}
+    assert all(isinstance(x, float) for x in flat.values())
+    assert flat["eval/psl/melr_mean"] == pytest.approx(want[1]["melr"]["mean"].mean(), abs=1e-5)
+    assert flat["eval/psl/melr_mean_std"] == pytest.approx(want[1]["melr"]["mean"].std(), abs=1e-5)
+
+
+def test_report_without_obs_and_its_argument_checks():
+    samples, truth = _ensemble(L=3)
+    rep = spectra.spectral_report(torch.as_tensor(samples), torch.as_tensor(truth))
+    assert rep.names == ["var0", "var1"] and rep["var0"]["obs_rapsd_over_time"] is None and rep["var0"]["obs_wavelengths"] is None
+    with pytest.raises(ValueError):
+        spectra.spectral_report(torch.as_tensor(samples), torch.as_tensor(truth[:2]))
+    with pytest.raises(ValueError):
+        spectra.spectral_report(torch.as_tensor(samples), torch.as_tensor(truth), names=["only_one"])
+    with pytest.raises(ValueError):
+        spectra.spectral_report(torch.as_tensor(samples), torch.as_tensor(truth), torch.zeros(2, 2, 4, 4))  # T = 3
+
+
+# ------------------------------------------------------------------------------------------------------------------ the kernel's arithmetic
+
+def _cxx():
+    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
+        if cand and shutil.which(cand):
+            return [shutil.which(cand)]
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
+    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
+    return [hipcc, "-x", "c++"]
+
+
+@pytest.fixture(scope="module")
+def host_spectrum(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("host_spectrum") / "host_spectrum"
+    subprocess.run(_cxx() + ["-O1", "-std=c++17", "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"),
+                             os.path.join(ROOT, "tests", "host_spectrum_main.cpp"), "-o", str(exe)], check=True, timeout=300)
+    return exe
+
+
+@pytest.mark.parametrize("N", KERNEL_SIZES)
+def test_kernel_phases_on_the_host_meet_the_tolerance(host_spectrum, tmp_path, N):
+    """csrc/spectrum_core.h compiled for the host, its phases run one thread after the other: every index map of the kernel (packed rows,
+    in-place slots, the untangle, the column passes, the bin walk) and its fp32 arithmetic, against float64 by the rule of the GPU tier."""
+    dense, sparse = R.dense_fields(N), R.sparse_fields(N)
+    x = np.stack(list(dense.values()) + list(sparse.values()))
+    x.tofile(tmp_path / "in.f32")
+    subprocess.run([str(host_spectrum), str(N), str(len(x)), str(tmp_path / "in.f32"), str(tmp_path / "out.f32")], check=True, timeout=120)
+    S = np.fromfile(tmp_path / "out.f32", dtype=np.float32).reshape(len(x), N // 2)
+    S64 = R.rapsd64(x)
+    for i, name in enumerate(list(dense) + list(sparse)):
+        if name in dense:
+            e, b = R.e_log(S[i], S64[i]), R.bound_log(x[i], S64[i])
+        else:
+            e, b = R.e_abs(S[i], S64[i], x[i]), R.bound_abs(x[i], S64[i])
+        print(f"N={N} {name}: error {e:.3g} bound {b:.3g}")
+        assert e <= b, (N, name, e, b)
+
+
+# ------------------------------------------------------------------------------------------------------------------ C ABI
+
+def test_new_entry_points_have_matching_argument_lists():
+    from ctypes import c_int, c_longlong, c_void_p
+    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+
+    def ctype(arg):
+        arg = " ".join(arg.split())
+        if "*" in arg:
+            return c_void_p
+        return {"int": c_int, "long long": c_longlong}[arg.rsplit(" ", 1)[0]]
+
+    for name in ("c2w_rapsd_supported", "c2w_rapsd"):
+        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
+        assert m is not None, name
+        assert " ".join(m.group(1).split()) == "int"
+        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
+    assert {"c2w_rapsd_supported", "c2w_rapsd"} <= set(_lib.exported_symbols())
+    from climate2weather_amd import build as c2w_build
+    assert "spectrum.hip" in c2w_build.SOURCES
