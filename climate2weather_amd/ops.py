@@ -438,6 +438,22 @@ def rapsd(x, spec, n_fields, H, W) -> bool:
     return True
 
 
+def ssim_supported(H: int, W: int, win: int) -> bool:
+    return bool(_lib.load().c2w_ssim_supported(H, W, win))
+
+
+def ssim(x, y, data_range, out, n_pairs, n_truth, H, W, win) -> bool:
+    """out (n_pairs,) float64 = the mean SSIM of the pairs (x[i], y[i % n_truth]) of dense fp32 fields (H, W), 16-byte aligned, under
+    a uniform win x win window with the data range data_range[i % n_truth] (a device tensor of n_truth fp32)
+    (include/c2w_hip.h::c2w_ssim: the definition, the pivot, the fixed summation order).  False if the shape or the window is not
+    supported -- nothing is written and the caller takes the general definition (ssim.ssim)."""
+    rc = _lib.load().c2w_ssim(_p(x), _p(y), _p(data_range), _p(out), n_pairs, n_truth, H, W, win, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_ssim")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

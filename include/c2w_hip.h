@@ -357,6 +357,28 @@ int c2w_sq_err_levels_noise(const void* y, unsigned long long seed, const float*
  * are never written.  Supported: H == W in {8, 16, 32, 64, 128}; everything else returns C2W_ERR_UNSUPPORTED and writes nothing. */
 int c2w_rapsd_supported(int H, int W); /* 1 or 0 */
 int c2w_rapsd(const float* x, float* spec, long long n_fields, int H, int W, void* stream);
+/* Ensemble SSIM: the mean structural similarity of n_pairs field pairs under a uniform win x win window, out[n_pairs] double.
+ * x[n_pairs][H][W] and y[n_truth][H][W] are dense fp32, 16-byte aligned; pair i is (x[i], y[i % n_truth]) -- the layout that samples
+ * [M][T][F] against truth [T][F] gives; data_range[n_truth] is a DEVICE array, one range per truth slot (variables may differ), read by
+ * the kernel: nothing synchronises to fetch it.  The definition is the image library's structural_similarity with its defaults as the
+ * reference calls it (exp/metrics.py:201-210: uniform window, sample covariance), restated here from memory of that library and not
+ * checked against it.  With NP = win^2, cn = NP / (NP - 1), R = data_range:
+ *   u_a  = the mean of a over the window, for a in x, y, xx, yy, xy
+ *   vx   = cn (u_xx - u_x^2), vy likewise, vxy = cn (u_xy - u_x u_y);   C1 = (0.01 R)^2, C2 = (0.03 R)^2
+ *   S    = (2 u_x u_y + C1)(2 vxy + C2) / ((u_x^2 + u_y^2 + C1)(vx + vy + C2))
+ *   out  = the mean of S over the (H - win + 1)(W - win + 1) windows that lie inside the field (the library's crop by (win - 1) / 2, so
+ *          its border mode never matters).
+ * Numerics: both fields of a pair have p = the mean of y (double sum) taken off before any product is formed -- variances and the
+ * covariance do not move, and the luminance factor is formed as 1 - (u_x - u_y)^2 / (u_x^2 + u_y^2 + C1) with u_x = p + mean(x - p);
+ * window sums are direct fp32 sums, down the columns and then along the rows; the mean over the windows is a double sum.
+ * One launch, one read of each x field (y is read twice: for p, then with x), nothing but `out` written to global memory, no scratch,
+ * no atomics; every sum has one order fixed by (H, W, win), so out[i] is the same bits whatever i, n_pairs and n_truth are.  A NaN in a
+ * pair gives that pair NaN and no other; a NaN data_range gives NaN to the pairs of its slot.  Rows of out past n_pairs are never
+ * written.  Pairs with W <= 32 share a workgroup, four of them.  Supported: H and W multiples of 8 from 16 to 128 (rectangular
+ * included), win in {7, 11, 15}; everything else returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_ssim_supported(int H, int W, int win); /* 1 or 0 */
+int c2w_ssim(const float* x, const float* y, const float* data_range, double* out, long long n_pairs, long long n_truth, int H, int W, int win,
+             void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
