@@ -326,7 +326,9 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
             if (c < C) {
                 const size_t o = ((size_t)b * C + c) * HW + pix;
                 v = x[o];
-                if (eps) v = musig[2 * b] * v + musig[2 * b + 1] * eps[o];
+                // the tiled kernel's x_t (Ld::mix below), spelled out: left to the compiler this became v_pk_mul_f32 + v_add_f32, both
+                // products rounded -- one rounding more than the route every narrower row takes, and other bits for the same operands
+                if (eps) v = __fmaf_rn(musig[2 * b + 1], eps[o], __fmul_rn(musig[2 * b], v));
             }
             f[e] = v;
         }
