@@ -101,6 +101,10 @@ _PROTOS = {
     "c2w_rapsd": [c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
     "c2w_ssim_supported": [c_int, c_int, c_int],
     "c2w_ssim": [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_int, c_int, c_void_p],
+    "c2w_swd_supported": [c_int, c_int, c_int],
+    "c2w_swd_project": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_swd_project_pair": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_swd_distance": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

@@ -454,6 +454,43 @@ def ssim(x, y, data_range, out, n_pairs, n_truth, H, W, win) -> bool:
     return True
 
 
+def swd_supported(d: int, P: int, T: int) -> bool:
+    return bool(_lib.load().c2w_swd_supported(d, P, T))
+
+
+def swd_project(x, theta, shift, scale, proj, n_rep, T, F, d, P) -> bool:
+    """proj (n_rep, F, P, T) fp32 = every dense fp32 field of x (n_rep, T, F, d), 16-byte aligned, normalised as
+    ``(x - shift[f]) * scale[f]`` in fp32 and projected onto the P rows of theta (P, d) fp32 (include/c2w_hip.h::c2w_swd_project: the
+    fixed summation order).  shift, scale: device tensors of F fp32.  False if d or P is not supported -- nothing is written and the
+    caller takes the general definition (wasserstein.sliced_wasserstein)."""
+    rc = _lib.load().c2w_swd_project(_p(x), _p(theta), _p(shift), _p(scale), _p(proj), n_rep, T, F, d, P, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_swd_project")
+    return True
+
+
+def swd_project_pair(x, y, theta, shift, scale, proj_x, proj_y, n_rep, T, F, d, P) -> bool:
+    """``swd_project`` of the samples x (n_rep, T, F, d) into proj_x and of the truth y (T, F, d) into proj_y (F, P, T) in one launch:
+    the same bits as two calls, without a launch that fills an eighth of the chip (include/c2w_hip.h::c2w_swd_project_pair)."""
+    rc = _lib.load().c2w_swd_project_pair(_p(x), _p(y), _p(theta), _p(shift), _p(scale), _p(proj_x), _p(proj_y), n_rep, T, F, d, P, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_swd_project_pair")
+    return True
+
+
+def swd_distance(proj_x, proj_y, out, n_rep, F, P, T) -> bool:
+    """out (n_rep, F, P) float64 = the mean squared difference of the sorted columns proj_x[rep, f, p, :] and proj_y[f, p, :] (fp32,
+    T contiguous; include/c2w_hip.h::c2w_swd_distance).  A NaN in either column gives NaN.  False if T is not supported -- nothing is
+    written."""
+    rc = _lib.load().c2w_swd_distance(_p(proj_x), _p(proj_y), _p(out), n_rep, F, P, T, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_swd_distance")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

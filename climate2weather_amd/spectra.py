@@ -21,9 +21,8 @@ check against -- README, "statements every number here rests on").  For a field 
 Nothing here synchronises.  A NaN in a field gives that field a NaN spectrum; the reference's library raises on one instead.  The
 reference scores DE-NORMALISED fields (``QuantileNormalizer.unnormalize`` first, exp/exputil.py): do the same before calling this.
 
-Out of scope: the sliced-Wasserstein score of exp/metrics.py (a vendor GEMM and a sort, but its projections are drawn by the random
-generator of a library this project does not have, so its numbers could not be matched), and collectives -- members are rank-local,
-gathering a report across ranks is the caller's.  The SSIM score of exp/metrics.py is in ``climate2weather_amd.ssim``.
+Out of scope: collectives -- members are rank-local, gathering a report across ranks is the caller's.  The SSIM score of
+exp/metrics.py is in ``climate2weather_amd.ssim``, its sliced-Wasserstein score in ``climate2weather_amd.wasserstein``.
 """
 from __future__ import annotations
 

@@ -30,7 +30,8 @@ then is NaN for the whole variable, as the reference's is.  The reference scores
 (``QuantileNormalizer.unnormalize`` first, exp/exputil.py): do the same before calling this.
 
 Out of scope: Gaussian weighting, the SSIM map itself, a tiled kernel for the deep variant's 256 x 256 (the general route takes it),
-the sliced-Wasserstein score, and collectives -- members are rank-local, gathering a report across ranks is the caller's.
+and collectives -- members are rank-local, gathering a report across ranks is the caller's.  The sliced-Wasserstein score of
+exp/metrics.py is in ``climate2weather_amd.wasserstein``.
 """
 from __future__ import annotations
 

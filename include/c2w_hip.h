@@ -379,6 +379,34 @@ int c2w_rapsd(const float* x, float* spec, long long n_fields, int H, int W, voi
 int c2w_ssim_supported(int H, int W, int win); /* 1 or 0 */
 int c2w_ssim(const float* x, const float* y, const float* data_range, double* out, long long n_pairs, long long n_truth, int H, int W, int win,
              void* stream);
+/* Ensemble sliced Wasserstein distance (exp/metrics.py:13-44: ot.sliced_wasserstein_distance(a, b, n_projections=100, seed=0) per member
+ * on arrays reshaped to (time, cells)).  The definition is restated from memory of that library (its sliced distance and its 1-D
+ * distance) and not checked against it.  For one variable, samples X (T, d), truth Y (T, d), d = H W, P projections, p = 2:
+ *   theta    = numpy.random.RandomState(seed).randn(d, P) in float64, every column divided by its Euclidean norm -- the same for every
+ *              variable, since the reference passes seed=0 each time (the caller's: climate2weather_amd.wasserstein.projections)
+ *   a, b     = X theta_p, Y theta_p;   D_p = mean_i (sort(a)_i - sort(b)_i)^2  (uniform weights, equal counts: the quantile form)
+ *   SWD      = sqrt(mean_p D_p)        (the caller's)
+ * and the reference normalises both arrays by the truth's moments first (exp/metrics.py:254-258): x^ = (x - shift[f]) * scale[f].
+ * c2w_swd_project: proj[n_rep][F][P][T] fp32 = x^ theta for all n_rep T F fields of x[n_rep][T][F][d] (dense fp32, 16-byte aligned);
+ * theta[P][d] fp32, 16-byte aligned, the float64 columns rounded once; shift[F], scale[F] DEVICE fp32.  Numerics: x^ is formed in fp32
+ * on the loaded value BEFORE any product -- never (theta x - shift sum theta) * scale, a difference of two numbers near 1e5 on a
+ * pressure field.  An fp32-input MFMA GEMM (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain), a workgroup owning 128 fields x all P
+ * projections; a sum is d / 256 chunk sums, each a 256-long chain in a fixed k order, added in ascending order.  No atomics, no
+ * scratch: a field's P outputs are the same bits wherever it lies in the batch; a NaN stays in its field's P outputs; nothing is
+ * written past n_rep F P T.  Supported: d a multiple of 64 from 64 to 65536, 1 <= P <= 128.
+ * c2w_swd_project_pair: the same for x and for the truth y[T][F][d] -> proj_y[F][P][T] in ONE launch (the truth's T F fields are too
+ * few to fill the chip on their own); the same bits as two c2w_swd_project calls.  y == NULL: x only.
+ * c2w_swd_distance: out[n_rep][F][P] double = D_p of the columns proj_x[rep][f][p][0..T) and proj_y[f][p][0..T): one workgroup per
+ * pair sorts both columns in LDS (bitonic, padded with +inf to a power of two, the padding never enters the sum); differences,
+ * squares and the sum over i < T in double, in an order fixed by T.  A NaN in either column is detected at load and NaN is written
+ * for that (rep, f, p) explicitly; +-inf inputs are unspecified.  Supported: 1 <= T <= 16384 (two padded columns = 128 KiB of LDS).
+ * Everything unsupported returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_swd_supported(int d, int P, int T); /* 1 or 0 */
+int c2w_swd_project(const float* x, const float* theta, const float* shift, const float* scale, float* proj, long long n_rep, int T, int F,
+                    int d, int P, void* stream);
+int c2w_swd_project_pair(const float* x, const float* y, const float* theta, const float* shift, const float* scale, float* proj_x,
+                         float* proj_y, long long n_rep, int T, int F, int d, int P, void* stream);
+int c2w_swd_distance(const float* proj_x, const float* proj_y, double* out, long long n_rep, int F, int P, int T, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
