@@ -5,8 +5,7 @@
 //   backward: flash-style recompute from (q,k,v,lse) with delta[t] = sum_c dO[t][c] O[t][c]:
 //             pass A (query tiles): dq ;  pass B (key tiles): dk, dv   -- no atomics, bit-reproducible
 // qkv layout: [B][T][3C] rows (the NHWC output of the 1x1 qkv conv): q | k | v channel blocks.
-#include "common.h"
-#include "c2w_hip.h"
+#include "launch.h"
 
 // matrix-core path for bf16, T = 64 (attention_mfma.hip)
 bool c2w_attention_mfma_eligible(int B, int Tn, int C, int dtype);
@@ -208,14 +207,11 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ a, co
     }
 }
 
-template <typename K>
-int set_lds(K kernel, int bytes) {
-    return (int)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
+constexpr int ATTN_LDS_MAX = 160 * 1024;  // the whole LDS of a CU: the longest score rows these kernels take
 
 template <typename T>
 int valu_forward(const void* qkv, void* o, float* lse, int Tn, int C, dim3 grid, int lds, hipStream_t st) {
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (int rc = c2w_lds_optin<attn_fwd_kernel<T>>(ATTN_LDS_MAX)) return rc;
     attn_fwd_kernel<T><<<grid, 256, lds, st>>>((const T*)qkv, (T*)o, lse, Tn, C);
     return (int)hipGetLastError();
 }
@@ -224,8 +220,8 @@ template <typename T>
 int valu_backward(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dqkv, int Tn, int C, long long rows,
                   dim3 grid, int rgrid, int lds, hipStream_t st) {
     rowdot_kernel<T><<<rgrid, 256, 0, st>>>((const T*)d_o, (const T*)o, delta_ws, rows, C);
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_kernel<T, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_kernel<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (int rc = c2w_lds_optin<attn_bwd_kernel<T, 0>>(ATTN_LDS_MAX)) return rc;
+    if (int rc = c2w_lds_optin<attn_bwd_kernel<T, 1>>(ATTN_LDS_MAX)) return rc;
     attn_bwd_kernel<T, 0><<<grid, 256, lds, st>>>((const T*)qkv, (const T*)d_o, lse, delta_ws, (T*)dqkv, Tn, C);
     attn_bwd_kernel<T, 1><<<grid, 256, lds, st>>>((const T*)qkv, (const T*)d_o, lse, delta_ws, (T*)dqkv, Tn, C);
     return (int)hipGetLastError();
@@ -240,12 +236,9 @@ extern "C" int c2w_attention_forward(const void* qkv, void* o, float* lse, int B
     if (c2w_attention_mfma_blocks_eligible(B, Tn, C, dtype))
         return c2w_attention_mfma_blocks_forward(qkv, o, lse, B, Tn, C, dtype, (hipStream_t)stream);
     const int lds = (TR * C + TR * Tn) * 4;
-    if (lds > 160 * 1024) return C2W_ERR_UNSUPPORTED;
+    if (lds > ATTN_LDS_MAX) return C2W_ERR_UNSUPPORTED;
     dim3 grid((Tn + TR - 1) / TR, B);
-    if (dtype == C2W_DTYPE_F32) return valu_forward<float>(qkv, o, lse, Tn, C, grid, lds, (hipStream_t)stream);
-    if (dtype == C2W_DTYPE_BF16) return valu_forward<bf16_t>(qkv, o, lse, Tn, C, grid, lds, (hipStream_t)stream);
-    if (dtype == C2W_DTYPE_F16) return valu_forward<f16_t>(qkv, o, lse, Tn, C, grid, lds, (hipStream_t)stream);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype(dtype, [&](auto t) { return valu_forward<decltype(t)>(qkv, o, lse, Tn, C, grid, lds, (hipStream_t)stream); });
 }
 
 extern "C" int c2w_attention_backward(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta_ws, void* dqkv, int B,
@@ -256,18 +249,19 @@ extern "C" int c2w_attention_backward(const void* qkv, const void* o, const void
     if (c2w_attention_mfma_blocks_eligible(B, Tn, C, dtype)) {  // T = 64 nb: delta over the whole row first, then the two block kernels
         const long long nrows = (long long)B * Tn;
         const int rg = (int)((nrows + 15) / 16 < 4096 ? (nrows + 15) / 16 : 4096);
-        if (dtype == C2W_DTYPE_F16) rowdot_kernel<f16_t><<<rg, 256, 0, (hipStream_t)stream>>>((const f16_t*)d_o, (const f16_t*)o, delta_ws, nrows, C);
-        else rowdot_kernel<bf16_t><<<rg, 256, 0, (hipStream_t)stream>>>((const bf16_t*)d_o, (const bf16_t*)o, delta_ws, nrows, C);
+        const int rc = c2w_by_dtype16(dtype, [&](auto t) {
+            using T = decltype(t);
+            rowdot_kernel<T><<<rg, 256, 0, (hipStream_t)stream>>>((const T*)d_o, (const T*)o, delta_ws, nrows, C);
+            return 0;
+        });
+        if (rc != 0) return rc;
         return c2w_attention_mfma_blocks_backward(qkv, d_o, lse, delta_ws, dqkv, B, Tn, C, dtype, (hipStream_t)stream);
     }
     const int lds = (TR * C + 2 * TR * Tn) * 4;
-    if (lds > 160 * 1024) return C2W_ERR_UNSUPPORTED;
+    if (lds > ATTN_LDS_MAX) return C2W_ERR_UNSUPPORTED;
     dim3 grid((Tn + TR - 1) / TR, B);
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)B * Tn;
     const int rgrid = (int)((rows + 15) / 16 < 4096 ? (rows + 15) / 16 : 4096);
-    if (dtype == C2W_DTYPE_F32) return valu_backward<float>(qkv, o, d_o, lse, delta_ws, dqkv, Tn, C, rows, grid, rgrid, lds, st);
-    if (dtype == C2W_DTYPE_BF16) return valu_backward<bf16_t>(qkv, o, d_o, lse, delta_ws, dqkv, Tn, C, rows, grid, rgrid, lds, st);
-    if (dtype == C2W_DTYPE_F16) return valu_backward<f16_t>(qkv, o, d_o, lse, delta_ws, dqkv, Tn, C, rows, grid, rgrid, lds, st);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype(dtype, [&](auto t) { return valu_backward<decltype(t)>(qkv, o, d_o, lse, delta_ws, dqkv, Tn, C, rows, grid, rgrid, lds, st); });
 }

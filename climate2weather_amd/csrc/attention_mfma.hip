@@ -14,9 +14,8 @@
 //
 // The fp32 / general-T kernels in attention.hip stay the reference implementation and the fallback.
 #include <cstdlib>
-#include "common.h"
 #include "knobs.h"
-#include "c2w_hip.h"
+#include "launch.h"
 
 namespace {
 
@@ -471,47 +470,36 @@ bool c2w_attention_mfma_eligible(int B, int Tn, int C, int dtype) {
 }
 
 namespace {
+constexpr int AM_LDS_MAX = 160 * 1024;  // the whole LDS of a CU: what the launches take grows with C, up to 151,552 B (backward, C = 512)
 template <typename T>
 int fwd_launch(const void* qkv, void* o, float* lse, int B, int C, hipStream_t st) {
     const int lds = T64 * (C * 2 + 16) + T64 * PP + 4 * 4096;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_mfma_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<attn_mfma_fwd_kernel<T>>(AM_LDS_MAX)) return rc;
     attn_mfma_fwd_kernel<T><<<B, NTA, lds, st>>>((const bf16_t*)qkv, (bf16_t*)o, lse, C, 1.0f / sqrtf((float)C));
     return (int)hipGetLastError();
 }
 template <typename T>
 int bwd_launch(const void* qkv, const void* d_o, const float* lse, void* dqkv, int B, int C, hipStream_t st) {
     const int lds = 2 * T64 * (C * 2 + 16) + 2 * T64 * PP;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_mfma_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<attn_mfma_bwd_kernel<T>>(AM_LDS_MAX)) return rc;
     attn_mfma_bwd_kernel<T><<<B, NTA, lds, st>>>((const bf16_t*)qkv, (const bf16_t*)d_o, lse, (bf16_t*)dqkv, C, 1.0f / sqrtf((float)C));
     return (int)hipGetLastError();
 }
 template <typename T>
 int blocks_launch(const void* qkv, void* o, float* lse, int B, int Tn, int C, hipStream_t st) {
     const int lds = T64 * (C * 2 + 16) + 4 * 16 * PP;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_mfma_fwd_blocks_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<attn_mfma_fwd_blocks_kernel<T>>(AM_LDS_MAX)) return rc;
     attn_mfma_fwd_blocks_kernel<T><<<dim3(Tn / T64, B), 256, lds, st>>>((const bf16_t*)qkv, (bf16_t*)o, lse, Tn, C, 1.0f / sqrtf((float)C));
     return (int)hipGetLastError();
 }
 }  // namespace
 
 int c2w_attention_mfma_forward(const void* qkv, void* o, float* lse, int B, int C, int dtype, hipStream_t st) {
-    return dtype == C2W_DTYPE_F16 ? fwd_launch<f16_t>(qkv, o, lse, B, C, st) : fwd_launch<bf16_t>(qkv, o, lse, B, C, st);
+    return c2w_by_dtype16(dtype, [&](auto t) { return fwd_launch<decltype(t)>(qkv, o, lse, B, C, st); });
 }
 
 int c2w_attention_mfma_backward(const void* qkv, const void* d_o, const float* lse, void* dqkv, int B, int C, int dtype, hipStream_t st) {
-    return dtype == C2W_DTYPE_F16 ? bwd_launch<f16_t>(qkv, d_o, lse, dqkv, B, C, st) : bwd_launch<bf16_t>(qkv, d_o, lse, dqkv, B, C, st);
+    return c2w_by_dtype16(dtype, [&](auto t) { return bwd_launch<decltype(t)>(qkv, d_o, lse, dqkv, B, C, st); });
 }
 
 // T a multiple of 64 beyond 64: forward with the online softmax over key blocks, backward in 64 x 64 blocks (two kernels)
@@ -520,7 +508,7 @@ bool c2w_attention_mfma_blocks_eligible(int B, int Tn, int C, int dtype) {
 }
 
 int c2w_attention_mfma_blocks_forward(const void* qkv, void* o, float* lse, int B, int Tn, int C, int dtype, hipStream_t st) {
-    return dtype == C2W_DTYPE_F16 ? blocks_launch<f16_t>(qkv, o, lse, B, Tn, C, st) : blocks_launch<bf16_t>(qkv, o, lse, B, Tn, C, st);
+    return c2w_by_dtype16(dtype, [&](auto t) { return blocks_launch<decltype(t)>(qkv, o, lse, B, Tn, C, st); });
 }
 
 namespace {
@@ -528,12 +516,8 @@ template <typename T>
 int blocks_bwd_launch(const void* qkv, const void* d_o, const float* lse, const float* delta, void* dqkv, int B, int Tn, int C, hipStream_t st) {
     const int VP = C * 2 + 16;
     const int lds_kv = 2 * T64 * VP + 2 * T64 * PP, lds_q = T64 * VP + 2 * T64 * PP;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_mfma_bwd_kv_blocks_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_mfma_bwd_q_blocks_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<attn_mfma_bwd_kv_blocks_kernel<T>>(AM_LDS_MAX)) return rc;
+    if (int rc = c2w_lds_optin<attn_mfma_bwd_q_blocks_kernel<T>>(AM_LDS_MAX)) return rc;
     const float scale2 = 1.0f / sqrtf((float)C);
     const dim3 grid(Tn / T64, B);
     attn_mfma_bwd_kv_blocks_kernel<T><<<grid, NTA, lds_kv, st>>>((const bf16_t*)qkv, (const bf16_t*)d_o, lse, delta, (bf16_t*)dqkv, Tn, C, scale2);
@@ -545,6 +529,5 @@ int blocks_bwd_launch(const void* qkv, const void* d_o, const float* lse, const 
 // backward of the T = 64 nb shapes: delta[row] = sum_c dO O must have been computed (attention.hip: rowdot_kernel) into `delta`
 int c2w_attention_mfma_blocks_backward(const void* qkv, const void* d_o, const float* lse, const float* delta, void* dqkv, int B, int Tn, int C,
                                        int dtype, hipStream_t st) {
-    return dtype == C2W_DTYPE_F16 ? blocks_bwd_launch<f16_t>(qkv, d_o, lse, delta, dqkv, B, Tn, C, st)
-                                  : blocks_bwd_launch<bf16_t>(qkv, d_o, lse, delta, dqkv, B, Tn, C, st);
+    return c2w_by_dtype16(dtype, [&](auto t) { return blocks_bwd_launch<decltype(t)>(qkv, d_o, lse, delta, dqkv, B, Tn, C, st); });
 }

@@ -19,8 +19,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "c2w_hip.h"
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -30,6 +29,7 @@ constexpr int CC_PROW = CC_PW * 128;        // bytes per patch row of one 64-cha
 constexpr int CC_NPIECE = 10 * 3;           // (8 + 2) patch rows x 3 pieces of 8 pixels
 constexpr int CC_PBYTES = CC_NPIECE * 1024; // 30,720
 constexpr int CC_WTILE = 16 * 128;          // one (chunk, tap) weight tile: 16 rows x 128 B
+constexpr int CC_LDS_MAX = 2 * 9 * CC_WTILE + CC_PBYTES;  // at Cin = 128, the widest c2w_conv_center_supported admits
 
 template <typename T>
 __global__ __launch_bounds__(CC_NTHR, 2) void conv_center_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
@@ -142,13 +142,9 @@ template <typename T>
 int launch(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int Cin, int wrows, int r0, int nr, long long ostride,
            hipStream_t st) {
     const int lds = (Cin / 64) * 9 * CC_WTILE + CC_PBYTES;
-    static int attr_lds = 0;
-    if (lds > attr_lds) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_center_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_lds = lds;
-    }
-    const long long tiles = (long long)B * (H >> 3) * (W >> 4);
-    const int grid = (int)(tiles < 1024 ? tiles : 1024);  // two co-resident workgroups per CU and two more queued behind them
+    if (int rc = c2w_lds_optin<conv_center_kernel<T>>(CC_LDS_MAX)) return rc;
+    const long long tiles = (long long)B * (H >> 3) * (W >> 4), cap = 4 * c2w_cu_count();
+    const int grid = (int)(tiles < cap ? tiles : cap);  // two co-resident workgroups per CU and two more queued behind them
     conv_center_kernel<T><<<grid, CC_NTHR, lds, st>>>((const T*)x, (const T*)w, bias, out, (int)tiles, H, W, Cin, wrows, r0, nr, ostride);
     return (int)hipGetLastError();
 }
@@ -164,6 +160,5 @@ extern "C" int c2w_conv_center(const void* x, const void* w, const float* bias, 
                                long long ostride, int dtype, void* stream) {
     if (!x || !w || !out || B <= 0 || r0 < 0 || r0 + nr > wrows) return C2W_ERR_BAD_ARG;
     if (!c2w_conv_center_supported(H, W, Cin, nr, dtype) || (long long)B * (H >> 3) * (W >> 4) >= (1ll << 31)) return C2W_ERR_BAD_SHAPE;
-    if (dtype == C2W_DTYPE_BF16) return launch<bf16_t>(x, w, bias, out, B, H, W, Cin, wrows, r0, nr, ostride, (hipStream_t)stream);
-    return launch<f16_t>(x, w, bias, out, B, H, W, Cin, wrows, r0, nr, ostride, (hipStream_t)stream);
+    return c2w_by_dtype16(dtype, [&](auto t) { return launch<decltype(t)>(x, w, bias, out, B, H, W, Cin, wrows, r0, nr, ostride, (hipStream_t)stream); });
 }

@@ -22,6 +22,7 @@
 
 #include "conv_epilogue.h"
 #include "knobs.h"
+#include "launch.h"
 
 namespace {
 
@@ -309,11 +310,7 @@ int launch_tile(const C2wConvArgs& a, long long npix, int nN, hipStream_t st) {
     constexpr int ESZ = sizeof(T);
     constexpr int lds_loop = NSLOT * (CF::PBYTES + WBYTES), lds_epi = CF::BM * (BN * ESZ + 16);
     constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_igemm_kernel<T, MODE, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
+    if (int rc = c2w_lds_optin<conv_igemm_kernel<T, MODE, NW>>(lds)) return rc;
     const int nM = (int)((npix + CF::BM - 1) / CF::BM);
     conv_igemm_kernel<T, MODE, NW><<<nM * nN, CF::NTHREADS, lds, st>>>(a);
     return (int)hipGetLastError();
@@ -330,7 +327,7 @@ int launch_mode(const C2wConvArgs& a, int naive, hipStream_t st) {
     }
     const int nN = (a.Cout + BN - 1) / BN;
     // 256-pixel tiles unless they would leave CUs idle (fewer workgroups than CUs): then 128-pixel tiles, twice the workgroups
-    const bool small = ((npix + 255) / 256) * nN < 256;
+    const bool small = ((npix + 255) / 256) * nN < c2w_cu_count();
     return small ? launch_tile<T, MODE, 2>(a, npix, nN, st) : launch_tile<T, MODE, 4>(a, npix, nN, st);
 }
 
@@ -487,8 +484,5 @@ extern "C" int c2w_conv_forward(const C2wConvArgs* a, int dtype, int naive, void
     if (patch && c2w_conv_ts2_patch_eligible(*a)) return c2w_conv_patch_ts2(*a, dtype, st);
     if (patch && c2w_conv_s2_patch_eligible(*a, dtype)) return c2w_conv_patch_s2(*a, dtype, st);
     if (naive == 2) naive = 0;  // force the general gather kernel
-    if (dtype == C2W_DTYPE_F32) return launch_dtype<float>(*a, naive, st);
-    if (dtype == C2W_DTYPE_BF16) return launch_dtype<bf16_t>(*a, naive, st);
-    if (dtype == C2W_DTYPE_F16) return launch_dtype<f16_t>(*a, naive, st);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype(dtype, [&](auto t) { return launch_dtype<decltype(t)>(*a, naive, st); });
 }

@@ -21,6 +21,7 @@
 
 #include "conv_epilogue.h"
 #include "knobs.h"
+#include "launch.h"
 
 namespace {
 
@@ -1119,11 +1120,7 @@ __global__ __launch_bounds__(H_NTHR, 2) void conv_patch_ts2_all_kernel(const C2w
 
 template <typename T>
 int launch_ts2_all(const C2wConvArgs& a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_ts2_all_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<conv_patch_ts2_all_kernel<T>>(H_LDS)) return rc;
     const int nN = (a.Cout + 127) / 128;
     const int nM = a.B * (a.Hin >> 3) * (a.Win >> 4);
     const int ntile = nM * nN, per_xcd = (ntile + 7) / 8;
@@ -1133,11 +1130,7 @@ int launch_ts2_all(const C2wConvArgs& a, hipStream_t st) {
 
 template <typename T>
 int launch_ts2_pairs(const C2wConvArgs& a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_ts2_pairs_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<conv_patch_ts2_pairs_kernel<T>>(H_LDS)) return rc;
     const int nN = (a.Cout + 127) / 128;
     const int nM = a.B * (a.Hin >> 3) * (a.Win >> 4);
     const int ntile = nM * nN, per_xcd = (ntile + 7) / 8;
@@ -1233,42 +1226,33 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const C2wConv
 // where there is one per CU anyway.
 template <typename T>
 static inline bool half8_wanted(long long wgs) {
-    return c2w_knobs().half8 && (sizeof(T) == 2 || wgs <= 256);
+    return c2w_knobs().half8 && (sizeof(T) == 2 || wgs <= c2w_cu_count());
 }
 
 template <typename T, bool PAIR, bool SPLITK, bool DB>
 int launch_half8_db(const C2wConvArgs& a, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_half8_kernel<T, PAIR, SPLITK, DB>, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-        attr = true;
-    }
-    conv_patch_half8_kernel<T, PAIR, SPLITK, DB><<<nwg, H8_NTHR, DB ? H8_LDS_DB : H_LDS, st>>>(a);
+    constexpr int lds = DB ? H8_LDS_DB : H_LDS;
+    if (int rc = c2w_lds_optin<conv_patch_half8_kernel<T, PAIR, SPLITK, DB>>(lds)) return rc;
+    conv_patch_half8_kernel<T, PAIR, SPLITK, DB><<<nwg, H8_NTHR, lds, st>>>(a);
     return (int)hipGetLastError();
 }
 
 // one workgroup per CU at most: the second patch buffer costs nothing (C2W_HALF8_DB=0: never)
 template <typename T, bool PAIR, bool SPLITK>
 int launch_half8(const C2wConvArgs& a, int nwg, hipStream_t st) {
-    if (nwg <= 256 && c2w_knobs().half8_db) return launch_half8_db<T, PAIR, SPLITK, true>(a, nwg, st);
+    if (nwg <= c2w_cu_count() && c2w_knobs().half8_db) return launch_half8_db<T, PAIR, SPLITK, true>(a, nwg, st);
     return launch_half8_db<T, PAIR, SPLITK, false>(a, nwg, st);
 }
 
 template <typename T, bool PAIR>
 int launch_splitk(const C2wConvArgs& a, int ntiles, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_half_kernel<T, PAIR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        attr = true;
-    }
-    int rc;
     if (half8_wanted<T>((long long)ntiles * a.splitk)) {
-        rc = launch_half8<T, PAIR, true>(a, ntiles * a.splitk, st);
+        if (int rc = launch_half8<T, PAIR, true>(a, ntiles * a.splitk, st)) return rc;
     } else {
+        if (int rc = c2w_lds_optin<conv_patch_half_kernel<T, PAIR, true>>(H_LDS)) return rc;
         conv_patch_half_kernel<T, PAIR, true><<<ntiles * a.splitk, H_NTHR, H_LDS, st>>>(a);
-        rc = (int)hipGetLastError();
+        HIP_CHECK_RET(hipGetLastError());
     }
-    if (rc != 0) return rc;
     conv_splitk_epilogue_kernel<T, PAIR><<<ntiles * (128 / (256 / (128 / (16 / (int)sizeof(T))))), 256, 0, st>>>(a, ntiles);
     return (int)hipGetLastError();
 }
@@ -1277,11 +1261,6 @@ template <typename T>
 int launch(const C2wConvArgs& a, hipStream_t st) {  // two 8x16-tile workgroups per CU
     constexpr int ESZ = sizeof(T);
     static_assert(128 * (128 * ESZ + 16) <= H_LDS, "half-tile output rows fit");
-    static bool attr_h = false;
-    if (!attr_h) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_half_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        attr_h = true;
-    }
     const int nN = (a.Cout + 127) / 128;
     const int nMh = a.B * (a.Hout >> 3) * (a.Wout >> 4);
     if (a.splitk > 1) return launch_splitk<T, false>(a, nMh * nN, st);
@@ -1290,6 +1269,7 @@ int launch(const C2wConvArgs& a, hipStream_t st) {  // two 8x16-tile workgroups 
         const int rc = launch_half8<T, false, false>(a, nMh * nN, st);
         return rc != 0 ? rc : conv_ln_dm_reduce(a, tpi, st);
     }
+    if (int rc = c2w_lds_optin<conv_patch_half_kernel<T>>(H_LDS)) return rc;
     conv_patch_half_kernel<T><<<nMh * nN, H_NTHR, H_LDS, st>>>(a);
     return conv_ln_dm_reduce(a, tpi, st);
 }
@@ -1299,15 +1279,11 @@ int launch(const C2wConvArgs& a, hipStream_t st) {  // two 8x16-tile workgroups 
 namespace {
 template <typename T>
 int launch_pair(const C2wConvArgs& a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_half_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-        attr = true;
-    }
     const int nN = (a.Cout + 127) / 128;
     const int nM = ((a.B + 1) >> 1) * (a.Hin >> 3);
     if (a.splitk > 1) return launch_splitk<T, true>(a, nM * nN, st);
     if (half8_wanted<T>((long long)nM * nN)) return launch_half8<T, true, false>(a, nM * nN, st);
+    if (int rc = c2w_lds_optin<conv_patch_half_kernel<T, true>>(H_LDS)) return rc;
     conv_patch_half_kernel<T, true><<<nM * nN, H_NTHR, H_LDS, st>>>(a);
     return (int)hipGetLastError();
 }
@@ -1328,7 +1304,7 @@ int c2w_conv_splitk_plan_impl(const C2wConvArgs& a, int dtype, unsigned long lon
     // As many workgroups per tile as keep the launch at ONE workgroup per CU (two per CU share the matrix pipe: the chain gets
     // shorter and each stage slower -- 444 workgroups of 27 stages took 31.6 us where 222 of 54 take 35.9, before the 18-us second
     // launch), at most one per chunk and 8 (the reduction's unroll).  76 tiles x 8 chunks -> 3 workgroups of 2 / 3 / 3 chunks.
-    int best = (int)(256 / (tiles > 0 ? tiles : 1));
+    int best = (int)(c2w_cu_count() / (tiles > 0 ? tiles : 1));
     if (best > nchunk) best = nchunk;
     if (best > 8) best = 8;
     if (best < 2) return 1;
@@ -1357,11 +1333,7 @@ bool c2w_conv_s2_patch_eligible(const C2wConvArgs& a, int dtype) {
 namespace {
 template <typename T, bool PAIR>
 int launch_s2(const C2wConvArgs& a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_s2_kernel<T, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<conv_patch_s2_kernel<T, PAIR>>(S2Plan<PAIR>::LDS)) return rc;
     const int nN = (a.Cout + 127) / 128;
     const int nwg = (PAIR ? ((a.B + 1) >> 1) * (a.Hout >> 3) : a.B * (a.Hout >> 3) * (a.Wout >> 4)) * nN;
     conv_patch_s2_kernel<T, PAIR><<<nwg, H8_NTHR, S2Plan<PAIR>::LDS, st>>>(a);
@@ -1370,9 +1342,7 @@ int launch_s2(const C2wConvArgs& a, hipStream_t st) {
 }  // namespace
 
 int c2w_conv_patch_s2(const C2wConvArgs& a, int dtype, hipStream_t st) {
-    if (dtype == C2W_DTYPE_BF16) return a.Wout == 8 ? launch_s2<bf16_t, true>(a, st) : launch_s2<bf16_t, false>(a, st);
-    if (dtype == C2W_DTYPE_F16) return a.Wout == 8 ? launch_s2<f16_t, true>(a, st) : launch_s2<f16_t, false>(a, st);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype16(dtype, [&](auto t) { return a.Wout == 8 ? launch_s2<decltype(t), true>(a, st) : launch_s2<decltype(t), false>(a, st); });
 }
 
 // input gradient of the stride-2 convs per output-parity class on the halo patch (conv_patch_ts2_pairs_kernel / conv_patch_ts2_all_kernel)
@@ -1383,10 +1353,7 @@ bool c2w_conv_ts2_patch_eligible(const C2wConvArgs& a) {
 }
 
 int c2w_conv_patch_ts2(const C2wConvArgs& a, int dtype, hipStream_t st) {
-    if (dtype == C2W_DTYPE_F32) return launch_ts2<float>(a, st);
-    if (dtype == C2W_DTYPE_BF16) return launch_ts2<bf16_t>(a, st);
-    if (dtype == C2W_DTYPE_F16) return launch_ts2<f16_t>(a, st);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype(dtype, [&](auto t) { return launch_ts2<decltype(t)>(a, st); });
 }
 
 // 8-pixel-wide images: two of them per 8x16 tile (conv_patch_half_kernel<T, PAIR>); no fused LayerNorm epilogues in that mode
@@ -1396,10 +1363,7 @@ bool c2w_conv_pair_eligible(const C2wConvArgs& a) {
 }
 
 int c2w_conv_patch_pair(const C2wConvArgs& a, int dtype, hipStream_t st) {
-    if (dtype == C2W_DTYPE_F32) return launch_pair<float>(a, st);
-    if (dtype == C2W_DTYPE_BF16) return launch_pair<bf16_t>(a, st);
-    if (dtype == C2W_DTYPE_F16) return launch_pair<f16_t>(a, st);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype(dtype, [&](auto t) { return launch_pair<decltype(t)>(a, st); });
 }
 
 bool c2w_conv_patch_eligible(const C2wConvArgs& a) {  // OUTPUT grids that 8 x 16-pixel tiles cover exactly; stride 1, or x2 upsampling folded in
@@ -1411,9 +1375,6 @@ bool c2w_conv_patch_eligible(const C2wConvArgs& a) {  // OUTPUT grids that 8 x 1
 
 int c2w_conv_patch_s1(const C2wConvArgs& a, int dtype, hipStream_t st) {
     if (c2w_conv_patch3_wanted(a, dtype)) return c2w_conv_patch3(a, dtype, st);
-    if (dtype == C2W_DTYPE_F32) return launch<float>(a, st);
-    if (dtype == C2W_DTYPE_BF16) return launch<bf16_t>(a, st);
-    if (dtype == C2W_DTYPE_F16) return launch<f16_t>(a, st);
-    return C2W_ERR_BAD_ARG;
+    return c2w_by_dtype(dtype, [&](auto t) { return launch<decltype(t)>(a, st); });
 }
 

@@ -31,6 +31,7 @@
 
 #include "conv_epilogue.h"
 #include "knobs.h"
+#include "launch.h"
 
 namespace {
 
@@ -414,11 +415,7 @@ __global__ __launch_bounds__(64 * NW, (T3Cfg<TR, NW>::WAVES_PER_SIMD)) void conv
 template <int TR, typename T, int NW, int EPI, bool WPK>
 int t3_launch_wpk(const C2wConvArgs& a, hipStream_t st) {
     typedef T3Cfg<TR, NW> CF;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv_patch_t3_kernel<TR, T, NW, EPI, WPK>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS));
-        attr = true;
-    }
+    if (int rc = c2w_lds_optin<conv_patch_t3_kernel<TR, T, NW, EPI, WPK>>(CF::LDS)) return rc;
     const int nN = (a.Cout + 127) / 128;
     const int nM = a.B * (a.Hout / TR) * (a.Wout >> 4);
     conv_patch_t3_kernel<TR, T, NW, EPI, WPK><<<nM * nN, CF::NTHR, CF::LDS, st>>>(a);
@@ -457,14 +454,13 @@ int t3_launch(const C2wConvArgs& a, hipStream_t st) {
 // Round 6: from 512 workgroups (one full round of two per CU) instead of 1024 -- what the 32^2 level has at the 8-GPU strong-scaling
 // batch of 64 windows per GPU (step 26.16 -> 26.00 ms) and the 64^2 level of a one-member sampler step at L = 49 (37 windows: 6.36 k ->
 // 6.64 k window-forwards/s); 256 is behind again (26.97 against 26.90 ms at B = 64).
-constexpr long long T3_MIN_WGS = 512;
 bool c2w_conv_patch3_wanted(const C2wConvArgs& a, int dtype) {
     const int mode = c2w_knobs().conv_t3;
     if ((dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16) || mode == 0 || (a.Hout & 15) != 0 || (a.Wout & 15) != 0) return false;
     const long long wgs = (long long)a.B * (a.Hout >> 4) * (a.Wout >> 4) * ((a.Cout + 127) / 128);
-    return mode == 16 || wgs >= T3_MIN_WGS;
+    return mode == 16 || wgs >= 2 * c2w_cu_count();
 }
 
 int c2w_conv_patch3(const C2wConvArgs& a, int dtype, hipStream_t st) {
-    return dtype == C2W_DTYPE_F16 ? t3_launch<16, f16_t, T3_WAVES>(a, st) : t3_launch<16, bf16_t, T3_WAVES>(a, st);
+    return c2w_by_dtype16(dtype, [&](auto t) { return t3_launch<16, decltype(t), T3_WAVES>(a, st); });
 }

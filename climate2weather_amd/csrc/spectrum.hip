@@ -4,9 +4,7 @@
 // arithmetic and the index maps; this file is the workgroup around them).  A field of N <= 32 takes 2N threads, so a workgroup of 256
 // takes 16, 8 or 4 fields; at N = 64 and 128 it takes one.  No atomics, no float sum whose order depends on the launch: a field's
 // outputs are the same bits wherever it lies in the batch.
-#include <atomic>
-#include "common.h"
-#include "c2w_hip.h"
+#include "launch.h"
 
 #define SPEC_HD __device__ __forceinline__
 #define SPEC_TABLE static __device__ const
@@ -54,22 +52,13 @@ __global__ __launch_bounds__(256) void rapsd_kernel(const float* __restrict__ x,
     if (live) phase_store<N>(v, tl);
 }
 
-constexpr int SPEC_MAX_DEVICES = 64;
-
-// The N = 128 image is 66 KiB: above the static limit, so the kernel needs the dynamic-LDS opt-in -- once per DEVICE (the attribute is
-// a property of the function on a device).  Two threads racing here both set it before either launches: harmless.
+// The N = 128 image is 66 KiB: above the static limit, so the kernel needs the dynamic-LDS opt-in.
 template <int N>
 int rapsd_launch(const float* x, float* spec, long long n_fields, hipStream_t st) {
     using P = Plan<N>;
     constexpr size_t lds = P::lds_bytes();
-    if (lds > 48 * 1024) {
-        static std::atomic<bool> opted[SPEC_MAX_DEVICES];
-        int dev = 0;
-        HIP_CHECK_RET(hipGetDevice(&dev));
-        if (dev < 0 || dev >= SPEC_MAX_DEVICES || !opted[dev].load(std::memory_order_acquire)) {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)rapsd_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < SPEC_MAX_DEVICES) opted[dev].store(true, std::memory_order_release);
-        }
+    if constexpr (lds > 48 * 1024) {
+        if (int rc = c2w_lds_optin<rapsd_kernel<N>>((int)lds)) return rc;
     }
     const long long grid = (n_fields + P::FPW - 1) / P::FPW;
     if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;

@@ -3,8 +3,7 @@
 // directions with the normalisation applied to the loaded value; swd_distance_kernel sorts one column pair per workgroup in LDS and
 // writes one double.  swd_core.h has the index maps and the arithmetic; this file is the workgroups around them.  No atomics, no
 // scratch, no sum whose order depends on the launch.
-#include "common.h"
-#include "c2w_hip.h"
+#include "launch.h"
 
 #define SWD_HD __device__ __attribute__((always_inline))
 #define SWD_BOTH __host__ __device__ __attribute__((always_inline))
@@ -102,8 +101,7 @@ extern "C" int c2w_swd_distance(const float* proj_x, const float* proj_y, double
     if (grid == 0) return 0;
     if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
     const int N = swd::padded(T), lds = 2 * N * (int)sizeof(float);
-    // above the static limit: the opt-in is a property of the function on a device, so it is set with every launch (no state here)
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)swd_distance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * MAX_T * (int)sizeof(float)));
+    if (int rc = c2w_lds_optin<swd_distance_kernel>(2 * MAX_T * (int)sizeof(float))) return rc;  // above the static limit at the largest T
     swd_distance_kernel<<<(unsigned)grid, swd::sort_threads(N), lds, (hipStream_t)stream>>>(proj_x, proj_y, out, F, P, T, N);
     return (int)hipGetLastError();
 }

@@ -17,6 +17,7 @@
 
 #include "conv_geom.h"
 #include "knobs.h"
+#include "launch.h"
 
 namespace {
 
@@ -476,11 +477,7 @@ int launch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_t ws_byte
     constexpr int lds_main = NSLOT * (ABYTES + BBYTES);
     constexpr int lds_epi = COT * (4 * CIB + 4) * 4;
     constexpr int lds = lds_main > lds_epi ? lds_main : lds_epi;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)wgrad_kernel<T, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
+    if (int rc = c2w_lds_optin<wgrad_kernel<T, MODE>>(lds)) return rc;
     const size_t need = (size_t)p.nsplit * tilesMN * COT * 4 * CIB * sizeof(float);
     p.det = (a.flags & C2W_CONV_DETERMINISTIC) ? 1 : 0;
     if (p.det) {  // never a silent fall-back to atomics: the knob is refused, the workspace must be what c2w_conv_wgrad_workspace_bytes asks for
@@ -564,11 +561,7 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
     constexpr int lds_main = NSLOT * (ABYTES + BBYTES);
     constexpr int lds_epi = COT * (4 * CIB + 4) * 4;
     constexpr int lds = lds_main > lds_epi ? lds_main : lds_epi;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)wgrad_group_kernel<T, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
+    if (int rc = c2w_lds_optin<wgrad_group_kernel<T, MODE>>(lds)) return rc;
     wgrad_group_kernel<T, MODE><<<g.live_per_item * n, NTHREADS, lds, st>>>(g);
     if (p.ws != nullptr) {
         const size_t per4 = (size_t)tilesMN * COT * 4 * CIB / 4;
@@ -606,9 +599,7 @@ extern "C" int c2w_conv_wgrad(const C2wConvArgs* a, float* dw, float* dbias, voi
     float* ws = (float*)workspace;
     const size_t wsb = workspace == nullptr ? 0 : (size_t)workspace_bytes;
     if (c2w_wgrad_patch_eligible(*a) && !c2w_knobs().force_gather) return c2w_wgrad_patch(*a, dw, dbias, ws, wsb, dtype, st);
-    if (dtype == C2W_DTYPE_F32) return launch_dtype<float>(*a, dw, dbias, ws, wsb, st);
-    if (dtype == C2W_DTYPE_BF16) return launch_dtype<bf16_t>(*a, dw, dbias, ws, wsb, st);
-    return launch_dtype<f16_t>(*a, dw, dbias, ws, wsb, st);
+    return c2w_by_dtype(dtype, [&](auto t) { return launch_dtype<decltype(t)>(*a, dw, dbias, ws, wsb, st); });
 }
 
 // the 1x1 layers (Conv1d(k = 1) / Linear: model/nn.py:45,47) group on the gather kernel
@@ -642,9 +633,7 @@ extern "C" int c2w_conv_wgrad_grouped(const C2wConvArgs* a, const C2wWgradItem* 
     const size_t wsb = workspace == nullptr ? 0 : (size_t)workspace_bytes;
     hipStream_t st = (hipStream_t)stream;
     if (c2w_wgrad_patch_group_eligible(*a, n, dtype) && !c2w_knobs().force_gather) return c2w_wgrad_patch_group(*a, items, n, ws, wsb, dtype, st);
-    if (dtype == C2W_DTYPE_F32) return launch_group<float, C2W_CONV_1X1>(*a, items, n, ws, wsb, st);
-    if (dtype == C2W_DTYPE_BF16) return launch_group<bf16_t, C2W_CONV_1X1>(*a, items, n, ws, wsb, st);
-    return launch_group<f16_t, C2W_CONV_1X1>(*a, items, n, ws, wsb, st);
+    return c2w_by_dtype(dtype, [&](auto t) { return launch_group<decltype(t), C2W_CONV_1X1>(*a, items, n, ws, wsb, st); });
 }
 
 extern "C" int c2w_conv_wgrad_dispatch(const C2wConvArgs* a, int dtype) {

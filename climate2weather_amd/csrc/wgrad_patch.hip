@@ -21,6 +21,7 @@
 #include "conv_geom.h"
 
 #include "knobs.h"
+#include "launch.h"
 // (schedule variants measured and rejected -- burst LDS-DMA issue, fragments one tap ahead, carried kh = 2 fragments -- and the ablation
 // builds live in lab/csrc/wgrad_patch_lab.hip; results in profiles/r02_experiments.md section 1)
 
@@ -554,16 +555,15 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const WpGroupAr
     wgrad_reduce_body<COT, CIB>(g.c.ws + (size_t)it * g.ws_item_floats, e.dw, nsplit, tilesMN, ncib, g.c.Cin, g.c.Cout, br.nmain);
 }
 
-// split of the K (pixel-tile) range over workgroups: one resident workgroup per CU and ONE round: tilesMN * nsplit <= 256 (rounding
-// up gave 270 workgroups for 384 -> 384 -- a second round for 14 of them: 155 us instead of one round's ~90 at 16x16); every workgroup
-// costs 295 KB of partial sums
-constexpr int WGRAD_WGS = 256;  // one per CU
+// split of the K (pixel-tile) range over workgroups: one resident workgroup per CU and ONE round: tilesMN * nsplit <= the CU count
+// (rounding up gave 270 workgroups for 384 -> 384 on 256 CUs -- a second round for 14 of them: 155 us instead of one round's ~90 at
+// 16x16); every workgroup costs 295 KB of partial sums
 template <int ESZ, bool PAIR>
 static void split_plan(const C2wConvArgs& a, int& ktiles, int& tilesMN, int& nsplit, int& ktiles_per_split) {
     constexpr int COT = 256 / ESZ, CIB = 128 / ESZ;
     ktiles = PAIR ? ((a.B + 1) >> 1) * (a.Hout >> 3) : a.B * (a.Hout >> 3) * (a.Wout >> 4);
     tilesMN = ((a.Cout + COT - 1) / COT) * (a.Cin / CIB);
-    nsplit = WGRAD_WGS / tilesMN;
+    nsplit = c2w_cu_count() / tilesMN;
     if (nsplit > ktiles) nsplit = ktiles;
     if (nsplit < 1) nsplit = 1;
     ktiles_per_split = (ktiles + nsplit - 1) / nsplit;
@@ -589,11 +589,7 @@ int launch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_t ws_byte
     p.up = a.mode == C2W_CONV_UP ? 1 : 0;
     int tilesMN, nsplit;
     split_plan<ESZ, PAIR>(a, p.ktiles, tilesMN, nsplit, p.ktiles_per_split);
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)wgrad_patch_kernel<T, PAIR, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_set = true;
-    }
+    if (int rc = c2w_lds_optin<wgrad_patch_kernel<T, PAIR, NARROW>>(LDS_BYTES)) return rc;
     const size_t need = (size_t)nsplit * tilesMN * 9 * COT * CIB * sizeof(float);
     const int bias_cols = (tilesMN / (a.Cin / CIB)) * COT;
     p.det = (a.flags & C2W_CONV_DETERMINISTIC) ? 1 : 0;
@@ -616,21 +612,21 @@ int launch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_t ws_byte
 }
 
 // ---- grouped launches.  Split plan for n layers of one geometry (T = n * tilesMN output tiles, each `ktiles` K tiles deep): the number
-// of splits that minimises  rounds x (K tiles per workgroup x t_k + t_fixed) + reduction launch  over 1 ... 4 rounds of 256 workgroups,
+// of splits that minimises  rounds x (K tiles per workgroup x t_k + t_fixed) + reduction launch  over 1 ... 4 rounds of one workgroup per CU,
 // with t_k = 4.1 us per K tile at the clock the chip holds under this kernel and t_fixed = 16 us (prologue + a 295-KB tile added onto dw)
 // or 28 us (partial sums stored and read again) -- the two constants reproduce the per-layer launches of the default network within 10 %
 // (71 / 116 / 169 / 169 / 563 us predicted at the 8x8 ... 128x128 levels against 68 / 105 / 153 / 162 / 568 measured, round 4).
 static void group_plan(int n, int tilesMN, int ktiles, int& nsplit, int& ktiles_per_split) {
-    const int T = n * tilesMN;
+    const int T = n * tilesMN, cus = c2w_cu_count();
     double best = 1e30;
     nsplit = 1;
     for (int r = 0; r <= 4; ++r) {  // r = 0: no split at all, whatever the number of rounds
-        int ns = r == 0 ? 1 : (256 * r) / T;
+        int ns = r == 0 ? 1 : (cus * r) / T;
         if (ns < 1) ns = 1;
         if (ns > ktiles) ns = ktiles;
         const int per = (ktiles + ns - 1) / ns;
         ns = (ktiles + per - 1) / per;
-        const int rounds = (T * ns + 255) / 256;
+        const int rounds = (T * ns + cus - 1) / cus;
         const double cost = rounds * (per * 4.1 + (ns > 1 ? 28.0 : 16.0)) + (ns > 1 ? 10.0 : 0.0);
         if (cost < best - 1e-9) {
             best = cost;
@@ -678,11 +674,7 @@ int launch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* 
         const C2wWgradItem& e = items[i < n ? i : n - 1];
         g.item[i].dy = e.dy; g.item[i].x = e.x; g.item[i].dw = e.dw; g.item[i].db = e.dbias;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)wgrad_patch_group_kernel<T, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_set = true;
-    }
+    if (int rc = c2w_lds_optin<wgrad_patch_group_kernel<T, PAIR>>(LDS_BYTES)) return rc;
     wgrad_patch_group_kernel<T, PAIR><<<g.live_per_item * n, NTHREADS, LDS_BYTES, st>>>(g);
     if (p.ws != nullptr) {
         const size_t per_split = (size_t)tilesMN * 9 * COT * CIB;
@@ -703,16 +695,8 @@ bool c2w_wgrad_patch_group_eligible(const C2wConvArgs& a, int n, int dtype) {
 }
 
 int c2w_wgrad_patch_group(const C2wConvArgs& a, const C2wWgradItem* items, int n, float* ws, size_t ws_bytes, int dtype, hipStream_t st) {
-    if (c2w_wgrad_patch_pair(a)) {
-        if (dtype == C2W_DTYPE_F32) return launch_group<float, true>(a, items, n, ws, ws_bytes, st);
-        if (dtype == C2W_DTYPE_BF16) return launch_group<bf16_t, true>(a, items, n, ws, ws_bytes, st);
-        if (dtype == C2W_DTYPE_F16) return launch_group<f16_t, true>(a, items, n, ws, ws_bytes, st);
-        return C2W_ERR_BAD_ARG;
-    }
-    if (dtype == C2W_DTYPE_F32) return launch_group<float, false>(a, items, n, ws, ws_bytes, st);
-    if (dtype == C2W_DTYPE_BF16) return launch_group<bf16_t, false>(a, items, n, ws, ws_bytes, st);
-    if (dtype == C2W_DTYPE_F16) return launch_group<f16_t, false>(a, items, n, ws, ws_bytes, st);
-    return C2W_ERR_BAD_ARG;
+    if (c2w_wgrad_patch_pair(a)) return c2w_by_dtype(dtype, [&](auto t) { return launch_group<decltype(t), true>(a, items, n, ws, ws_bytes, st); });
+    return c2w_by_dtype(dtype, [&](auto t) { return launch_group<decltype(t), false>(a, items, n, ws, ws_bytes, st); });
 }
 
 size_t c2w_wgrad_patch_group_ws_bytes(const C2wConvArgs& a, int n, int dtype) {
@@ -732,17 +716,10 @@ bool c2w_wgrad_patch_eligible(const C2wConvArgs& a) {
 }
 
 int c2w_wgrad_patch(const C2wConvArgs& a, float* dw, float* db, float* ws, size_t ws_bytes, int dtype, hipStream_t st) {
-    if (c2w_wgrad_patch_pair(a)) {
-        if (dtype == C2W_DTYPE_F32) return launch<float, true>(a, dw, db, ws, ws_bytes, st);
-        if (dtype == C2W_DTYPE_BF16) return launch<bf16_t, true>(a, dw, db, ws, ws_bytes, st);
-        if (dtype == C2W_DTYPE_F16) return launch<f16_t, true>(a, dw, db, ws, ws_bytes, st);
-        return C2W_ERR_BAD_ARG;
-    }
-    if (dtype == C2W_DTYPE_F32) return launch<float, false>(a, dw, db, ws, ws_bytes, st);
-    const bool narrow = a.Cout <= 80;  // the output conv (65 channels)
-    if (dtype == C2W_DTYPE_BF16) return narrow ? launch<bf16_t, false, true>(a, dw, db, ws, ws_bytes, st) : launch<bf16_t, false>(a, dw, db, ws, ws_bytes, st);
-    if (dtype == C2W_DTYPE_F16) return narrow ? launch<f16_t, false, true>(a, dw, db, ws, ws_bytes, st) : launch<f16_t, false>(a, dw, db, ws, ws_bytes, st);
-    return C2W_ERR_BAD_ARG;
+    if (c2w_wgrad_patch_pair(a)) return c2w_by_dtype(dtype, [&](auto t) { return launch<decltype(t), true>(a, dw, db, ws, ws_bytes, st); });
+    if (dtype != C2W_DTYPE_F32 && a.Cout <= 80)  // the output conv (65 channels): the narrow form, 16-bit only
+        return c2w_by_dtype16(dtype, [&](auto t) { return launch<decltype(t), false, true>(a, dw, db, ws, ws_bytes, st); });
+    return c2w_by_dtype(dtype, [&](auto t) { return launch<decltype(t), false>(a, dw, db, ws, ws_bytes, st); });
 }
 
 size_t c2w_wgrad_patch_ws_bytes(const C2wConvArgs& a, int dtype) {

@@ -35,6 +35,12 @@ def _stream():
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
 
 
+def _geom_args(g: dict) -> ConvArgs:
+    """The geometry alone (every pointer NULL, no epilogue): what the query entry points read."""
+    return ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
+                    g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
+
+
 def _conv_args(x, w, bias, res, mul, y, g, act, mulmode, y2=None, ln=None, lnf=None, resn=None) -> ConvArgs:
     a = ConvArgs(_p(x), _p(w), _p(bias), _p(res), _p(mul), _p(y), _p(y2), g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"],
                  g["Cout"], g["ldy"], g["wrows"], g["mode"], act, mulmode)
@@ -85,9 +91,7 @@ def conv(x, w, bias, y, g: dict, dtype: int, act: int = ACT_NONE, res=None, mul=
 
 def conv_wpacked_supported(g: dict, dtype: int) -> bool:
     """True when c2w_conv_forward takes this geometry with stage-major packed weights (it goes to the 16x16-tile kernel)."""
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
-    return bool(_lib.load().c2w_conv_wpacked_supported(ctypes.byref(a), dtype))
+    return bool(_lib.load().c2w_conv_wpacked_supported(ctypes.byref(_geom_args(g)), dtype))
 
 
 def packed_conv_weights_numel(rows: int, cin: int) -> int:
@@ -112,21 +116,15 @@ def knobs_reload() -> None:
 
 
 def conv_patch_supported(g: dict, dtype: int) -> bool:
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
-    return bool(_lib.load().c2w_conv_patch_supported(ctypes.byref(a), dtype))
+    return bool(_lib.load().c2w_conv_patch_supported(ctypes.byref(_geom_args(g)), dtype))
 
 
 def conv_pool2_supported(g: dict, dtype: int) -> bool:
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
-    return bool(_lib.load().c2w_conv_pool2_supported(ctypes.byref(a), dtype))
+    return bool(_lib.load().c2w_conv_pool2_supported(ctypes.byref(_geom_args(g)), dtype))
 
 
 def conv_lnfwd_supported(g: dict, dtype: int) -> bool:
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
-    return bool(_lib.load().c2w_conv_lnfwd_supported(ctypes.byref(a), dtype))
+    return bool(_lib.load().c2w_conv_lnfwd_supported(ctypes.byref(_geom_args(g)), dtype))
 
 
 def conv_splitk_plan(g: dict, dtype: int, act: int = ACT_NONE) -> tuple:
@@ -168,15 +166,12 @@ def conv_det_scratch_bytes(g: dict, dtype: int, ln_ldm: Optional[int] = None, lo
 
 
 def conv_lnbwd_supported(g: dict, dtype: int) -> bool:
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
-    return bool(_lib.load().c2w_conv_lnbwd_supported(ctypes.byref(a), dtype))
+    return bool(_lib.load().c2w_conv_lnbwd_supported(ctypes.byref(_geom_args(g)), dtype))
 
 
 def conv_dispatch(g: dict, dtype: int, pool2: bool = False, fused_ln: bool = False) -> int:
     """Kernel family (``_lib.KERNEL_*``) c2w_conv_forward runs this geometry on; ``fused_ln``: with a LayerNorm epilogue requested."""
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
+    a = _geom_args(g)
     if pool2:
         a.flags = _lib.CONV_POOL2
     if fused_ln:
@@ -185,8 +180,7 @@ def conv_dispatch(g: dict, dtype: int, pool2: bool = False, fused_ln: bool = Fal
 
 
 def conv_wgrad_dispatch(g: dict, dtype: int) -> int:
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
+    a = _geom_args(g)
     rc = int(_lib.load().c2w_conv_wgrad_dispatch(ctypes.byref(a), dtype))
     if rc < 0:
         check(rc, "c2w_conv_wgrad_dispatch")
@@ -208,19 +202,13 @@ def conv_wgrad(x, dy, dw, g: dict, dtype: int, dbias=None, workspace: Optional[t
 
 
 def conv_wgrad_workspace_bytes(g: dict, dtype: int, deterministic: bool = False) -> int:
-    a = ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                 g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
+    a = _geom_args(g)
     if deterministic:
         a.flags = _lib.CONV_DETERMINISTIC
     n = int(_lib.load().c2w_conv_wgrad_workspace_bytes(ctypes.byref(a), dtype))
     if n < 0:
         check(n, "c2w_conv_wgrad_workspace_bytes")
     return n
-
-
-def _geom_args(g: dict):
-    return ConvArgs(None, None, None, None, None, None, None, g["B"], g["Hin"], g["Win"], g["Cin"], g["Hout"], g["Wout"], g["Cout"], g["ldy"],
-                    g["wrows"], g["mode"], ACT_NONE, MUL_PLAIN)
 
 
 def conv_wgrad_grouped_supported(g: dict, n: int, dtype: int) -> bool:
