@@ -479,6 +479,64 @@ def swd_distance(proj_x, proj_y, out, n_rep, F, P, T) -> bool:
     return True
 
 
+def kde_supported(hw: int, N: int) -> bool:
+    return bool(_lib.load().c2w_kde_supported(hw, N))
+
+
+def kde_scratch_bytes(D: int, n: int, N: int) -> int:
+    """bytes of scratch ``kde_eval`` needs for D data sets of n values at N grid points (a function of these three alone)"""
+    return int(_lib.load().c2w_kde_scratch_bytes(D, n, N))
+
+
+def kde_eval(x, y, offsets, pivot, h, scratch, dens, n_rep, T, F, hw, N) -> bool:
+    """dens (n_rep F + F, N) float64 = the Gaussian kernel density estimate of every (member, variable) of x (n_rep, T, F, hw) and every
+    (truth, variable) of y (T, F, hw) -- dense fp32, 16-byte aligned; y None: x only, n_rep F rows -- at the grid points pivot[f] +
+    offsets[f, j] (device fp32 tensors (F,) and (F, N)) with the bandwidths h (device float64, one per row of dens)
+    (include/c2w_hip.h::c2w_kde_eval: the definition, the pivot, the fixed summation order).  scratch: a float64 device tensor of at
+    least ``kde_scratch_bytes`` bytes.  False if hw or N is not supported -- nothing is written and the caller takes the general
+    definition (marginals.gaussian_kde)."""
+    rc = _lib.load().c2w_kde_eval(_p(x), _p(y), _p(offsets), _p(pivot), _p(h), _p(scratch), scratch.numel() * scratch.element_size(), _p(dens),
+                                  n_rep, T, F, hw, N, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_kde_eval")
+    return True
+
+
+def kde_partial(x, y, offsets, pivot, h, scratch, n_rep, T, F, hw, N) -> bool:
+    """the first launch of ``kde_eval`` alone: the chunk sums into scratch (include/c2w_hip.h::c2w_kde_partial)"""
+    rc = _lib.load().c2w_kde_partial(_p(x), _p(y), _p(offsets), _p(pivot), _p(h), _p(scratch), scratch.numel() * scratch.element_size(), n_rep, T, F,
+                                     hw, N, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_kde_partial")
+    return True
+
+
+def kde_fold(scratch, h, dens, D, n, N) -> bool:
+    """the second launch of ``kde_eval`` alone: dens (D, N) from the chunk sums in scratch (include/c2w_hip.h::c2w_kde_fold)"""
+    rc = _lib.load().c2w_kde_fold(_p(scratch), _p(h), _p(dens), D, n, N, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_kde_fold")
+    return True
+
+
+def pit_supported(hw: int, M: int) -> bool:
+    return bool(_lib.load().c2w_pit_supported(hw, M))
+
+
+def pit_counts(x, y, counts, M, T, F, hw) -> bool:
+    """counts (F, M + 1) int64 = per variable the number of (time, cell) at which exactly r of the M members x (M, T, F, hw) are <= the
+    truth y (T, F, hw) (dense fp32, 16-byte aligned; include/c2w_hip.h::c2w_pit_counts).  The call zeroes counts first.  False if hw or
+    M is not supported -- nothing is written."""
+    rc = _lib.load().c2w_pit_counts(_p(x), _p(y), _p(counts), M, T, F, hw, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_pit_counts")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

@@ -407,6 +407,49 @@ int c2w_swd_project(const float* x, const float* theta, const float* shift, cons
 int c2w_swd_project_pair(const float* x, const float* y, const float* theta, const float* shift, const float* scale, float* proj_x,
                          float* proj_y, long long n_rep, int T, int F, int d, int P, void* stream);
 int c2w_swd_distance(const float* proj_x, const float* proj_y, double* out, long long n_rep, int F, int P, int T, void* stream);
+/* Ensemble marginals and calibration (exp/figures.py:23-241, kde_and_pmf): the Gaussian kernel density estimate of every member's and the
+ * truth's values per variable (:52-80, scipy.stats.gaussian_kde with its defaults, evaluated at N = 1000 points), and the rank
+ * histogram of the truth within the ensemble (:86, :178-192).  The KDE formula below is VERIFIED against scipy.stats.gaussian_kde
+ * (tests/test_kde_cpu.py prints the agreement); the rank count is the reference's own line of numpy.
+ *   KDE   f(g) = (1 / (n h sqrt(2 pi))) * sum_i exp(-(g - x_i)^2 / (2 h^2)),  h = factor * std(x, ddof = 1), factor = n^(-1/5) (Scott,
+ *         scipy's default), (3 n / 4)^(-1/5) for "silverman", or a number taken as the factor itself (the caller's:
+ *         climate2weather_amd.marginals.bandwidth).  One data set is one (member, variable) or (truth, variable) over all T times and
+ *         hw cells, n = T hw, and every data set has its own h.  The report's grid per variable is linspace(min(truth.min,
+ *         samples.min), max(truth.max, samples.max), N) in float64 (the caller's).
+ *   PIT   r = #{m : sample_m <= truth} per (time, variable, cell) with IEEE <=: ties count, a NaN on either side compares false;
+ *         counts[f][r], r = 0 .. M.  The reference's PIT value is r / M, its density=True histogram counts * M / counts.sum().
+ * c2w_kde_eval: dens[D][N] double for the D = n_rep F (+ F with y) data sets of x[n_rep][T][F][hw] and of the truth y[T][F][hw] (dense
+ * fp32, 16-byte aligned; y == NULL: x only) in ONE launch pair; data set ds < n_rep F is member ds / F, variable ds % F, the rest are
+ * the truth's variables; h[D] DEVICE doubles in that order.  Numerics: the grid arrives as fp32 offsets[F][N] = g_j - pivot[f],
+ * computed in float64 and rounded once, from an fp32 pivot[f] near the middle of variable f's grid (both DEVICE arrays); the kernel
+ * forms x - pivot in fp32 ON THE LOADED VALUE, before anything else touches it -- exact whenever x and the pivot lie within a factor
+ * of two of each other.  A pressure field lies at 101325 +- 1200 and with n in the millions h is a few tens: a float64 grid point
+ * rounded to fp32 moves by up to 0.004, 1e-4 of h, several 1e-4 relative in a tail term -- never evaluate g - x on raw fp32 values.
+ * exp(-u^2 / 2) = exp2(-((g - x) k)^2), k = sqrt(log2(e) / 2) / h rounded to fp32 once per data set: per pair one fma (against g k,
+ * formed in double and rounded once per grid point), one multiply, one v_exp_f32 (terms below 2^-126 flush to zero), one add.
+ * Dense and exact: no pair is dropped, no truncation radius.  kde_partial_kernel: a workgroup owns one data set and one chunk of its
+ * values, a thread up to four grid points as fp32 accumulators; a chain holds at most 256 terms before it joins a double, in value
+ * order; a chunk's N doubles go to scratch as partial[D][chunks][N].  The chunk length is a function of n alone (n / 64 rounded up to
+ * whole tiles of 1024 values), not of D or of the device: dens[ds] is the same bits whatever else rides in the launch and wherever
+ * the data set lies in it.  kde_fold_kernel adds the chunks in index order and multiplies by 1 / (n h sqrt(2 pi)), both in double.
+ * No atomics.  A NaN or inf value makes its data set's whole row NaN, written explicitly, and touches no other row; n < 2 or zero
+ * spread (h NaN or 0) gives a NaN row as the formula does.  scratch: c2w_kde_scratch_bytes(D, T hw, N) bytes, 8-byte aligned, every
+ * byte of it written before it is read.  Supported: hw a multiple of 4, 1 <= N <= 1024.  c2w_kde_partial and c2w_kde_fold are the two
+ * launches of c2w_kde_eval on their own (the same bits), for a caller that times or schedules them apart.
+ * c2w_pit_counts: counts[F][M + 1] int64 (zeroed by the call, on the stream) from x[M][T][F][hw] against y[T][F][hw] (dense fp32,
+ * 16-byte aligned).  pit_count_kernel: a workgroup stays inside one variable's (t, f) planes, reads the truth with 16-byte loads and
+ * the M members at stride T F hw, counts per cell in registers, bins in an LDS histogram and issues one global integer add per
+ * (workgroup, bin) -- integer sums are exact in any order.  Supported: hw a multiple of 4, 1 <= M <= 64.
+ * Everything unsupported returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_kde_supported(int hw, int N); /* 1 or 0 */
+long long c2w_kde_scratch_bytes(long long D, long long n, int N);
+int c2w_kde_eval(const float* x, const float* y, const float* offsets, const float* pivot, const double* h, double* scratch,
+                 unsigned long long scratch_bytes, double* dens, long long n_rep, int T, int F, int hw, int N, void* stream);
+int c2w_kde_partial(const float* x, const float* y, const float* offsets, const float* pivot, const double* h, double* scratch,
+                    unsigned long long scratch_bytes, long long n_rep, int T, int F, int hw, int N, void* stream);
+int c2w_kde_fold(const double* scratch, const double* h, double* dens, long long D, long long n, int N, void* stream);
+int c2w_pit_supported(int hw, int M); /* 1 or 0 */
+int c2w_pit_counts(const float* x, const float* y, long long* counts, int M, int T, int F, int hw, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
