@@ -113,6 +113,10 @@ _PROTOS = {
     "c2w_kde_fold": [c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_int, c_void_p],
     "c2w_pit_supported": [c_int, c_int],
     "c2w_pit_counts": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_quantile_supported": [c_int, c_int],
+    "c2w_quantile_scratch_bytes": [c_longlong, c_int],
+    "c2w_quantiles": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_ulonglong, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int,
+                      c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

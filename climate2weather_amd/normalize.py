@@ -1,7 +1,8 @@
 """Quantile (de)normalisation either side of the sampler (``data/pipeline.py:183-244`` applied at
 ``exp/downscaling.py:150,188,198,274``).  The reference does it in xarray on the host; every mode is a per-variable
 affine map, so on an ``(L, F, H, W)`` trajectory that already lives in HBM it is one streaming kernel
-(``c2w_affine_channels``).  netCDF / quantile-file I/O stays with the caller: pass the quantile values."""
+(``c2w_affine_channels``).  netCDF / quantile-file I/O stays with the caller: pass the quantile values, or let
+``QuantileNormalizer.from_data`` compute them from the fields (``climate2weather_amd.quantiles``)."""
 from __future__ import annotations
 
 from typing import Dict, Sequence
@@ -31,6 +32,22 @@ class QuantileNormalizer:
         self.lower = torch.as_tensor(quantiles[sub], dtype=torch.float64).reshape(-1)
         self.range = (torch.as_tensor(quantiles[hi], dtype=torch.float64) - torch.as_tensor(quantiles[lo], dtype=torch.float64)).reshape(-1)
         self._dev = {}
+
+    @classmethod
+    def from_data(cls, x: torch.Tensor, mode: str = "quant95", skipna: bool = True) -> "QuantileNormalizer":
+        """The normaliser of the data itself: ``x (..., T, F, H, W)``, any float dtype, on any device; the levels ``MODES[mode]`` needs
+        are computed per variable over everything but F (``data/xarray_preproc.py::compute_quantiles`` over time, rlat and rlon) by
+        ``quantiles.quantile`` -- on the GPU by the radix-select kernels, without a host sync -- and equal ``numpy.quantile`` of the
+        same values.  ``skipna``: leave NaNs out (the default) or let one make its variable's constants NaN."""
+        from . import quantiles
+        if mode not in MODES:
+            raise ValueError(f"Invalid mode: {mode}")
+        if x.dim() < 4:
+            raise ValueError(f"expected (..., T, F, H, W), got {tuple(x.shape)}")
+        x = x.reshape((-1,) + tuple(x.shape[-3:]))  # leading indices join the time axis: one data set per variable
+        levels = sorted(set(MODES[mode]))
+        values = quantiles.quantile(x, levels, skipna=skipna)  # (F, Q) float64
+        return cls({level: values[:, j] for j, level in enumerate(levels)}, mode)
 
     def _coef(self, device, inverse: bool):
         key = (str(device), inverse)

@@ -537,6 +537,31 @@ def pit_counts(x, y, counts, M, T, F, hw) -> bool:
     return True
 
 
+def quantile_supported(hw: int, Q: int) -> bool:
+    return bool(_lib.load().c2w_quantile_supported(hw, Q))
+
+
+def quantile_scratch_bytes(D: int, Q: int) -> int:
+    """bytes of scratch ``quantiles`` needs for D data sets and Q levels (a function of these two alone)"""
+    return int(_lib.load().c2w_quantile_scratch_bytes(D, Q))
+
+
+def quantiles(x, y, q, skipna, scratch, out, stats, n_valid, n_rep, T, F, hw) -> bool:
+    """out (n_rep F + F, Q) float64, stats (.., Q, 2) fp32 and n_valid (..,) int64 = the quantiles at the levels q (a sequence of Q host
+    floats in [0, 1]), the two order statistics each is interpolated from and the number of non-NaN values of every (member, variable)
+    of x (n_rep, T, F, hw) and every (truth, variable) of y (T, F, hw) -- dense fp32, 16-byte aligned; y None: x only
+    (include/c2w_hip.h::c2w_quantiles: the definition, the radix select).  scratch: a device tensor of at least
+    ``quantile_scratch_bytes`` bytes, 16-byte aligned.  False if hw or Q is not supported -- nothing is written and the caller takes
+    the general definition (quantiles.quantile)."""
+    levels = (ctypes.c_double * len(q))(*[float(v) for v in q])
+    rc = _lib.load().c2w_quantiles(_p(x), _p(y), ctypes.cast(levels, ctypes.c_void_p), len(q), int(bool(skipna)), _p(scratch),
+                                   scratch.numel() * scratch.element_size(), _p(out), _p(stats), _p(n_valid), n_rep, T, F, hw, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_quantiles")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

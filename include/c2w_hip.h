@@ -450,6 +450,38 @@ int c2w_kde_partial(const float* x, const float* y, const float* offsets, const 
 int c2w_kde_fold(const double* scratch, const double* h, double* dens, long long D, long long n, int N, void* stream);
 int c2w_pit_supported(int hw, int M); /* 1 or 0 */
 int c2w_pit_counts(const float* x, const float* y, long long* counts, int M, int T, int F, int hw, void* stream);
+/* Exact quantiles on the device (data/xarray_preproc.py::compute_quantiles: xds.quantile(levels, dim=["time", "rlat", "rlon"]) per
+ * variable, the constants data/pipeline.py::normalize_ds scales by; evaluated per ensemble member they are the tail diagnostic).
+ * Definition.  A data set is every value of one variable, indexed as for c2w_kde_eval: data set d = rep * F + f is x[rep][t][f][:] for
+ * all t < T; with a truth y[T][F][hw] its F data sets follow as d = n_rep * F + f; D data sets in all, n = T * hw values each, dense
+ * fp32.  For data set d and level q in [0, 1]:
+ *   1. nv = the number of non-NaN values
+ *   2. v = (nv - 1) * q in float64
+ *   3. lo = floor(v), hi = min(lo + 1, nv - 1), t = v - lo
+ *   4. a, b = the lo-th and hi-th smallest non-NaN values, exact, as fp32 bit patterns
+ *   5. the result, float64: a + (b - a) * t where t < 0.5, b - (b - a) * (1 - t) where t >= 0.5
+ * This is numpy.quantile(x.astype(float64), q, method="linear") with numpy's own _lerp (checked against numpy 2.2.6 by
+ * tests/test_quantiles_cpu.py), applied uniformly: an infinite neighbour gives what numpy gives (NaN at q = 0 when the minimum is
+ * -inf).  A zero result may carry either sign.  skipna != 0 (numpy.nanquantile): NaNs are counted and left out; skipna == 0
+ * (numpy.quantile): any NaN makes the data set's whole row NaN; nv == 0 gives a NaN row.
+ * c2w_quantiles: out[D][Q] double, stats[D][Q][2] fp32 (the two order statistics a, b), n_valid[D] int64 (nv, whatever skipna is).
+ * q: a HOST array of Q doubles, passed to the kernels by value; a level that is NaN or outside [0, 1] is C2W_ERR_BAD_ARG.
+ * Method: radix select on the monotone key k = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) of the loaded bit pattern -- no float
+ * arithmetic touches a value, denormals are kept, -0.0 sorts just below +0.0, a NaN goes to the data set's NaN counter and never to a
+ * bin.  Three counting passes over key digits of 12 / 10 / 10 bits, most significant first, each one full read of the data with
+ * 16-byte loads: quantile_count_kernel (a workgroup owns one data set and a slab of its planes, counts in LDS ints -- all 4096 bins
+ * in pass 0, 1024 bins per active slot later -- and issues one 64-bit integer add per non-zero bin), then quantile_locate_kernel
+ * (one workgroup per data set: nv and the 2 Q target ranks in double after pass 0, each rank's bin and residual rank by a scan in
+ * index order, equal prefixes merged into slots, the slot table of the next pass; after the last pass the keys, inverted to values,
+ * and the interpolation without contraction).  All on the caller's stream, nothing read back by the host in between.  The result is
+ * a function of integer counts only: independent of the grid, the slab arithmetic and the order of the adds, the same bits wherever
+ * a data set lies in the launch.  No float atomics.  scratch: c2w_quantile_scratch_bytes(D, Q) bytes, 16-byte aligned; the call
+ * zeroes its tables with hipMemsetAsync on the stream.  Supported: hw a multiple of 4, 1 <= Q <= 16.  A workgroup's slab of 2^31
+ * values or more is C2W_ERR_BAD_SHAPE.  Everything unsupported returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_quantile_supported(int hw, int Q); /* 1 or 0 */
+long long c2w_quantile_scratch_bytes(long long D, int Q);
+int c2w_quantiles(const float* x, const float* y, const double* q, int Q, int skipna, void* scratch, unsigned long long scratch_bytes,
+                  double* out, float* stats, long long* n_valid, long long n_rep, int T, int F, int hw, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
