@@ -562,6 +562,29 @@ def quantiles(x, y, q, skipna, scratch, out, stats, n_valid, n_rep, T, F, hw) ->
     return True
 
 
+def crps_supported(hw: int, M: int) -> bool:
+    return bool(_lib.load().c2w_crps_supported(hw, M))
+
+
+def crps_scratch_bytes(T: int, F: int, hw: int) -> int:
+    """bytes of scratch ``crps_terms`` needs for T x F planes of hw cells (0 while a plane is one chunk)"""
+    return int(_lib.load().c2w_crps_scratch_bytes(T, F, hw))
+
+
+def crps_terms(x, y, sums, cells, scratch, M, T, F, hw) -> bool:
+    """sums (T, F, 4) float64 = per plane the sums over its hw cells of the four terms A, B, E, V of the M members x (M, T, F, hw)
+    against the truth y (T, F, hw) -- dense fp32, 16-byte aligned (include/c2w_hip.h::c2w_crps_terms: the definition, the algebra, the
+    fixed summation order); cells, if not None: (4, T, F, hw) fp32, the four terms per cell.  scratch: a float64 device tensor of at
+    least ``crps_scratch_bytes`` bytes, or None where that is 0.  False if hw or M is not supported -- nothing is written and the
+    caller takes the general definition (crps.ensemble_terms)."""
+    nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
+    rc = _lib.load().c2w_crps_terms(_p(x), _p(y), _p(sums), _p(cells), _p(scratch), nbytes, M, T, F, hw, _stream())
+    if rc == -3:
+        return False
+    check(rc, "c2w_crps_terms")
+    return True
+
+
 def timestep_embedding(t, out, n, dim, max_period=10000.0):
     check(_lib.load().c2w_timestep_embedding(_p(t), _p(out), n, dim, max_period, _stream()), "c2w_timestep_embedding")
 

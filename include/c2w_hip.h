@@ -482,6 +482,44 @@ int c2w_quantile_supported(int hw, int Q); /* 1 or 0 */
 long long c2w_quantile_scratch_bytes(long long D, int Q);
 int c2w_quantiles(const float* x, const float* y, const double* q, int Q, int skipna, void* scratch, unsigned long long scratch_bytes,
                   double* out, float* stats, long long* n_valid, long long n_rep, int T, int F, int hw, void* stream);
+/* Ensemble CRPS and spread-skill: the M members of one cell judged jointly against that cell's truth.
+ * Definition.  One cell (t, f, c) has the members x_1 .. x_M = x[m][t][f][c] and the truth y = y[t][f][c], fp32 inputs read as exact
+ * real numbers.  Four non-negative terms per cell:
+ *   A = (1 / M) sum_m |x_m - y|
+ *   B = sum_{m < m'} |x_m - x_m'|, with the members sorted = sum_{k = 1}^{M - 1} k (M - k) (x_(k + 1) - x_(k))
+ *   E = (mean_m x_m - y)^2
+ *   V = sum_m (x_m - mean x)^2 / (M - 1)                                                  (M = 1: NaN)
+ * and from their means over the cells of a (t, f) plane, or over any larger set (the caller's: climate2weather_amd.crps):
+ *   crps      = mean A - mean B / M^2         the empirical-CDF form, integral (F_M(z) - 1[z >= y])^2 dz, VERIFIED against that
+ *                                             integral evaluated exactly in float64 (tests/test_crps_cpu.py), not recalled
+ *   crps_fair = mean A - mean B / (M (M - 1))                                              (M = 1: NaN)
+ *   rmse = sqrt(mean E), spread = sqrt(mean V), ratio = sqrt((M + 1) / M) * spread / rmse  (1: a statistically consistent ensemble)
+ * Non-finite values: a member or a truth that is NaN or infinite makes the four terms of its cell, and with them the four sums of
+ * its (t, f) entry, NaN, written explicitly; no other entry is touched.
+ * c2w_crps_terms: sums[T][F][4] double = the sums of A, B, E, V over the hw cells of every plane, from x[M][T][F][hw] against
+ * y[T][F][hw] (dense fp32, 16-byte aligned); cells, if not NULL: [4][T][F][hw] fp32, the planes A, B, E, V per cell (16-byte aligned).
+ * Numerics: a straight fp32 port fails on the fields this project downscales -- on a pressure field at 101325 +- 1200 with a member
+ * spread of 0.05 - 3 the mean and the variance of the raw values put V off by orders of magnitude -- so the kernel forms only
+ * differences of nearby numbers and sums of non-negative terms.  crps_terms_kernel: a workgroup of 256 owns one plane, or one chunk of
+ * 4096 cells of it (a function of hw alone); a thread owns V adjacent cells at a time and holds their K x V member values in
+ * registers, K = M rounded up to 8, 16, 32 or 64 and (K, V) one of (8, 4), (16, 4), (32, 2), (64, 1), loaded as wide as V allows with
+ * all loads in flight before the first use (K loads in a straight line: row i asks for member min(i, M - 1), so a row from M on hits
+ * the line the last member's load has just brought in); non-finite values are found on the loaded values (min and max drop a NaN);
+ * rows M .. K - 1 are then set to +inf.  The rows are sorted by Batcher's odd-even merge network of v_min_f32 / v_max_f32 pairs with static indices (no scratch
+ * memory); every sum runs over the first M rows only.  B from the neighbour gaps times the exact weights k (M - k); the pivot
+ * p = x_(M / 2), e_i = x_(i) - p, ebar = (sum e) / M, V = sum (e_i - ebar)^2 / (M - 1), E = ((p - y) + ebar)^2; A = sum |x_(i) - y| / M;
+ * no multiply fused with an add.  Identical members give B = 0 and V = 0 exactly.  Per-cell values are fp32; they join four double
+ * accumulators per thread in cell order, the workgroup folds those through LDS in thread order (sixteen threads at a time, then the
+ * sixteen group totals), and when a plane has several chunks crps_fold_kernel adds them in index order: at most two launches on the
+ * caller's stream, no atomics, no host read-back, the same bits for a plane wherever it lies in the launch.  Per cell the error is at
+ * most (M + 16) 2^-24 s with s the float64 value itself for A, B, V and A^2 for E; a sum's at most (M + 16) 2^-24 times the sum of
+ * its cells' s (tests/fp64_crps_ref.py).  scratch: c2w_crps_scratch_bytes(T, F, hw) bytes (0 while a plane is one chunk: the pointer
+ * may then be NULL), 8-byte aligned, every byte of it written before it is read.  Supported: hw a multiple of 4, 1 <= M <= 64.
+ * Everything unsupported returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_crps_supported(int hw, int M); /* 1 or 0 */
+long long c2w_crps_scratch_bytes(int T, int F, int hw);
+int c2w_crps_terms(const float* x, const float* y, double* sums, float* cells, double* scratch, unsigned long long scratch_bytes, int M,
+                   int T, int F, int hw, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
