@@ -382,6 +382,14 @@ def weight_transpose_batched(flat, out, desc, nconv, dtype):
         weight_transpose(flat.reshape(-1)[w_off:], out.reshape(-1)[o_off:], R, NT, K, ldk, ldr, flip, dtype)
 
 
+def _one_minus(b):
+    """the kernels' `1.f - b` on the fp32 value the C ABI receives (pointwise.hip:800-813, :857): 1 - fp32(0.999) is 1.29e-5 (relative)
+    away from fp32(1 - 0.999), which the second-moment buffer shows in full -- found by replaying the engine's own launches
+    (tests/launch_replay.py); tests/fp64_update_ref.py::one_minus is the same statement with its error term"""
+    f = torch.tensor(b, dtype=torch.float32)
+    return float(1.0 - f)
+
+
 def adamw_ema(p, g, m, v, ema, shadow, n, lr, beta1, beta2, eps, weight_decay, step, ema_rate, grad_scale, scaler=None):
     P, G, M, V = (a.reshape(-1)[:n] for a in (p, g, m, v))
     if scaler is not None:  # torch.cuda.amp.GradScaler: unscale, skip the step on inf/nan (the EMA still moves)
@@ -389,17 +397,17 @@ def adamw_ema(p, g, m, v, ema, shadow, n, lr, beta1, beta2, eps, weight_decay, s
         step = int(scaler[3]) + 1
         if float(scaler[2]) != 0:
             if ema is not None:
-                ema.reshape(-1)[:n].mul_(ema_rate).add_(P, alpha=1 - ema_rate)
+                ema.reshape(-1)[:n].mul_(ema_rate).add_(P, alpha=_one_minus(ema_rate))
             return
     gi = G * grad_scale
     P.mul_(1 - lr * weight_decay)
-    M.mul_(beta1).add_(gi, alpha=1 - beta1)
-    V.mul_(beta2).addcmul_(gi, gi, value=1 - beta2)
+    M.mul_(beta1).add_(gi, alpha=_one_minus(beta1))
+    V.mul_(beta2).addcmul_(gi, gi, value=_one_minus(beta2))
     bc1 = 1 - beta1**step
     bc2 = 1 - beta2**step
     P.addcdiv_(M, V.sqrt() / math.sqrt(bc2) + eps, value=-lr / bc1)
     if ema is not None:
-        ema.reshape(-1)[:n].mul_(ema_rate).add_(P, alpha=1 - ema_rate)
+        ema.reshape(-1)[:n].mul_(ema_rate).add_(P, alpha=_one_minus(ema_rate))
     if shadow is not None:
         shadow.reshape(-1)[:n] = P.to(shadow.dtype)
 
@@ -428,7 +436,7 @@ def grad_scaler_update(state, growth, backoff, interval):
 
 
 def ema_update(ema, p, n, rate):
-    ema.reshape(-1)[:n].mul_(rate).add_(p.reshape(-1)[:n], alpha=1 - rate)
+    ema.reshape(-1)[:n].mul_(rate).add_(p.reshape(-1)[:n], alpha=_one_minus(rate))
 
 
 def _attn(qkv, B, T, C):

@@ -13,6 +13,7 @@ import torch
 
 import fp64_noise_ref as N
 import fp64_ref as R
+from fp64_guidance_ref import _cells, _chain, _div, _uncells, guidance_correction  # shared with tests/launch_replay.py
 from climate2weather_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -279,50 +280,6 @@ def test_window_gather_and_scatter_routes(case, dt):
 
 
 # ------------------------------------------------------------------------------------- guidance and the measurement operator
-
-def _div(a, c):
-    """a V over an exact fp32 scalar: one division (correctly rounded by default; K_ULP fp32 ulps allowed, as for fp64_ref's 1-ulp ops)"""
-    v = a.v / c
-    e = a.e / abs(c)
-    return R.V(v, e + R.K_ULP * R.U32 * (v.abs() + e))
-
-
-def _divv(a, b):
-    a, b = R._v(a), R._v(b)
-    v = a.v / b.v
-    e = (a.e + v.abs() * b.e) / (b.v.abs() - b.e)
-    return R.V(v, e + R.K_ULP * R.U32 * (v.abs() + e))
-
-
-def _cells(t, s):
-    """(n, F, H, W) -> (n, F, H / s, W / s, s * s)"""
-    n, F, H, W = t.shape
-    return t.reshape(n, F, H // s, s, W // s, s).permute(0, 1, 2, 4, 3, 5).reshape(n, F, H // s, W // s, s * s)
-
-
-def _uncells(t, s):
-    n, F, PH, PW, _ = t.shape
-    return t.reshape(n, F, PH, PW, s, s).permute(0, 1, 2, 4, 3, 5).reshape(n, F, PH * s, PW * s)
-
-
-def _chain(s):
-    return -(-s * s // 64) + 6  # a lane's loop over the cell, then the six shuffle steps of the wave sum
-
-
-def guidance_correction(x, eps, yobs, stdv, gam, nobs, s, t, mu, sigma):
-    """sampler.hip, guidance_kernel, in float64 with the kernel's roundings: corr = sigma (err / var) / (mu s^2) per pooled cell, where
-    x0 = (x - sigma eps) / mu, err = y - mean_cell(x0), var = std_c^2 + gamma_c (sigma / mu)^2.  V (nobs, F, PH, PW); mu, sigma fp32 values."""
-    X, E = R.exact(x[::t][:nobs]), R.exact(eps[::t][:nobs])
-    x0 = _div(R._sub(X, R._mul(sigma, E)), mu)
-    tot = R._sum(R.V(_cells(x0.v, s), _cells(x0.e, s)), -1, chain=_chain(s))
-    mean = _div(tot, float(s * s))
-    ratio = _div(R._v(sigma), mu)
-    sd = R.exact(stdv).view(1, -1, 1, 1)
-    var = R._add(R._mul(sd, sd), R._mul(R._mul(R.exact(gam).view(1, -1, 1, 1), ratio), ratio))
-    err = R._sub(R.exact(yobs), mean)
-    q = _divv(err, R.V(var.v.expand_as(err.v), var.e.expand_as(err.v)))
-    return _divv(R._mul(sigma, q), R._mul(mu, float(s * s)))
-
 
 @pytest.mark.parametrize("L,F,H,W,s,t", [(7, 3, 24, 36, 12, 3), (4, 2, 6, 9, 3, 1), (5, 1, 8, 16, 1, 2)])
 def test_guidance_and_pooling_on_non_square_fields(L, F, H, W, s, t):
