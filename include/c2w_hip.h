@@ -520,6 +520,49 @@ int c2w_crps_supported(int hw, int M); /* 1 or 0 */
 long long c2w_crps_scratch_bytes(int T, int F, int hw);
 int c2w_crps_terms(const float* x, const float* y, double* sums, float* cells, double* scratch, unsigned long long scratch_bytes, int M,
                    int T, int F, int hw, void* stream);
+/* Wind power of an ensemble: hub-height speed, turbine power curve, domain sums (the reference's exp/figures.py::_calc_windpower).
+ * Definition.  One cell of one (d, t) plane -- d a data set: a member, the truth, the coarse observation; t a time -- has the fp32 wind
+ * components u, v in m/s (fields DE-NORMALISED), read as exact real numbers.
+ *   hub factor  c = (hub_height / reference_height)^alpha, formed in float64 by the caller (defaults 100, 10, 1/7), passed as a float
+ *   speed       = sqrt(u u + v v) c                         (the reference writes np.sqrt(u**2 + v**2), not hypot)
+ *   power       = numpy.interp(speed, xs, ps, left = 0, right = 0), the curve having K >= 2 knots, xs strictly increasing, ps in W:
+ *                 ps[j] + (speed - xs[j]) slope_j for xs[j] <= speed < xs[j + 1]; ps[K - 1] at speed == xs[K - 1]; 0 strictly above
+ *                 it (cut-out) and below xs[0]; NaN for a NaN speed; 0 for +inf
+ *   sums[d][t]  = {S_speed, S_power}, the sums of the two over the hw cells of the plane, in double
+ * and from them (the caller's: climate2weather_amd.windpower) mean power = S_power / hw and the cumulative energy series
+ * cumsum_t(mean power / 1e3).  That windpowerlib's ModelChain with its defaults is this numpy.interp call is RECALLED (README, statement
+ * 9); numpy.interp itself is the float64 reference of every test.  No turbine's data is shipped: the caller passes the curve.
+ * Non-finite values: a NaN u or v makes the two values of its cell, and with them the two sums of its (d, t) entry, NaN, written
+ * explicitly; no other entry is touched.  An infinite u or v gives speed +inf and power 0.
+ * c2w_wind_table (pure host code) fills the packed table of c2w_wind_table_bytes(K) = 32 + 16 (K - 1) + 512 bytes at table_host, 16-byte
+ * aligned: a header {x^_0, x^_{K-1}, p_{K-1}, buckets per m/s, K, mode}; the K - 1 intervals as {x^_j, p_j, slope_j, x^_{j+1}} fp32, one
+ * 16-byte LDS read per interpolation; 256 two-byte starting knots of a uniform bucket index over [x^_0, x^_{K-1}].  The knots are rounded
+ * to fp32 (x^) and must still increase strictly; slope_j = (p_{j+1} - p_j) / (x^_{j+1} - x^_j) is formed in float64 from the rounded
+ * knots and rounded once, so the table is the piecewise-linear curve through (x^_j, p_j).  C2W_ERR_BAD_ARG for K outside 2 .. 256, a
+ * knot, a power or a slope that is not finite in fp32, and knots that do not increase strictly (as given, or once rounded).  The caller
+ * copies the table to the device.
+ * c2w_wind_power: fields is [planes][F][hw] dense fp32, 16-byte aligned; the u and v planes of every (d, t) sit at u_index and v_index
+ * of its F, so 2 / F of the tensor is read, every value once, 16 bytes a load.  sums[planes][2] double; derived, if not NULL:
+ * [planes][2][hw] fp32, speed in plane 0 and power in plane 1 (16-byte aligned) -- the layout c2w_kde_eval takes as F = 2 variables.
+ * wind_power_kernel: a workgroup of 256 owns one plane, or one chunk of 4096 cells of it (a function of hw alone), and copies the table
+ * to LDS once.  The lookup is bucket -> starting knot -> 2 forward steps, none behind a branch, where no bucket holds more than 2 knots (mode 0), a
+ * binary search over the intervals otherwise (mode 1: curves whose knots crowd a bucket).  The arithmetic is fp32, no multiply fused
+ * with an add, the square root correctly rounded.  Per-cell values join two double accumulators per thread in cell order, the
+ * workgroup folds those through LDS in thread order (sixteen threads at a time, then the sixteen group totals), and when a plane has
+ * several chunks wind_fold_kernel adds them in index order: at most two launches on the caller's stream, no atomics, no host
+ * read-back, the same bits for a plane wherever it lies in the launch.  Error against float64 (tests/fp64_wind_ref.py): the speed within
+ * 6 * 2^-24 of itself plus 2^-62 c where the squares underflow; the power between the least and the largest value of the float64 curve
+ * over the speed's window widened by the rounding of a knot, give or take 9 * 2^-24 of the larger power at the interval's ends; a sum
+ * within the sum of its cells' bounds.  A float64 u u + v v beyond the fp32 range gives speed +inf.  scratch:
+ * c2w_wind_scratch_bytes(planes, hw) bytes (0 while a plane is one chunk: the pointer may then be NULL), 8-byte aligned, every byte of
+ * it written before it is read.  Supported: hw a multiple of 4, 2 <= K <= 256.  Everything unsupported returns C2W_ERR_UNSUPPORTED and
+ * writes nothing. */
+int c2w_wind_supported(int hw, int K); /* 1 or 0 */
+long long c2w_wind_table_bytes(int K);
+int c2w_wind_table(const double* xs, const double* ps, int K, void* table_host);
+long long c2w_wind_scratch_bytes(long long planes, int hw);
+int c2w_wind_power(const float* fields, int F, int u_index, int v_index, const void* table, int K, float hub_factor, double* sums,
+                   float* derived, double* scratch, unsigned long long scratch_bytes, long long planes, int hw, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
