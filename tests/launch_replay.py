@@ -20,7 +20,8 @@ include/c2w_hip.h; scratch (splitk / det / workspace / delta_ws) is handed to th
 ``*_noise`` launchers get the float64 Philox stream of tests/fp64_noise_ref.py as their noise tensor.
 
 This proves kernel against reference AT THE ENGINE'S ARGUMENTS.  It does not prove that the engine passes the right arguments (that is
-tests/test_engine_emulated.py and the oracle parities), nor anything about races between launches: the harness serialises.
+tests/test_engine_emulated.py and the oracle parities), nor anything about races between launches: the harness serialises
+(the ordering between streams is tests/stream_audit.py's subject).
 """
 from __future__ import annotations
 
@@ -436,6 +437,12 @@ class Harness:
             got, ref, old = call.out(p), at(call.ref, p), at(call.snap, p)
             rule, tol = compare_rule(name, p, call.real, got)
             what = f"{pstr(p)} vs restatement"
+            if got.dtype.is_floating_point and got.shape == ref.shape == old.shape:
+                # NaNs that were in the buffer before the call and that neither side touched (the unwritten part of a torch.empty behind
+                # an open-ended view): equal bits three times over, but NaN != NaN would fail every comparison below
+                stale = torch.isnan(old) & _eq_bits(got, old) & _eq_bits(ref, old)
+                if bool(stale.any()):
+                    got, ref, old = (torch.where(stale, torch.zeros_like(t), t) for t in (got, ref, old))
             if rule == "equal" or not got.dtype.is_floating_point:
                 assert torch.equal(got, ref), f"{what}: bits differ in {int((got != ref).sum())} of {got.numel()} elements"
                 self.report.ratio(name, what, 0.0)
@@ -498,6 +505,14 @@ def _has(tree, path):
         return isinstance(at(tree, path), torch.Tensor)
     except (KeyError, IndexError, TypeError):
         return False
+
+
+_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _eq_bits(a, b):
+    """element-wise: the same bits"""
+    return a.contiguous().view(_INT[a.element_size()]) == b.contiguous().view(_INT[b.element_size()])
 
 
 def _same_bits(a, b):

@@ -123,6 +123,29 @@ def test_an_output_that_is_its_own_residual_shares_one_clone(monkeypatch):
     assert rep.checked["conv"] == 1 and not _all_zero(rep)
 
 
+def test_nan_garbage_behind_an_open_ended_output_is_not_a_difference(monkeypatch):
+    """score_fn hands the launchers views of a torch.empty trajectory: what a call leaves alone may hold anything, NaNs included.  They
+    have equal bits before and after on both sides and must not fail the comparison -- while a NaN the launcher WRITES still does."""
+    emu_ops.install(monkeypatch, c2w_ops)
+    rep = LR.install(monkeypatch, c2w_ops)
+    F, HW, k, nw, nwin = 2, 16, 1, 2, 6
+    eps = torch.full((8 * F * HW,), float("nan"))
+    y = torch.randn(nw * HW, 32, generator=torch.Generator().manual_seed(4))
+    c2w_ops.window_scatter(y, eps, nw, F, HW, k, 2, nwin, 32, c2w_ops.DTYPE_F32)
+    H, W = 8, 16
+    out = torch.full((6 * 3 * H * W,), float("nan"))
+    x, w = torch.randn(2 * H * W, 64, generator=torch.Generator().manual_seed(5)), torch.randn(9 * 9 * 64, generator=torch.Generator().manual_seed(6)) / 24
+    c2w_ops.conv_center(x, w, None, out[3 * H * W:], 2, H, W, 64, 9, 3, 3, 3 * H * W, c2w_ops.DTYPE_F32)
+    rep.assert_clean()
+    assert rep.checked["window_scatter"] == 1 and rep.checked["conv_center"] == 1 and not torch.isnan(eps[3 * F * HW: 5 * F * HW]).any()
+
+    def nan_out(call):
+        call.real["eps"].reshape(-1)[3 * F * HW + 1] = float("nan")
+    bad = LR.install(monkeypatch, c2w_ops, planted=nan_out)
+    c2w_ops.window_scatter(y, eps, nw, F, HW, k, 2, nwin, 32, c2w_ops.DTYPE_F32)
+    assert [f[1] for f in bad.failures] == ["window_scatter"]
+
+
 def test_a_written_argument_that_partially_overlaps_another_is_an_error(monkeypatch):
     emu_ops.install(monkeypatch, c2w_ops)
     LR.install(monkeypatch, c2w_ops)
