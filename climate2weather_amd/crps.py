@@ -33,7 +33,8 @@ cell the error is at most ``(M + 16) 2^-24`` of the term (of ``A^2`` for ``E``);
 
 Nothing here synchronises.
 
-Out of scope: weighted or thresholded CRPS, the energy score and other multivariate scores, CRPS against a parametric forecast, the
+Out of scope: weighted or thresholded CRPS, other multivariate scores (``multivariate.py`` has the energy score and the variogram
+score), CRPS against a parametric forecast, the
 plotting, more than 64 members on the kernel (the general route takes them), and collectives -- members are rank-local.
 """
 from __future__ import annotations

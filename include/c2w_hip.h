@@ -563,6 +563,50 @@ int c2w_wind_table(const double* xs, const double* ps, int K, void* table_host);
 long long c2w_wind_scratch_bytes(long long planes, int hw);
 int c2w_wind_power(const float* fields, int F, int u_index, int v_index, const void* table, int K, float hub_factor, double* sums,
                    float* derived, double* scratch, unsigned long long scratch_bytes, long long planes, int hw, void* stream);
+/* Energy score and variogram score of an ensemble: the two multivariate scores, which see the dependence between the cells of a field
+ * that the per-cell CRPS cannot (Gneiting & Raftery 2007; Scheuerer & Hamill 2015 -- both as recalled: README, statement 10).
+ *
+ * Definitions.  One (t, f) plane of hw = H W cells has the rows r_0 = y (the truth) and r_1 .. r_M = x_m, fp32 read as exact numbers;
+ * planes = T F, x is [M][planes][hw], y is [planes][hw], dense.
+ *   Energy score.  D2[plane][p] = sum_c (r_i[c] - r_j[c])^2 for every pair i < j, p row-major over i < j
+ *   (p = i (2 (M + 1) - i - 1) / 2 + j - i - 1), P = M (M + 1) / 2 -- the kernel's product, double.  From it, the caller's in float64
+ *   (climate2weather_amd.multivariate): D = sqrt(D2), A = (1 / M) sum_m D(0, m)^beta, B = sum_{1 <= m < m'} D(m, m')^beta,
+ *   ES = A - B / M^2, fair: A - B / (M (M - 1)) (NaN for M = 1), beta in (0, 2), default 1; over all variables jointly
+ *   D2_joint = sum_f D2[t][f] / scale_f^2.
+ *   Variogram score of order p.  The offsets o = (di, dj) with max(|di|, |dj|) <= R in the half plane di > 0, or di == 0 and dj > 0,
+ *   row-major: (0, 1) .. (0, R), then di = 1 .. R each with dj = -R .. R; O = ((2 R + 1)^2 - 1) / 2.  For every cell pair (c, c + o) with
+ *   both cells inside the field g_y = |y_c - y_{c+o}|^p and g_x = (1 / M) sum_m |x_{m,c} - x_{m,c+o}|^p, and
+ *   V[plane][o][0..2] = the sums over the pairs of ((g_y - g_x)^2, g_y, g_x) -- the kernel's product, double.  The weights are the
+ *   caller's: VS = sum_o w_o V[..][o][0]; V[..][1] and V[..][2] over the pair count (H - di) (W - |dj|) are the empirical variograms
+ *   of truth and ensemble by lag.  The kernel takes p as order2 = 2 p in {1, 2, 4}.
+ * Non-finite values: a NaN or an infinity in a row makes every D2 entry of that row in its plane NaN, and the three sums of every
+ * (plane, o) one of whose pairs touches its cell NaN; no other entry is touched.  The kernels see it on the result -- every term is
+ * >= 0 and a difference with a non-finite end is not finite -- so a term that overflows fp32 (a difference beyond 1.8e19) ends as NaN
+ * as well.
+ * escore_pairs_kernel: a workgroup of 256 owns 256 cells of one plane and copies them, all M + 1 rows, from HBM to LDS once, 16 bytes a
+ * load; a thread owns a 4 x 4 tile of row pairs and every S-th group of 4 cells (S a function of M) and keeps 16 double sums:
+ * d = a - b in fp32, d * d in fp32, not fused, added to the double in cell order.  The S threads of a tile fold through LDS in thread
+ * order; escore_fold_kernel adds the chunks of a plane in index order.  (M + 1) 1040 bytes of LDS, at least 32 KiB: 67 600 at M = 64.
+ * vario_terms_kernel: a workgroup of 256 owns an 8 x 32 tile of one plane and copies it with its halo (R columns either side, R rows
+ * below) of all M + 1 rows to LDS; a thread owns a cell and walks the offsets four at a time, the member loop innermost: every term
+ * fp32 (p = 0.5 the correctly rounded square root, p = 1 the absolute value, p = 2 a product), g_x the fp32 chain of the M terms in
+ * member order times the fp32 1 / M, ((double)g_y - (double)g_x)^2 and the two variograms summed in double, through LDS in thread
+ * order (sixteen threads at a time, then the sixteen group totals); vario_fold_kernel adds the tiles in index order.  At most 78 336
+ * bytes of LDS (R = 8, M = 16).  At most two launches each on the caller's stream, no atomics, no host read-back, the same bits for a
+ * plane wherever it lies in the launch.  Error against float64 (tests/fp64_escore_ref.py): a D2 entry within 3 * 2^-24 of itself;
+ * V[..][0] within (2 M + 8) 2^-24 sum (g_y + g_x)^2 over its pairs, V[..][1] within 3 * 2^-24 and V[..][2] within (M + 4) 2^-24 of
+ * themselves.  scratch: c2w_*_scratch_bytes bytes (0 while a plane is one chunk or one tile: the pointer may then be NULL), 8-byte
+ * aligned, every byte of it written before it is read.  Supported: pairs hw a multiple of 4, 1 <= M <= 64 (x, y 16-byte aligned);
+ * variogram H and W multiples of 8, 1 <= R <= 8, 1 <= M <= 16, order2 in {1, 2, 4}.  Everything unsupported returns
+ * C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_escore_supported(int hw, int M); /* 1 or 0 */
+long long c2w_escore_scratch_bytes(long long planes, int hw, int M);
+int c2w_escore_pairs(const float* x, const float* y, double* d2, double* scratch, unsigned long long scratch_bytes, int M, long long planes,
+                     int hw, void* stream);
+int c2w_vario_supported(int H, int W, int R, int M, int order2); /* 1 or 0 */
+long long c2w_vario_scratch_bytes(long long planes, int H, int W, int R);
+int c2w_vario_terms(const float* x, const float* y, double* V, double* scratch, unsigned long long scratch_bytes, int M, long long planes,
+                    int H, int W, int R, int order2, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`

@@ -1,0 +1,219 @@
+"""TEST DOUBLE for the energy-score and variogram-score launchers (climate2weather_amd.escore_ops), on CPU tensors.
+
+It restates the kernels of csrc/escore.hip in NumPy with the index maps of csrc/escore_core.h written out again in Python -- the
+chunks of 256 cells, the 4 x 4 pair tiles and their S slices of every S-th group of 4 cells, the 8 x 32 cell tiles, the offset
+enumeration, the folds through LDS in thread order and over the chunks and tiles -- and with the kernels' arithmetic in fp32,
+operation by operation and in the kernels' order, no multiply fused with an add.  Unsupported shapes answer False and write nothing.
+``install`` also makes the multivariate module treat CPU tensors as device tensors, so the host code takes the launcher's branch.
+"""
+from __future__ import annotations
+
+import sys
+
+import numpy as np
+import torch
+
+CALLS = []  # ("pairs", M, planes, hw) / ("vario", M, planes, H, W, R, order2) of every call that reached a launcher
+
+THREADS, GROUP = 256, 16
+GROUPS = THREADS // GROUP
+P_MAX_M, P_CHUNK = 64, 256
+V_MAX_M, V_MAX_R, V_TH, V_TW, V_BATCH = 16, 8, 8, 32, 4
+
+
+def _nan_if_not_finite(t):
+    return np.where(np.isfinite(t), t, np.nan)
+
+
+def _seq_sum(a, axis):
+    """the sum along `axis` in index order from +0, one addition after the other (numpy.sum adds pairwise)"""
+    a = np.moveaxis(a, axis, 0)
+    t = np.zeros(a.shape[1:], np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(a.shape[0]):
+            t = t + a[k]
+    return t
+
+
+# ------------------------------------------------------------------------------------------------------------------ pairs
+
+def escore_supported(hw, M):
+    return hw >= 4 and hw % 4 == 0 and 1 <= M <= P_MAX_M
+
+
+def pairs(M):
+    return M * (M + 1) // 2
+
+
+def tiles(M):
+    nb = (M + 1 + 3) // 4
+    return nb * (nb + 1) // 2
+
+
+def slices(M):
+    s = 64
+    while s * tiles(M) > THREADS:
+        s //= 2
+    return s
+
+
+def chunks(hw):
+    return (hw + P_CHUNK - 1) // P_CHUNK
+
+
+def lds_bytes(M):
+    return max((M + 1) * (P_CHUNK + 4) * 4, 16 * THREADS * 8)
+
+
+def escore_scratch_bytes(planes, hw, M):
+    if planes < 1 or not escore_supported(hw, M):
+        return 0
+    return planes * chunks(hw) * pairs(M) * 8 if chunks(hw) > 1 else 0
+
+
+def chunk_pairs(rows, M):
+    """rows (M + 1, n <= 256) fp32 of one chunk -> (P,) float64 as one workgroup forms it"""
+    f32 = np.float32
+    assert rows.dtype == f32
+    S = slices(M)
+    padded = np.zeros((M + 1, P_CHUNK), f32)
+    padded[:, :rows.shape[1]] = rows
+    out = np.zeros(pairs(M), np.float64)
+    p = 0
+    with np.errstate(all="ignore"):
+        for i in range(M):
+            d = padded[i][None] - padded[i + 1:]          # (M - i, 256) fp32
+            sq = d * d
+            assert sq.dtype == f32
+            # thread s of the tile takes the groups of 4 cells s, s + S, ..: (k, s, c) -> per thread the cells in ascending order
+            per_thread = sq.astype(np.float64).reshape(-1, P_CHUNK // 4 // S, S, 4).transpose(0, 2, 1, 3).reshape(-1, S, P_CHUNK // S)
+            out[p:p + M - i] = _seq_sum(_seq_sum(per_thread, 2), 1)
+            p += M - i
+    return _nan_if_not_finite(out)
+
+
+def escore_pairs(x, y, d2, scratch, M, planes, hw):
+    CALLS.append(("pairs", int(M), int(planes), int(hw)))
+    if not escore_supported(hw, M):
+        return False
+    for t in (x, y):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+    P, nc = pairs(M), chunks(hw)
+    assert d2.dtype == torch.float64 and d2.is_contiguous() and d2.numel() >= planes * P
+    need = escore_scratch_bytes(planes, hw, M)
+    assert need == 0 or (scratch is not None and scratch.dtype == torch.float64 and scratch.numel() * 8 >= need)
+    xs, ys = x.reshape(M, planes, hw).numpy(), y.reshape(planes, hw).numpy()
+    part = np.full((planes, nc, P), np.nan)
+    for pl in range(planes):
+        rows = np.concatenate([ys[pl][None], xs[:, pl]])
+        for c in range(nc):
+            part[pl, c] = chunk_pairs(rows[:, c * P_CHUNK:(c + 1) * P_CHUNK], M)
+    if nc > 1:
+        scratch.reshape(-1).numpy()[:planes * nc * P] = part.reshape(-1)
+    out = _nan_if_not_finite(_seq_sum(part, 1)) if nc > 1 else part[:, 0]
+    d2.reshape(-1).numpy()[:planes * P] = out.reshape(-1)
+    return True
+
+
+# ------------------------------------------------------------------------------------------------------------------ variogram
+
+def vario_supported(H, W, R, M, order2):
+    return H >= 8 and W >= 8 and H % 8 == 0 and W % 8 == 0 and 1 <= R <= V_MAX_R and 1 <= M <= V_MAX_M and order2 in (1, 2, 4)
+
+
+def n_offsets(R):
+    return ((2 * R + 1) ** 2 - 1) // 2
+
+
+def offset_of(R, o):
+    if o < R:
+        return 0, o + 1
+    return 1 + (o - R) // (2 * R + 1), (o - R) % (2 * R + 1) - R
+
+
+def vario_tiles(H, W):
+    return (H // V_TH) * ((W + V_TW - 1) // V_TW)
+
+
+def vario_lds_bytes(R, M):
+    return ((M + 1) * (V_TH + R) * (V_TW + 2 * R) * 4 + 7) // 8 * 8 + 3 * V_BATCH * (THREADS + GROUPS) * 8
+
+
+def vario_scratch_bytes(planes, H, W, R):
+    if planes < 1 or H < 1 or W < 1 or not 1 <= R <= V_MAX_R:
+        return 0
+    return planes * vario_tiles(H, W) * n_offsets(R) * 3 * 8 if vario_tiles(H, W) > 1 else 0
+
+
+def _power32(d, order2):
+    a = np.abs(d)
+    out = np.sqrt(a) if order2 == 1 else a if order2 == 2 else a * a
+    assert out.dtype == np.float32
+    return out
+
+
+def plane_terms(x, y, di, dj, order2):
+    """x (M, H, W), y (H, W) fp32 -> (3, H, W) float64: the three terms of every cell for one offset as its thread forms them, +0
+    where the pair does not lie inside the field"""
+    f32 = np.float32
+    M, H, W = x.shape
+    out = np.zeros((3, H, W), np.float64)
+    if di >= H or abs(dj) >= W:
+        return out
+    ci, cj = slice(0, H - di), slice(max(0, -dj), W - max(0, dj))
+    ni, nj = slice(di, H), slice(max(0, dj), W + min(0, dj))
+    with np.errstate(all="ignore"):
+        gy = _power32(y[ci, cj] - y[ni, nj], order2)
+        s = np.zeros_like(gy)
+        for m in range(M):
+            s = s + _power32(x[m][ci, cj] - x[m][ni, nj], order2)
+        mean = s * f32(1.0 / M)
+        assert mean.dtype == f32
+        d = gy.astype(np.float64) - mean.astype(np.float64)
+        terms = np.stack([d * d, gy.astype(np.float64), mean.astype(np.float64)])
+        terms[:, ~np.isfinite(gy + mean)] = np.nan
+    out[:, ci, cj] = terms
+    return out
+
+
+def fold_tiles(terms):
+    """terms (3, H, W) float64 -> (tiles, 3): per tile of 8 x 32 cells the 256 threads in thread order, sixteen at a time, then the
+    sixteen group totals"""
+    _, H, W = terms.shape
+    tw = (W + V_TW - 1) // V_TW
+    padded = np.zeros((3, H, tw * V_TW), np.float64)
+    padded[:, :, :W] = terms
+    t = padded.reshape(3, H // V_TH, V_TH, tw, V_TW).transpose(1, 3, 0, 2, 4).reshape(-1, 3, GROUPS, GROUP)  # (tile, sum, group, thread)
+    return _nan_if_not_finite(_seq_sum(_seq_sum(t, 3), 2))
+
+
+def vario_terms(x, y, V, scratch, M, planes, H, W, R, order2):
+    CALLS.append(("vario", int(M), int(planes), int(H), int(W), int(R), int(order2)))
+    if not vario_supported(H, W, R, M, order2):
+        return False
+    for t in (x, y):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    O, nt = n_offsets(R), vario_tiles(H, W)
+    assert O % V_BATCH == 0
+    assert V.dtype == torch.float64 and V.is_contiguous() and V.numel() >= planes * O * 3
+    need = vario_scratch_bytes(planes, H, W, R)
+    assert need == 0 or (scratch is not None and scratch.dtype == torch.float64 and scratch.numel() * 8 >= need)
+    xs, ys = x.reshape(M, planes, H, W).numpy(), y.reshape(planes, H, W).numpy()
+    part = np.full((planes, nt, O, 3), np.nan)
+    for pl in range(planes):
+        for o in range(O):
+            di, dj = offset_of(R, o)
+            part[pl, :, o] = fold_tiles(plane_terms(xs[:, pl], ys[pl], di, dj, order2))
+    if nt > 1:
+        scratch.reshape(-1).numpy()[:planes * nt * O * 3] = part.reshape(-1)
+    out = _nan_if_not_finite(_seq_sum(part, 1)) if nt > 1 else part[:, 0]
+    V.reshape(-1).numpy()[:planes * O * 3] = out.reshape(-1)
+    return True
+
+
+def install(monkeypatch, ops_module, multivariate_module):
+    me = sys.modules[__name__]
+    del CALLS[:]
+    for name in ("escore_supported", "escore_scratch_bytes", "escore_pairs", "vario_supported", "vario_scratch_bytes", "vario_terms"):
+        monkeypatch.setattr(ops_module, name, getattr(me, name))
+    monkeypatch.setattr(multivariate_module, "_on_device", lambda x: True)
