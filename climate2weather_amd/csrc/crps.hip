@@ -1,9 +1,9 @@
 // Ensemble CRPS and spread-skill (c2w_hip.h: c2w_crps_terms): per cell the four terms A, B, E, V of the M members against the truth,
 // per (t, f) plane their sums in double.  crps_terms_kernel is the hot path: a workgroup owns one plane or one chunk of it, a thread
-// sorts the members of its cells in registers by a compile-time network and reads every value once; crps_fold_kernel adds the chunks
-// of a plane in index order when there are several.  crps_core.h has the index maps and the arithmetic; this file is the workgroups
+// sorts the members of its cells in registers by a compile-time network and reads every value once; the shared fold_parts_kernel
+// (ordered_sum_launch.h) adds the chunks of a plane in index order when there are several.  crps_core.h has the index maps and the arithmetic; this file is the workgroups
 // around them.  No float atomics, no sum whose order depends on the launch.
-#include "launch.h"
+#include "ordered_sum_launch.h"
 
 #define CRPS_HD __device__ __attribute__((always_inline))
 #define CRPS_BOTH __host__ __device__ __attribute__((always_inline))
@@ -34,11 +34,6 @@ __global__ __launch_bounds__(THREADS) void crps_terms_kernel(const float* __rest
     t_fold_groups(v, tid);
     __syncthreads();
     t_fold_store(v, tid);
-}
-
-__global__ __launch_bounds__(THREADS) void crps_fold_kernel(const double* __restrict__ partial, double* __restrict__ sums, long long entries, int n_chunks) {
-    const long long e = (long long)blockIdx.x * THREADS + threadIdx.x;
-    if (e < entries) f_fold(partial, sums, e, n_chunks);
 }
 
 template <int K, int V>
@@ -76,7 +71,5 @@ extern "C" int c2w_crps_terms(const float* x, const float* y, double* sums, floa
         default: rc = launch_terms<64, 1>(x, y, out, cells, grid, nc, M, T, F, hw, st); break;
     }
     if (rc || nc == 1) return rc;
-    const long long entries = planes * 4;
-    crps_fold_kernel<<<(unsigned)((entries + THREADS - 1) / THREADS), THREADS, 0, st>>>(scratch, sums, entries, nc);
-    return (int)hipGetLastError();
+    return c2w_fold_parts<ordered_sum::nan_if_nan, 4>(scratch, sums, planes, nc, st);
 }

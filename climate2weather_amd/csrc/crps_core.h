@@ -19,9 +19,9 @@
 //   p = x_(M / 2) the pivot, e_i = x_(i) - p, ebar = (sum e) / M, V = sum (e_i - ebar)^2 / (M - 1), E = ((p - y) + ebar)^2;
 //   A = sum |x_(i) - y| / M.
 // No multiply is fused with an add (the host run and the NumPy restatement give the same bits).  Identical members give B = V = 0.
-// The fp32 terms of a cell join the thread's four double accumulators in cell order; the workgroup folds them through LDS in thread
-// order -- sixteen threads at a time, then the sixteen group totals -- and writes four doubles: to sums if the plane is one chunk, to
-// partial[plane][chunk][4] otherwise, which crps_fold adds in chunk order.  No atomics: a plane's bits are fixed by (M, hw).
+// The fp32 terms of a cell join the thread's four double accumulators in cell order; the workgroup folds them by the fixed-order sum
+// of ordered_sum.h (N = 4, nan_if_nan) and writes four doubles: to sums if the plane is one chunk, to partial[plane][chunk][4]
+// otherwise, which the shared fold kernel adds in chunk order.  No atomics: a plane's bits are fixed by (M, hw).
 #ifndef C2W_CRPS_CORE_H
 #define C2W_CRPS_CORE_H
 
@@ -37,15 +37,15 @@
 #else
 #define CRPS_NO_CONTRACT
 #endif
+#include "ordered_sum.h"
 
 namespace crps {
 
 constexpr int THREADS = 256;
 constexpr int MAX_M = 64;
 constexpr int CHUNK = 4096;             // cells a workgroup owns: 4, 8 or 16 rounds of 256 threads at V = 4, 2, 1
-constexpr int GROUP = 16;               // threads whose accumulators are added in one go; THREADS / GROUP group totals follow
-constexpr int GROUPS = THREADS / GROUP;
-constexpr int LDS_DOUBLES = 4 * THREADS + 4 * GROUPS;
+constexpr int LDS_DOUBLES = ordered_sum::lds_doubles<4>();
+static_assert(THREADS == ordered_sum::THREADS, "the workgroup the fixed-order sum is written for");
 static_assert(CHUNK % (4 * THREADS) == 0, "a chunk is a whole number of rounds at every V");
 
 template <int V>
@@ -268,37 +268,19 @@ static CRPS_HD inline void t_cells(const View& v, Thread<K, V>& th) {
     }
 }
 
+// the three phases of ordered_sum.h at N = 4: thread s writes the workgroup's entry of sum s, an infinite sum stays; f_fold then
+// writes sums[entry], entry = plane 4 + s, from the chunks in index order
 template <int K, int V>
-static CRPS_HD inline void t_stash(const View& v, const Thread<K, V>& th, int tid) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) v.lds[s * THREADS + tid] = th.acc[s];
-}
-
-// thread s GROUPS + g adds sum s of the threads g GROUP .. g GROUP + GROUP - 1, in thread order
-static CRPS_HD inline void t_fold_groups(const View& v, int tid) {
-    if (tid >= 4 * GROUPS) return;
-    const double* p = v.lds + (tid / GROUPS) * THREADS + (tid % GROUPS) * GROUP;
-    double t = 0.0;
-    for (int j = 0; j < GROUP; ++j) t += p[j];
-    v.lds[4 * THREADS + tid] = t;
-}
-
-// thread s adds the group totals of sum s in group order and writes the workgroup's entry; a NaN is written as NaN explicitly
+static CRPS_HD inline void t_stash(const View& v, const Thread<K, V>& th, int tid) { ordered_sum::stash<4>(v.lds, th.acc, tid); }
+static CRPS_HD inline void t_fold_groups(const View& v, int tid) { ordered_sum::fold_groups<4>(v.lds, tid); }
 static CRPS_HD inline void t_fold_store(const View& v, int tid) {
     if (tid >= 4) return;
-    const double* p = v.lds + 4 * THREADS + tid * GROUPS;
-    double t = 0.0;
-    for (int g = 0; g < GROUPS; ++g) t += p[g];
+    const double t = ordered_sum::fold_total<4>(v.lds, tid);
     const int nc = chunks(v.hw);
-    v.out[(v.plane * nc + v.chunk) * 4 + tid] = t != t ? (double)__builtin_nanf("") : t;
+    v.out[(v.plane * nc + v.chunk) * 4 + tid] = ordered_sum::nan_if_nan(t);
 }
-
-// sums[entry], entry = plane 4 + s: the chunks in index order
 static CRPS_HD inline void f_fold(const double* partial, double* sums, long long entry, int nc) {
-    const double* p = partial + (entry / 4) * nc * 4 + entry % 4;
-    double t = 0.0;
-    for (int c = 0; c < nc; ++c) t += p[c * 4];
-    sums[entry] = t != t ? (double)__builtin_nanf("") : t;
+    sums[entry] = ordered_sum::nan_if_nan(ordered_sum::fold_parts(partial, entry, nc, 4));
 }
 
 }  // namespace crps

@@ -1,11 +1,11 @@
 // Energy and variogram scores of an ensemble (c2w_hip.h: c2w_escore_pairs, c2w_vario_terms): per (t, f) plane the squared distances
 // of every pair of the M + 1 rows (the truth and the members), and per offset of a half-plane stencil the three sums of the variogram
 // score, all in double.  escore_pairs_kernel: a workgroup owns 256 cells of one plane, reads every value of the M + 1 rows once from
-// HBM into LDS and serves the pair loop from there, a thread a 4 x 4 tile of pairs; escore_fold_kernel adds the chunks of a plane in
-// index order.  vario_terms_kernel: a workgroup owns an 8 x 32 tile of one plane with its halo in LDS, a thread a cell, the offsets
-// four at a time with the member loop innermost; vario_fold_kernel adds the tiles in index order.  escore_core.h has the index maps
+// HBM into LDS and serves the pair loop from there, a thread a 4 x 4 tile of pairs.  vario_terms_kernel: a workgroup owns an 8 x 32
+// tile of one plane with its halo in LDS, a thread a cell, the offsets four at a time with the member loop innermost.  The shared
+// fold_parts_kernel (ordered_sum_launch.h) adds the chunks or the tiles of a plane in index order.  escore_core.h has the index maps
 // and the arithmetic; this file is the workgroups around them.  No float atomics, no sum whose order depends on the launch.
-#include "launch.h"
+#include "ordered_sum_launch.h"
 
 #define ESC_HD __device__ __attribute__((always_inline))
 #define ESC_BOTH __host__ __device__ __attribute__((always_inline))
@@ -34,12 +34,6 @@ __global__ __launch_bounds__(THREADS) void escore_pairs_kernel(const float* __re
     p_fold_store(v, tid);
 }
 
-__global__ __launch_bounds__(THREADS) void escore_fold_kernel(const double* __restrict__ partial, double* __restrict__ d2, long long entries, int n_chunks,
-                                                              int P) {
-    const long long e = (long long)blockIdx.x * THREADS + threadIdx.x;
-    if (e < entries) p_fold(partial, d2, e, n_chunks, P);
-}
-
 // workgroup b owns plane b / n_tiles and tile b % n_tiles
 template <int ORDER2>
 __global__ __launch_bounds__(THREADS) void vario_terms_kernel(const float* __restrict__ x, const float* __restrict__ y, double* __restrict__ out,
@@ -58,12 +52,6 @@ __global__ __launch_bounds__(THREADS) void vario_terms_kernel(const float* __res
         __syncthreads();
         v_fold_store(v, tid, o0);
     }
-}
-
-__global__ __launch_bounds__(THREADS) void vario_fold_kernel(const double* __restrict__ partial, double* __restrict__ V, long long entries, int n_tiles,
-                                                             int O3) {
-    const long long e = (long long)blockIdx.x * THREADS + threadIdx.x;
-    if (e < entries) v_fold(partial, V, e, n_tiles, O3);
 }
 
 constexpr int P_LDS_MAX = (P_MAX_M + 1) * P_PITCH * 4;  // 67 600 bytes at M = 64: beyond 64 KiB, hence the opt-in
@@ -102,9 +90,7 @@ extern "C" int c2w_escore_pairs(const float* x, const float* y, double* d2, doub
     escore_pairs_kernel<<<(unsigned)grid, escore::THREADS, lds, st>>>(x, y, nc > 1 ? scratch : d2, planes, nc, M, hw);
     int rc = (int)hipGetLastError();
     if (rc || nc == 1) return rc;
-    const long long entries = planes * P;
-    escore_fold_kernel<<<(unsigned)((entries + escore::THREADS - 1) / escore::THREADS), escore::THREADS, 0, st>>>(scratch, d2, entries, nc, P);
-    return (int)hipGetLastError();
+    return c2w_fold_parts<ordered_sum::nan_if_not_finite>(scratch, d2, planes, nc, st, P);
 }
 
 extern "C" int c2w_vario_supported(int H, int W, int R, int M, int order2) { return escore::v_supported(H, W, R, M, order2) ? 1 : 0; }
@@ -131,8 +117,5 @@ extern "C" int c2w_vario_terms(const float* x, const float* y, double* V, double
         default: rc = launch_vario<4>(x, y, out, planes, grid, nt, M, H, W, R, st); break;
     }
     if (rc || nt == 1) return rc;
-    const int O3 = escore::v_offsets(R) * 3;
-    const long long entries = planes * O3;
-    vario_fold_kernel<<<(unsigned)((entries + escore::THREADS - 1) / escore::THREADS), escore::THREADS, 0, st>>>(scratch, V, entries, nt, O3);
-    return (int)hipGetLastError();
+    return c2w_fold_parts<ordered_sum::nan_if_not_finite>(scratch, V, planes, nt, st, escore::v_offsets(R) * 3);
 }

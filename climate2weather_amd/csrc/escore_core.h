@@ -17,17 +17,17 @@
 // (bi <= bj, row-major) and one slice s of the chunk's 64 groups of 4 cells -- groups s, s + S, s + 2 S .. with S = slices(M) threads a
 // tile, so the lanes of a wave read adjacent 16-byte groups -- and keeps its 16 sums in double registers: d = a - b in fp32, d * d in
 // fp32, not fused, added to the double, cells in ascending order.  The S threads of a tile then fold through LDS in thread order and
-// the pairs i < j <= M of the tile are written: to D2 if the plane is one chunk, else to partial[plane][chunk][P], which escore_fold
-// adds in chunk order.  A row block that ends past row M reads row M again and its pairs are dropped.
+// the pairs i < j <= M of the tile are written: to D2 if the plane is one chunk, else to partial[plane][chunk][P], which the shared
+// fold kernel (ordered_sum_launch.h) adds in chunk order.  A row block that ends past row M reads row M again and its pairs are dropped.
 //
 // vario_terms: a workgroup of 256 owns a tile of 8 x 32 cells of one plane and copies the tile with its halo -- R columns on either
 // side, R rows below: the offsets lie in the half plane -- of all M + 1 rows to LDS.  Thread (tid / 32, tid % 32) owns one cell; the 32
 // lanes of half a wave read 32 adjacent floats whatever the pitch.  It walks the offsets four at a time (O is a multiple of 4 at every
 // R), the member loop innermost: g_y and every member term are fp32 (p = 0.5: the correctly rounded square root, p = 1: the absolute
 // value, p = 2: a product), g_x is the fp32 chain of the M terms in member order times the fp32 1 / M, and
-// ((double)g_y - (double)g_x)^2, g_y and g_x join the fold as doubles.  The 12 sums of the four offsets fold through LDS in thread
-// order -- sixteen threads at a time, then the sixteen group totals -- and go to V if the plane is one tile, else to
-// partial[plane][tile][O][3], which vario_fold adds in tile order.  No atomics anywhere: the bits of a plane are fixed by its shape.
+// ((double)g_y - (double)g_x)^2, g_y and g_x join the fold as doubles.  The 12 sums of the four offsets fold by the fixed-order sum of
+// ordered_sum.h (N = 12, nan_if_not_finite) and go to V if the plane is one tile, else to partial[plane][tile][O][3], which the shared
+// fold kernel adds in tile order.  No atomics anywhere: the bits of a plane are fixed by its shape.
 #ifndef C2W_ESCORE_CORE_H
 #define C2W_ESCORE_CORE_H
 
@@ -47,16 +47,15 @@
 #ifndef ESC_VISIT  // the host driver counts the cell pairs here
 #define ESC_VISIT(plane, cell, offset)
 #endif
+#include "ordered_sum.h"
 
 namespace escore {
 
 constexpr int THREADS = 256;
-constexpr int GROUP = 16;  // threads whose sums are added in one go; THREADS / GROUP group totals follow
-constexpr int GROUPS = THREADS / GROUP;
+static_assert(THREADS == ordered_sum::THREADS, "the workgroup the fixed-order sum is written for");
+using ordered_sum::nan_if_not_finite;  // the write policy of every sum here: the kernels find a non-finite input on the result
 
 typedef float F4 __attribute__((vector_size(16)));  // 16 bytes a load; a struct of four floats would be merged through memory
-
-static ESC_HD inline double nan_if_not_finite(double t) { return t - t == 0.0 ? t : (double)__builtin_nanf(""); }
 
 // ================================================================================================================ pairs
 
@@ -162,7 +161,7 @@ static ESC_HD inline void p_stash(const PView& v, const PThread& th, int tid) {
 }
 
 // sum a of tile k is entry k * 16 + a; the threads share the entries round robin: each adds the S threads of the tile in thread order
-// and writes the pair if it is one
+// and writes the pair if it is one; p_fold then writes D2[entry], entry = plane P + p, from the chunks in index order
 static ESC_HD inline void p_fold_store(const PView& v, int tid) {
     const int S = p_slices(v.M), n = p_tiles(v.M) * 16;
     for (int e = tid; e < n; e += THREADS) {
@@ -177,13 +176,8 @@ static ESC_HD inline void p_fold_store(const PView& v, int tid) {
         v.out[(v.plane * p_chunks(v.hw) + v.chunk) * p_pairs(v.M) + p_pair_index(v.M, i, j)] = nan_if_not_finite(t);
     }
 }
-
-// D2[entry], entry = plane P + p: the chunks in index order
 static ESC_HD inline void p_fold(const double* partial, double* d2, long long entry, int nc, int P) {
-    const double* p = partial + (entry / P) * nc * P + entry % P;
-    double t = 0.0;
-    for (int c = 0; c < nc; ++c) t += p[(long long)c * P];
-    d2[entry] = nan_if_not_finite(t);
+    d2[entry] = nan_if_not_finite(ordered_sum::fold_parts(partial, entry, nc, P));
 }
 
 // ================================================================================================================ variogram
@@ -192,7 +186,8 @@ constexpr int V_MAX_M = 16;
 constexpr int V_MAX_R = 8;
 constexpr int V_TH = 8, V_TW = 32;  // the tile: one cell a thread, tid = ti * 32 + tj
 constexpr int V_BATCH = 4;          // offsets between two folds
-constexpr int V_FOLD_DOUBLES = 3 * V_BATCH * (THREADS + GROUPS);
+constexpr int V_SUMS = 3 * V_BATCH;  // sums a thread hands to one fold
+constexpr int V_FOLD_DOUBLES = ordered_sum::lds_doubles<V_SUMS>();
 
 // order2 = 2 p: 1, 2 or 4
 static ESC_BOTH inline bool v_supported(int H, int W, int R, int M, int order2) {
@@ -252,7 +247,7 @@ static ESC_HD inline float v_power(float d) {
     return a * a;
 }
 
-// offsets o0 .. o0 + 3 of the thread's cell: its 12 terms to the fold area
+// offsets o0 .. o0 + 3 of the thread's cell: its 12 terms go straight to the fold area, in the layout of ordered_sum::stash<V_SUMS>
 template <int ORDER2>
 static ESC_HD inline void v_terms(const VView& v, int tid, int o0) {
     ESC_NO_CONTRACT
@@ -297,32 +292,17 @@ static ESC_HD inline void v_terms(const VView& v, int tid, int o0) {
     }
 }
 
-// thread q GROUPS + g adds sum q (of 12) of the threads g GROUP .. g GROUP + GROUP - 1, in thread order
-static ESC_HD inline void v_fold_groups(const VView& v, int tid) {
-    if (tid >= 3 * V_BATCH * GROUPS) return;
-    double* fold = v_fold_area(v);
-    const double* p = fold + (tid / GROUPS) * THREADS + (tid % GROUPS) * GROUP;
-    double t = 0.0;
-    for (int k = 0; k < GROUP; ++k) t += p[k];
-    fold[3 * V_BATCH * THREADS + tid] = t;
-}
-
-// thread q adds the group totals of sum q in group order and writes the entry of offset o0 + q / 3
+// the fold of ordered_sum.h over the fold area at N = V_SUMS: thread q writes sum q, the entry of offset o0 + q / 3; v_fold then
+// writes V[entry], entry = (plane O + o) 3 + s, from the tiles in index order
+static ESC_HD inline void v_fold_groups(const VView& v, int tid) { ordered_sum::fold_groups<V_SUMS>(v_fold_area(v), tid); }
 static ESC_HD inline void v_fold_store(const VView& v, int tid, int o0) {
-    if (tid >= 3 * V_BATCH) return;
-    const double* p = v_fold_area(v) + 3 * V_BATCH * THREADS + tid * GROUPS;
-    double t = 0.0;
-    for (int g = 0; g < GROUPS; ++g) t += p[g];
+    if (tid >= V_SUMS) return;
+    const double t = ordered_sum::fold_total<V_SUMS>(v_fold_area(v), tid);
     const long long O = v_offsets(v.R);
     v.out[((v.plane * v_tiles(v.H, v.W) + v.tile) * O + o0) * 3 + tid] = nan_if_not_finite(t);
 }
-
-// V[entry], entry = (plane O + o) 3 + s: the tiles in index order
 static ESC_HD inline void v_fold(const double* partial, double* V, long long entry, int nt, int O3) {
-    const double* p = partial + (entry / O3) * nt * O3 + entry % O3;
-    double t = 0.0;
-    for (int k = 0; k < nt; ++k) t += p[(long long)k * O3];
-    V[entry] = nan_if_not_finite(t);
+    V[entry] = nan_if_not_finite(ordered_sum::fold_parts(partial, entry, nt, O3));
 }
 
 }  // namespace escore

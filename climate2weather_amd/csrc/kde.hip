@@ -8,6 +8,7 @@
 
 #define KDE_HD __device__ __attribute__((always_inline))
 #define KDE_BOTH __host__ __device__ __attribute__((always_inline))
+#define ORDERED_SUM_HD KDE_HD
 #include "kde_core.h"
 
 namespace {

@@ -35,10 +35,12 @@
 #define KDE_HOST 1
 #include <cmath>
 #endif
+#include "ordered_sum.h"
 
 namespace kde {
 
 constexpr int THREADS = 256;
+static_assert(THREADS == ordered_sum::THREADS, "the workgroup the fixed-order sum is written for");
 constexpr int MAX_N = 1024;           // grid points: four a thread at most
 constexpr int TILE = 4 * THREADS;     // values staged per barrier pair: one 16-byte load a thread
 constexpr int FOLD = 256;             // terms an fp32 chain holds before it joins its double
@@ -199,9 +201,7 @@ static KDE_HD inline void k_store(const KView& v, const KThread<P>& th, int tid,
 // dens[ds][j]: the chunks in index order, then the normalisation, all in double
 static KDE_HD inline void f_fold(const double* partial, const double* h, double* dens, long long ds, int j, long long n, int N) {
     const long long nc = chunks(n);
-    const double* p = partial + ds * nc * N + j;
-    double s = 0.0;
-    for (long long c = 0; c < nc; ++c) s += p[c * N];
+    const double s = ordered_sum::fold_strided(partial + ds * nc * N + j, nc, N);  // fold_parts at entry ds N + j, undivided
     dens[ds * N + j] = s != s ? (double)__builtin_nanf("") : s * (1.0 / ((double)n * h[ds] * SQRT_2PI));
 }
 

@@ -1,9 +1,10 @@
 // Wind power of an ensemble (c2w_hip.h: c2w_wind_power): per cell the hub-height wind speed from the u and v planes and the turbine's
 // power by a table lookup from LDS, per (d, t) plane their sums in double.  wind_power_kernel is the hot path: a workgroup owns one
 // plane or one chunk of it, copies the packed curve into LDS once and reads every value of the two planes once, 16 bytes at a time;
-// wind_fold_kernel adds the chunks of a plane in index order when there are several.  wind_core.h has the table, the lookup, the
-// arithmetic and the index maps; this file is the workgroups around them.  No float atomics, no sum whose order depends on the launch.
-#include "launch.h"
+// the shared fold_parts_kernel (ordered_sum_launch.h) adds the chunks of a plane in index order when there are several.  wind_core.h
+// has the table, the lookup, the arithmetic and the index maps; this file is the workgroups around them.  No float atomics, no sum whose
+// order depends on the launch.
+#include "ordered_sum_launch.h"
 
 #define WIND_HD __device__ __attribute__((always_inline))
 #define WIND_BOTH __host__ __device__ __attribute__((always_inline))
@@ -33,11 +34,6 @@ __global__ __launch_bounds__(THREADS) void wind_power_kernel(const float* __rest
     t_fold_groups(w, tid);
     __syncthreads();
     t_fold_store(w, tid);
-}
-
-__global__ __launch_bounds__(THREADS) void wind_fold_kernel(const double* __restrict__ partial, double* __restrict__ sums, long long entries, int n_chunks) {
-    const long long e = (long long)blockIdx.x * THREADS + threadIdx.x;
-    if (e < entries) f_fold(partial, sums, e, n_chunks);
 }
 
 }  // namespace
@@ -70,7 +66,5 @@ extern "C" int c2w_wind_power(const float* fields, int F, int u_index, int v_ind
                                                                 hub_factor, hw);
     int rc = (int)hipGetLastError();
     if (rc || nc == 1) return rc;
-    const long long entries = planes * 2;
-    wind_fold_kernel<<<(unsigned)((entries + wind::THREADS - 1) / wind::THREADS), wind::THREADS, 0, st>>>(scratch, sums, entries, nc);
-    return (int)hipGetLastError();
+    return c2w_fold_parts<ordered_sum::nan_if_nan, 2>(scratch, sums, planes, nc, st);
 }

@@ -26,9 +26,9 @@
 // wind_power: a workgroup of 256 owns one plane, or one chunk of CHUNK cells of it (a function of hw alone).  A thread owns 4 adjacent
 // cells in each of its ROUNDS rounds and asks for all its 16-byte loads of u and of v before it uses one.  No multiply is fused with an
 // add (the host run and the NumPy restatement give the same bits); the square root is the correctly rounded one.  The fp32 values of a
-// cell join the thread's two double accumulators in cell order; the workgroup folds them through LDS in thread order -- sixteen
-// threads at a time, then the sixteen group totals -- and writes two doubles: to sums if the plane is one chunk, to
-// partial[plane][chunk][2] otherwise, which wind_fold adds in chunk order.  No atomics: a plane's bits are fixed by hw and the table.
+// cell join the thread's two double accumulators in cell order; the workgroup folds them by the fixed-order sum of ordered_sum.h
+// (N = 2, nan_if_nan) and writes two doubles: to sums if the plane is one chunk, to partial[plane][chunk][2] otherwise, which the
+// shared fold kernel adds in chunk order.  No atomics: a plane's bits are fixed by hw and the table.
 #ifndef C2W_WIND_CORE_H
 #define C2W_WIND_CORE_H
 
@@ -44,6 +44,7 @@
 #else
 #define WIND_NO_CONTRACT
 #endif
+#include "ordered_sum.h"
 
 namespace wind {
 
@@ -53,10 +54,9 @@ constexpr int BUCKETS = 256;
 constexpr int SCAN = 2;                 // knots a bucket may hold while the bounded scan serves the curve
 constexpr int ROUNDS = 4;               // rounds of 256 threads x 4 cells a workgroup makes over its chunk
 constexpr int CHUNK = ROUNDS * THREADS * 4;  // 4096 cells
-constexpr int GROUP = 16;               // threads whose accumulators are added in one go; THREADS / GROUP group totals follow
-constexpr int GROUPS = THREADS / GROUP;
-constexpr int LDS_DOUBLES = 2 * THREADS + 2 * GROUPS;
+constexpr int LDS_DOUBLES = ordered_sum::lds_doubles<2>();
 constexpr int MODE_BUCKETS = 0, MODE_BISECT = 1;
+static_assert(THREADS == ordered_sum::THREADS, "the workgroup the fixed-order sum is written for");
 
 struct alignas(16) Pack {
     float v[4];
@@ -265,34 +265,17 @@ static WIND_HD inline void t_cells(const View& w, Thread& th, int tid) {
     }
 }
 
-static WIND_HD inline void t_stash(const View& w, const Thread& th, int tid) {
-    w.lds[tid] = th.acc[0], w.lds[THREADS + tid] = th.acc[1];
-}
-
-// thread s GROUPS + g adds sum s of the threads g GROUP .. g GROUP + GROUP - 1, in thread order
-static WIND_HD inline void t_fold_groups(const View& w, int tid) {
-    if (tid >= 2 * GROUPS) return;
-    const double* p = w.lds + (tid / GROUPS) * THREADS + (tid % GROUPS) * GROUP;
-    double t = 0.0;
-    for (int j = 0; j < GROUP; ++j) t += p[j];
-    w.lds[2 * THREADS + tid] = t;
-}
-
-// thread s adds the group totals of sum s in group order and writes the workgroup's entry; a NaN is written as NaN explicitly
+// the three phases of ordered_sum.h at N = 2: thread s writes the workgroup's entry of sum s, an infinite sum stays; f_fold then
+// writes sums[entry], entry = plane 2 + s, from the chunks in index order
+static WIND_HD inline void t_stash(const View& w, const Thread& th, int tid) { ordered_sum::stash<2>(w.lds, th.acc, tid); }
+static WIND_HD inline void t_fold_groups(const View& w, int tid) { ordered_sum::fold_groups<2>(w.lds, tid); }
 static WIND_HD inline void t_fold_store(const View& w, int tid) {
     if (tid >= 2) return;
-    const double* p = w.lds + 2 * THREADS + tid * GROUPS;
-    double t = 0.0;
-    for (int g = 0; g < GROUPS; ++g) t += p[g];
-    w.out[(w.plane * chunks(w.hw) + w.chunk) * 2 + tid] = t != t ? (double)__builtin_nanf("") : t;
+    const double t = ordered_sum::fold_total<2>(w.lds, tid);
+    w.out[(w.plane * chunks(w.hw) + w.chunk) * 2 + tid] = ordered_sum::nan_if_nan(t);
 }
-
-// sums[entry], entry = plane 2 + s: the chunks in index order
 static WIND_HD inline void f_fold(const double* partial, double* sums, long long entry, int nc) {
-    const double* p = partial + (entry / 2) * nc * 2 + entry % 2;
-    double t = 0.0;
-    for (int c = 0; c < nc; ++c) t += p[c * 2];
-    sums[entry] = t != t ? (double)__builtin_nanf("") : t;
+    sums[entry] = ordered_sum::nan_if_nan(ordered_sum::fold_parts(partial, entry, nc, 2));
 }
 
 }  // namespace wind

@@ -509,8 +509,8 @@ int c2w_quantiles(const float* x, const float* y, const double* q, int Q, int sk
  * memory); every sum runs over the first M rows only.  B from the neighbour gaps times the exact weights k (M - k); the pivot
  * p = x_(M / 2), e_i = x_(i) - p, ebar = (sum e) / M, V = sum (e_i - ebar)^2 / (M - 1), E = ((p - y) + ebar)^2; A = sum |x_(i) - y| / M;
  * no multiply fused with an add.  Identical members give B = 0 and V = 0 exactly.  Per-cell values are fp32; they join four double
- * accumulators per thread in cell order, the workgroup folds those through LDS in thread order (sixteen threads at a time, then the
- * sixteen group totals), and when a plane has several chunks crps_fold_kernel adds them in index order: at most two launches on the
+ * accumulators per thread in cell order, the workgroup folds those by the fixed-order sum of csrc/ordered_sum.h (sixteen threads at a
+ * time, then the sixteen group totals), and when a plane has several chunks fold_parts_kernel adds them in index order: at most two launches on the
  * caller's stream, no atomics, no host read-back, the same bits for a plane wherever it lies in the launch.  Per cell the error is at
  * most (M + 16) 2^-24 s with s the float64 value itself for A, B, V and A^2 for E; a sum's at most (M + 16) 2^-24 times the sum of
  * its cells' s (tests/fp64_crps_ref.py).  scratch: c2w_crps_scratch_bytes(T, F, hw) bytes (0 while a plane is one chunk: the pointer
@@ -548,8 +548,8 @@ int c2w_crps_terms(const float* x, const float* y, double* sums, float* cells, d
  * to LDS once.  The lookup is bucket -> starting knot -> 2 forward steps, none behind a branch, where no bucket holds more than 2 knots (mode 0), a
  * binary search over the intervals otherwise (mode 1: curves whose knots crowd a bucket).  The arithmetic is fp32, no multiply fused
  * with an add, the square root correctly rounded.  Per-cell values join two double accumulators per thread in cell order, the
- * workgroup folds those through LDS in thread order (sixteen threads at a time, then the sixteen group totals), and when a plane has
- * several chunks wind_fold_kernel adds them in index order: at most two launches on the caller's stream, no atomics, no host
+ * workgroup folds those by the fixed-order sum of csrc/ordered_sum.h (sixteen threads at a time, then the sixteen group totals), and when
+ * a plane has several chunks fold_parts_kernel adds them in index order: at most two launches on the caller's stream, no atomics, no host
  * read-back, the same bits for a plane wherever it lies in the launch.  Error against float64 (tests/fp64_wind_ref.py): the speed within
  * 6 * 2^-24 of itself plus 2^-62 c where the squares underflow; the power between the least and the largest value of the float64 curve
  * over the speed's window widened by the rounding of a knot, give or take 9 * 2^-24 of the larger power at the interval's ends; a sum
@@ -586,12 +586,12 @@ int c2w_wind_power(const float* fields, int F, int u_index, int v_index, const v
  * escore_pairs_kernel: a workgroup of 256 owns 256 cells of one plane and copies them, all M + 1 rows, from HBM to LDS once, 16 bytes a
  * load; a thread owns a 4 x 4 tile of row pairs and every S-th group of 4 cells (S a function of M) and keeps 16 double sums:
  * d = a - b in fp32, d * d in fp32, not fused, added to the double in cell order.  The S threads of a tile fold through LDS in thread
- * order; escore_fold_kernel adds the chunks of a plane in index order.  (M + 1) 1040 bytes of LDS, at least 32 KiB: 67 600 at M = 64.
+ * order; fold_parts_kernel (csrc/ordered_sum_launch.h) adds the chunks of a plane in index order.  (M + 1) 1040 bytes of LDS, at least 32 KiB: 67 600 at M = 64.
  * vario_terms_kernel: a workgroup of 256 owns an 8 x 32 tile of one plane and copies it with its halo (R columns either side, R rows
  * below) of all M + 1 rows to LDS; a thread owns a cell and walks the offsets four at a time, the member loop innermost: every term
  * fp32 (p = 0.5 the correctly rounded square root, p = 1 the absolute value, p = 2 a product), g_x the fp32 chain of the M terms in
- * member order times the fp32 1 / M, ((double)g_y - (double)g_x)^2 and the two variograms summed in double, through LDS in thread
- * order (sixteen threads at a time, then the sixteen group totals); vario_fold_kernel adds the tiles in index order.  At most 78 336
+ * member order times the fp32 1 / M, ((double)g_y - (double)g_x)^2 and the two variograms summed in double by the fixed-order sum of
+ * csrc/ordered_sum.h (sixteen threads at a time, then the sixteen group totals); fold_parts_kernel adds the tiles in index order.  At most 78 336
  * bytes of LDS (R = 8, M = 16).  At most two launches each on the caller's stream, no atomics, no host read-back, the same bits for a
  * plane wherever it lies in the launch.  Error against float64 (tests/fp64_escore_ref.py): a D2 entry within 3 * 2^-24 of itself;
  * V[..][0] within (2 M + 8) 2^-24 sum (g_y + g_x)^2 over its pairs, V[..][1] within 3 * 2^-24 and V[..][2] within (M + 4) 2^-24 of

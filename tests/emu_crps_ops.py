@@ -1,8 +1,8 @@
 """TEST DOUBLE for the CRPS launchers (climate2weather_amd.ops: crps_supported, crps_scratch_bytes, crps_terms), on CPU tensors.
 
 It restates the two kernels of csrc/crps.hip in NumPy with the index maps of csrc/crps_core.h written out again in Python -- the chunk
-bounds, the (round, thread, column) -> cell map, the per-thread accumulation order, the fold through LDS sixteen threads at a time and
-the fold over the chunks -- and with the kernel's arithmetic in fp32, operation by operation and in the kernel's order: the sort (any
+bounds, the (round, thread, column) -> cell map, the per-thread accumulation order; the fold through LDS and the fold over the chunks
+are emu_ordered_sum's -- and with the kernel's arithmetic in fp32, operation by operation and in the kernel's order: the sort (any
 correct sort gives the network's rows), the gaps times the exact weights, the pivot x_(M / 2), the offsets against it, no multiply fused
 with an add.  Unsupported shapes answer False and write nothing.  ``install`` also makes the crps module treat CPU tensors as device
 tensors, so the host code takes the launcher's branch.
@@ -14,10 +14,11 @@ import sys
 import numpy as np
 import torch
 
+from emu_ordered_sum import fold_parts, fold_workgroup, nan_if_nan, seq_sum
+
 CALLS = []  # (M, T, F, hw, with_cells) of every call that reached the launcher
 
-THREADS, MAX_M, CHUNK, GROUP = 256, 64, 4096, 16
-GROUPS = THREADS // GROUP
+THREADS, MAX_M, CHUNK = 256, 64, 4096
 
 
 # ------------------------------------------------------------------------------------------------------------------ crps_core.h, restated
@@ -84,28 +85,15 @@ def cell_terms32(x, y):
     return out
 
 
-def fold_workgroup(terms, V):
-    """terms (4, n) fp32 of one chunk in cell order -> (4,) float64: per thread in (round, column) order, then through LDS: sixteen
-    threads at a time in thread order, then the sixteen group totals"""
+def thread_sums(terms, V):
+    """terms (4, n) fp32 of one chunk in cell order -> (4, 256) float64: what each thread accumulates, in (round, column) order"""
     n = terms.shape[1]
     per_round = V * THREADS
     R = (n + per_round - 1) // per_round
     padded = np.zeros((4, R * per_round), np.float64)  # a thread without cells adds nothing: its accumulator stays +0
     padded[:, :n] = terms
-    t = padded.reshape(4, R, THREADS, V)
-    with np.errstate(invalid="ignore"):
-        acc = np.zeros((4, THREADS), np.float64)
-        for r in range(R):
-            for c in range(V):
-                acc = acc + t[:, r, :, c]
-        g = acc.reshape(4, GROUPS, GROUP)
-        tot = np.zeros((4, GROUPS), np.float64)
-        for j in range(GROUP):
-            tot = tot + g[:, :, j]
-        out = np.zeros(4, np.float64)
-        for k in range(GROUPS):
-            out = out + tot[:, k]
-    return np.where(np.isnan(out), np.nan, out)
+    t = padded.reshape(4, R, THREADS, V).transpose(0, 2, 1, 3).reshape(4, THREADS, R * V)
+    return seq_sum(t, 2)
 
 
 def crps_terms(x, y, sums, cells, scratch, M, T, F, hw):
@@ -131,14 +119,10 @@ def crps_terms(x, y, sums, cells, scratch, M, T, F, hw):
             terms = cell_terms32(xs[:, pl, lo:hi], ys[pl, lo:hi])
             if cl is not None:
                 cl[:, pl, lo:hi] = terms
-            part[pl, c] = fold_workgroup(terms, V)
+            part[pl, c] = fold_workgroup(thread_sums(terms, V), nan_if_nan)
     if nc > 1:
         scratch.reshape(-1).numpy()[:T * F * nc * 4] = part.reshape(-1)
-    with np.errstate(invalid="ignore"):
-        tot = np.zeros((T * F, 4), np.float64)
-        for c in range(nc):
-            tot = tot + part[:, c]
-    out[:T * F * 4] = (np.where(np.isnan(tot), np.nan, tot) if nc > 1 else part[:, 0]).reshape(-1)
+    out[:T * F * 4] = (fold_parts(part, 1, nan_if_nan) if nc > 1 else part[:, 0]).reshape(-1)
     return True
 
 

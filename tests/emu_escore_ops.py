@@ -2,7 +2,8 @@
 
 It restates the kernels of csrc/escore.hip in NumPy with the index maps of csrc/escore_core.h written out again in Python -- the
 chunks of 256 cells, the 4 x 4 pair tiles and their S slices of every S-th group of 4 cells, the 8 x 32 cell tiles, the offset
-enumeration, the folds through LDS in thread order and over the chunks and tiles -- and with the kernels' arithmetic in fp32,
+enumeration, the fold of a pair tile's threads (the variogram's fold through LDS and the folds over the chunks and tiles are
+emu_ordered_sum's) -- and with the kernels' arithmetic in fp32,
 operation by operation and in the kernels' order, no multiply fused with an add.  Unsupported shapes answer False and write nothing.
 ``install`` also makes the multivariate module treat CPU tensors as device tensors, so the host code takes the launcher's branch.
 """
@@ -13,26 +14,13 @@ import sys
 import numpy as np
 import torch
 
+from emu_ordered_sum import GROUPS, fold_parts, fold_workgroup, nan_if_not_finite, seq_sum
+
 CALLS = []  # ("pairs", M, planes, hw) / ("vario", M, planes, H, W, R, order2) of every call that reached a launcher
 
-THREADS, GROUP = 256, 16
-GROUPS = THREADS // GROUP
+THREADS = 256
 P_MAX_M, P_CHUNK = 64, 256
 V_MAX_M, V_MAX_R, V_TH, V_TW, V_BATCH = 16, 8, 8, 32, 4
-
-
-def _nan_if_not_finite(t):
-    return np.where(np.isfinite(t), t, np.nan)
-
-
-def _seq_sum(a, axis):
-    """the sum along `axis` in index order from +0, one addition after the other (numpy.sum adds pairwise)"""
-    a = np.moveaxis(a, axis, 0)
-    t = np.zeros(a.shape[1:], np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for k in range(a.shape[0]):
-            t = t + a[k]
-    return t
 
 
 # ------------------------------------------------------------------------------------------------------------------ pairs
@@ -87,9 +75,9 @@ def chunk_pairs(rows, M):
             assert sq.dtype == f32
             # thread s of the tile takes the groups of 4 cells s, s + S, ..: (k, s, c) -> per thread the cells in ascending order
             per_thread = sq.astype(np.float64).reshape(-1, P_CHUNK // 4 // S, S, 4).transpose(0, 2, 1, 3).reshape(-1, S, P_CHUNK // S)
-            out[p:p + M - i] = _seq_sum(_seq_sum(per_thread, 2), 1)
+            out[p:p + M - i] = seq_sum(seq_sum(per_thread, 2), 1)  # the S threads of a tile in thread order: p_fold_store's own scheme
             p += M - i
-    return _nan_if_not_finite(out)
+    return nan_if_not_finite(out)
 
 
 def escore_pairs(x, y, d2, scratch, M, planes, hw):
@@ -110,7 +98,7 @@ def escore_pairs(x, y, d2, scratch, M, planes, hw):
             part[pl, c] = chunk_pairs(rows[:, c * P_CHUNK:(c + 1) * P_CHUNK], M)
     if nc > 1:
         scratch.reshape(-1).numpy()[:planes * nc * P] = part.reshape(-1)
-    out = _nan_if_not_finite(_seq_sum(part, 1)) if nc > 1 else part[:, 0]
+    out = fold_parts(part, 1, nan_if_not_finite) if nc > 1 else part[:, 0]
     d2.reshape(-1).numpy()[:planes * P] = out.reshape(-1)
     return True
 
@@ -176,15 +164,14 @@ def plane_terms(x, y, di, dj, order2):
     return out
 
 
-def fold_tiles(terms):
-    """terms (3, H, W) float64 -> (tiles, 3): per tile of 8 x 32 cells the 256 threads in thread order, sixteen at a time, then the
-    sixteen group totals"""
+def tile_threads(terms):
+    """terms (3, H, W) float64 -> (tiles, 3, 256): per tile of 8 x 32 cells what each of its threads hands to the fold, thread
+    tid = ti * 32 + tj owning cell (ti, tj) of the tile"""
     _, H, W = terms.shape
     tw = (W + V_TW - 1) // V_TW
     padded = np.zeros((3, H, tw * V_TW), np.float64)
     padded[:, :, :W] = terms
-    t = padded.reshape(3, H // V_TH, V_TH, tw, V_TW).transpose(1, 3, 0, 2, 4).reshape(-1, 3, GROUPS, GROUP)  # (tile, sum, group, thread)
-    return _nan_if_not_finite(_seq_sum(_seq_sum(t, 3), 2))
+    return padded.reshape(3, H // V_TH, V_TH, tw, V_TW).transpose(1, 3, 0, 2, 4).reshape(-1, 3, THREADS)  # (tile, sum, thread)
 
 
 def vario_terms(x, y, V, scratch, M, planes, H, W, R, order2):
@@ -203,10 +190,10 @@ def vario_terms(x, y, V, scratch, M, planes, H, W, R, order2):
     for pl in range(planes):
         for o in range(O):
             di, dj = offset_of(R, o)
-            part[pl, :, o] = fold_tiles(plane_terms(xs[:, pl], ys[pl], di, dj, order2))
+            part[pl, :, o] = fold_workgroup(tile_threads(plane_terms(xs[:, pl], ys[pl], di, dj, order2)), nan_if_not_finite)
     if nt > 1:
         scratch.reshape(-1).numpy()[:planes * nt * O * 3] = part.reshape(-1)
-    out = _nan_if_not_finite(_seq_sum(part, 1)) if nt > 1 else part[:, 0]
+    out = fold_parts(part, 1, nan_if_not_finite) if nt > 1 else part[:, 0]
     V.reshape(-1).numpy()[:planes * O * 3] = out.reshape(-1)
     return True
 

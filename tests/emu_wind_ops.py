@@ -2,8 +2,8 @@
 wind_scratch_bytes, wind_power), on CPU tensors.
 
 It restates csrc/wind_core.h in NumPy: the table builder byte for byte (the fp32 knots, the slopes formed in float64 from the rounded
-knots, the bucket index and the mode), the chunk bounds, the (round, thread, column) -> cell map, the per-thread accumulation order,
-the fold through LDS sixteen threads at a time and the fold over the chunks -- and the kernel's arithmetic in fp32, operation by
+knots, the bucket index and the mode), the chunk bounds, the (round, thread, column) -> cell map, the per-thread accumulation order
+(the fold through LDS and the fold over the chunks are emu_ordered_sum's) -- and the kernel's arithmetic in fp32, operation by
 operation and in the kernel's order, no multiply fused with an add.  The interval of a speed is found by a plain search over the fp32
 knots: the bucket index and the bisection of the kernel are two ways to the same interval, and tests/host_wind_main.cpp holds both to
 this restatement bit for bit.  Unsupported shapes answer False and write nothing.  ``install`` also makes the windpower module treat CPU
@@ -16,11 +16,12 @@ import sys
 import numpy as np
 import torch
 
+from emu_ordered_sum import fold_parts, fold_workgroup, nan_if_nan, seq_sum
+
 CALLS = []  # (planes, F, u, v, K, hw, with_derived) of every call that reached the launcher
 
-THREADS, MAX_K, BUCKETS, SCAN, ROUNDS, GROUP = 256, 256, 256, 2, 4, 16
+THREADS, MAX_K, BUCKETS, SCAN, ROUNDS = 256, 256, 256, 2, 4
 CHUNK = ROUNDS * THREADS * 4
-GROUPS = THREADS // GROUP
 MODE_BUCKETS, MODE_BISECT = 0, 1
 F32_MAX = float(np.finfo(np.float32).max)
 f32 = np.float32
@@ -130,26 +131,13 @@ def cell_values32(u, v, hub, xf, pf, slope, p_last):
     return s, p
 
 
-def fold_workgroup(vals):
-    """vals (2, n) fp32 of one chunk in cell order -> (2,) float64: per thread in (round, column) order, then through LDS: sixteen
-    threads at a time in thread order, then the sixteen group totals"""
+def thread_sums(vals):
+    """vals (2, n) fp32 of one chunk in cell order -> (2, 256) float64: what each thread accumulates, in (round, column) order"""
     n = vals.shape[1]
     padded = np.zeros((2, CHUNK), np.float64)  # a thread without cells adds nothing: its accumulator stays +0
     padded[:, :n] = vals
-    t = padded.reshape(2, ROUNDS, THREADS, 4)
-    with np.errstate(invalid="ignore"):
-        acc = np.zeros((2, THREADS), np.float64)
-        for r in range(ROUNDS):
-            for c in range(4):
-                acc = acc + t[:, r, :, c]
-        g = acc.reshape(2, GROUPS, GROUP)
-        tot = np.zeros((2, GROUPS), np.float64)
-        for j in range(GROUP):
-            tot = tot + g[:, :, j]
-        out = np.zeros(2, np.float64)
-        for k in range(GROUPS):
-            out = out + tot[:, k]
-    return np.where(np.isnan(out), np.nan, out)
+    t = padded.reshape(2, ROUNDS, THREADS, 4).transpose(0, 2, 1, 3).reshape(2, THREADS, ROUNDS * 4)
+    return seq_sum(t, 2)
 
 
 def wind_power(fields, F, u_index, v_index, table, K, hub, sums, derived, scratch, planes, hw):
@@ -177,14 +165,10 @@ def wind_power(fields, F, u_index, v_index, table, K, hub, sums, derived, scratc
             s, p = cell_values32(x[pl, u_index, lo:hi], x[pl, v_index, lo:hi], hub, xf, pf, slope, p_last)
             if dv is not None:
                 dv[pl, 0, lo:hi], dv[pl, 1, lo:hi] = s, p
-            part[pl, c] = fold_workgroup(np.stack([s, p]))
+            part[pl, c] = fold_workgroup(thread_sums(np.stack([s, p])), nan_if_nan)
     if nc > 1:
         scratch.reshape(-1).numpy()[:planes * nc * 2] = part.reshape(-1)
-    with np.errstate(invalid="ignore"):
-        tot = np.zeros((planes, 2), np.float64)
-        for c in range(nc):
-            tot = tot + part[:, c]
-    out[:planes * 2] = (np.where(np.isnan(tot), np.nan, tot) if nc > 1 else part[:, 0]).reshape(-1)
+    out[:planes * 2] = (fold_parts(part, 1, nan_if_nan) if nc > 1 else part[:, 0]).reshape(-1)
     return True
 
 

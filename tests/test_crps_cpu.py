@@ -328,9 +328,12 @@ def test_support_predicate_and_chunking_agree():
     for hw, M, want in ((4, 1, True), (16384, 64, True), (66, 8, False), (64, 65, False), (64, 0, False), (0, 8, False)):
         assert emu_crps_ops.crps_supported(hw, M) is want
     core = open(os.path.join(ROOT, "climate2weather_amd", "csrc", "crps_core.h")).read()
-    for text in ("THREADS = 256", "MAX_M = 64", "CHUNK = 4096", "GROUP = 16", "hw % 4 == 0 && M >= 1 && M <= MAX_M",
+    for text in ("THREADS = 256", "MAX_M = 64", "CHUNK = 4096", "hw % 4 == 0 && M >= 1 && M <= MAX_M",
                  "M <= 8 ? 8 : M <= 16 ? 16 : M <= 32 ? 32 : 64", "K <= 16 ? 4 : K == 32 ? 2 : 1"):
         assert text in core, text
+    shared = open(os.path.join(ROOT, "climate2weather_amd", "csrc", "ordered_sum.h")).read()
+    for text in ("THREADS = 256", "GROUP = 16"):
+        assert text in shared, text
     assert [emu_crps_ops.rows_of(M) for M in (1, 8, 9, 16, 17, 32, 33, 64)] == [8, 8, 16, 16, 32, 32, 64, 64]
     assert [emu_crps_ops.chunks(hw) for hw in (4, 4096, 4100, 16384)] == [1, 1, 2, 4]  # a function of hw alone
     assert emu_crps_ops.crps_scratch_bytes(1457, 4, 16384) == 1457 * 4 * 4 * 4 * 8 and emu_crps_ops.crps_scratch_bytes(1457, 4, 4096) == 0

@@ -451,7 +451,10 @@ def test_support_predicates_and_maps_agree():
                                    (8, 8, 1, 17, 1, False), (8, 8, 1, 0, 1, False), (8, 8, 1, 1, 3, False)):
         assert emu_escore_ops.vario_supported(H, W_, Rr, M, o2) is want
     core = open(os.path.join(ROOT, "climate2weather_amd", "csrc", "escore_core.h")).read()
-    for text in ("THREADS = 256", "GROUP = 16", "P_MAX_M = 64", "P_CHUNK = 256", "P_PITCH = P_CHUNK + 4", "V_MAX_M = 16", "V_MAX_R = 8", "V_TH = 8, V_TW = 32",
+    shared = open(os.path.join(ROOT, "climate2weather_amd", "csrc", "ordered_sum.h")).read()
+    for text in ("THREADS = 256", "GROUP = 16"):
+        assert text in shared, text
+    for text in ("THREADS = 256", "P_MAX_M = 64", "P_CHUNK = 256", "P_PITCH = P_CHUNK + 4", "V_MAX_M = 16", "V_MAX_R = 8", "V_TH = 8, V_TW = 32",
                  "V_BATCH = 4", "hw >= 4 && hw % 4 == 0 && M >= 1 && M <= P_MAX_M", "H % 8 == 0 && W % 8 == 0 && R >= 1 && R <= V_MAX_R && M >= 1 && M <= V_MAX_M"):
         assert text in core, text
     assert [emu_escore_ops.tiles(M) for M in (1, 3, 4, 7, 8, 16, 33, 64)] == [1, 1, 3, 3, 6, 15, 45, 153]

@@ -472,9 +472,12 @@ def test_support_predicate_scratch_and_chunking_agree():
     for hw, K, want in ((4, 2, True), (16384, 256, True), (66, 8, False), (64, 257, False), (64, 1, False), (0, 8, False)):
         assert emu_wind_ops.wind_supported(hw, K) is want and wind_ops.wind_supported(hw, K) is want
     core = open(os.path.join(ROOT, "climate2weather_amd", "csrc", "wind_core.h")).read()
-    for text in ("THREADS = 256", "MAX_K = 256", "BUCKETS = 256", "SCAN = 2", "ROUNDS = 4", "CHUNK = ROUNDS * THREADS * 4", "GROUP = 16",
+    for text in ("THREADS = 256", "MAX_K = 256", "BUCKETS = 256", "SCAN = 2", "ROUNDS = 4", "CHUNK = ROUNDS * THREADS * 4",
                  "hw >= 4 && hw % 4 == 0 && K >= 2 && K <= MAX_K", "32 + 16 * (K - 1) + 2 * BUCKETS"):
         assert text in core, text
+    shared = open(os.path.join(ROOT, "climate2weather_amd", "csrc", "ordered_sum.h")).read()
+    for text in ("THREADS = 256", "GROUP = 16"):
+        assert text in shared, text
     assert emu_wind_ops.CHUNK == 4096 and [emu_wind_ops.chunks(hw) for hw in (4, 4096, 4100, 16384)] == [1, 1, 2, 4]  # a function of hw alone
     for planes, hw in ((2048, 16384), (2048, 4096), (3, 4100), (1, 4), (0, 64)):
         want = planes * emu_wind_ops.chunks(hw) * 2 * 8 if emu_wind_ops.chunks(hw) > 1 and planes > 0 else 0

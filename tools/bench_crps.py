@@ -5,7 +5,7 @@
 
 For every MEMBERSxTIMES of CONFIGS, on MEMBERS x TIMES x VARS fields of 128 x 128 against TIMES x VARS truth fields (the defaults are
 two ensembles of the same 537 MB), timed alternately in ROUNDS blocks of ITERS calls each:
-  kernel        ops.crps_terms without the per-cell output: crps_terms_kernel and, a plane being four chunks, crps_fold_kernel;
+  kernel        ops.crps_terms without the per-cell output: crps_terms_kernel and, a plane being four chunks, the shared fold_parts_kernel;
                 its bytes are the samples and the truth, each read once
   kernel_cells  the same with the (4, T, F, hw) per-cell output written
   torch_fp32    the same four sums through torch in fp32: torch.sort(dim=0), the gaps times the weights, the pivoted moments, the

@@ -6,7 +6,7 @@
 For every MEMBERSxTIMESxSIDE of CONFIGS, on MEMBERS x TIMES x VARS fields of SIDE x SIDE with the wind components in variables 2 and 3
 and a 61-knot curve (0.5 m/s steps), timed alternately in ROUNDS blocks of ITERS calls each, back to back:
   kernel          wind_ops.wind_power without the per-cell output: wind_power_kernel and, where a plane has several chunks,
-                  wind_fold_kernel; its bytes are the u and the v planes, each read once (2 / VARS of the tensor)
+                  the shared fold_parts_kernel; its bytes are the u and the v planes, each read once (2 / VARS of the tensor)
   kernel_derived  the same with the (planes, 2, hw) per-cell speed and power written
   torch_fp32      the same two sums through torch in fp32: sqrt, bucketize, gather, the reductions over a plane in float64
   general         windpower._general: the package's own float64 route, chunked (one call per round)
