@@ -156,6 +156,9 @@ __device__ __forceinline__ float sigmoid_f(float a) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * a));
 }
 __device__ __forceinline__ float silu_f(float a) { return a * sigmoid_f(a); }
+// ReLU that keeps NaN, as torch.relu does: fmaxf(a, 0.f) is v_max_f32, which under IEEE mode returns the other operand for a NaN, so a
+// NaN born inside a ReLU network (inf - inf after an fp16 overflow) was erased by the next activation and never reached the grad scaler
+__device__ __forceinline__ float relu_f(float a) { return a < 0.f ? 0.f : a; }
 __device__ __forceinline__ float dsilu_f(float a) {
     const float s = sigmoid_f(a);
     return s * (1.0f + a * (1.0f - s));

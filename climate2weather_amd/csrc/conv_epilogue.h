@@ -45,7 +45,7 @@ __device__ __forceinline__ void epi_acc_to_lds_impl(char* O, int OS, const f32x4
             for (int r = 0; r < 4; ++r) {
                 v[r] = acc[m][n][r] + bv[m][r];
                 if constexpr (ACTK == 1) v[r] = silu_f(v[r]);
-                if constexpr (ACTK == 2) v[r] = fmaxf(v[r], 0.f);
+                if constexpr (ACTK == 2) v[r] = relu_f(v[r]);
             }
             if constexpr (sizeof(T) == 4) {
                 *(f32x4_t*)(O + row * OS + col * 4) = (f32x4_t){v[0], v[1], v[2], v[3]};
@@ -83,7 +83,7 @@ __device__ __forceinline__ void epi_acc_to_lds_n(char* O, int OS, const f32x4_t 
             for (int r = 0; r < 4; ++r) {
                 v[r] = acc[m][n][r] + bv[m][r];
                 if (act == C2W_ACT_SILU) v[r] = silu_f(v[r]);  // (wave-uniform; 32 values per lane here, not 64: no separate instantiations)
-                if (act == C2W_ACT_RELU) v[r] = fmaxf(v[r], 0.f);
+                if (act == C2W_ACT_RELU) v[r] = relu_f(v[r]);
             }
             if constexpr (sizeof(T) == 4) {
                 *(f32x4_t*)(O + row * OS + col * 4) = (f32x4_t){v[0], v[1], v[2], v[3]};
@@ -616,7 +616,7 @@ struct EpiStore {
                     unpack16<T>(v[i], a_);
 #pragma unroll
                     for (int e = 0; e < PER16; ++e) {
-                        h_[e] = fmaxf(a_[e], 0.f);
+                        h_[e] = relu_f(a_[e]);
                         d_[e] = a_[e] > 0.f ? 1.f : 0.f;
                     }
                     if (st) {

@@ -278,7 +278,7 @@ __global__ void conv_naive_kernel(const C2wConvArgs p) {
         }
         if (p.bias && co < p.wrows) acc += p.bias[co];
         if (p.act == C2W_ACT_SILU) acc = silu_f(acc);
-        if (p.act == C2W_ACT_RELU) acc = fmaxf(acc, 0.f);
+        if (p.act == C2W_ACT_RELU) acc = relu_f(acc);
         const size_t off = (size_t)Q * p.ldy + co;
         if (p.mul) {
             float g = Elem<T>::ld((const T*)p.mul + off);
@@ -295,7 +295,7 @@ __global__ void conv_naive_kernel(const C2wConvArgs p) {
         if (p.act == C2W_ACT_RELU_PAIR && p.y2) {
             Elem<T>::st((T*)p.y + off, acc);
             const float a_ = Elem<T>::ld((const T*)p.y + off);  // as stored
-            Elem<T>::st((T*)p.y + off, fmaxf(a_, 0.f));
+            Elem<T>::st((T*)p.y + off, relu_f(a_));
             Elem<T>::st((T*)p.y2 + off, a_ > 0.f ? 1.f : 0.f);
             continue;
         }
@@ -406,7 +406,7 @@ extern "C" int c2w_conv_loss_supported(const C2wConvArgs* a, int dtype) {
     if (a->mode != C2W_CONV_S1 || a->wrows > 80 || a->Cout > 128 || a->ldy != 128 || a->res != nullptr || a->mul != nullptr || a->y2 != nullptr ||
         a->act != C2W_ACT_NONE || a->ln_x != nullptr || a->lnf_y != nullptr || (a->flags & C2W_CONV_POOL2) != 0)
         return 0;
-    if (a->loss_sum != nullptr && (a->loss_eps == nullptr || a->loss_C <= 0 || a->loss_C > a->wrows || (a->loss_lde & 7) != 0 || a->loss_lde < a->loss_C ||
+    if (a->loss_sum != nullptr && (a->loss_eps == nullptr || a->loss_C <= 0 || a->loss_C != a->wrows || (a->loss_lde & 7) != 0 || a->loss_lde < a->loss_C ||
                                    a->loss_lde > 128))
         return 0;
     const C2wKnobs& k = c2w_knobs();

@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const C2wConv
         for (int s_ = 0; s_ < 8; ++s_) v += part[s_][e >> 2][e & 3];  // split 0 first: a fixed order
         v += (p.bias != nullptr && c + e < p.wrows) ? p.bias[c + e] : 0.f;
         if (p.act == C2W_ACT_SILU) v = silu_f(v);
-        if (p.act == C2W_ACT_RELU) v = fmaxf(v, 0.f);
+        if (p.act == C2W_ACT_RELU) v = relu_f(v);
         f[e] = v;
     }
     if (p.mul != nullptr || p.res != nullptr) {  // on the value as the unsplit kernel stages it: rounded to the storage type first

@@ -1226,7 +1226,7 @@ __global__ __launch_bounds__(256) void gemv_f32_kernel(const float* __restrict__
     s = wave_sum(s);
     if (lane == 0) {
         s += bias != nullptr ? bias[r] : 0.f;
-        y[r] = act == C2W_ACT_SILU ? silu_f(s) : (act == C2W_ACT_RELU ? fmaxf(s, 0.f) : s);
+        y[r] = act == C2W_ACT_SILU ? silu_f(s) : (act == C2W_ACT_RELU ? relu_f(s) : s);
     }
 }
 

@@ -161,9 +161,11 @@ int c2w_conv_lnbwd_supported(const C2wConvArgs* args, int dtype);
 /* 1 when c2w_conv_forward takes lnf_mean / res_rstd + res_mean + res_m / C2W_CONV_NO_Y for this geometry (c2w_conv_lnfwd_supported's
  * conditions on the 16x16-tile kernel).  Elsewhere those fields make the call fail with C2W_ERR_BAD_SHAPE. */
 int c2w_conv_lnfwd_chain_supported(const C2wConvArgs* args, int dtype);
-/* 1 when c2w_conv_forward can run args with the fused training loss (loss_sum / loss_seed / loss_gscale / loss_C): 16-bit, 3x3
- * stride-1 on the 16x16-tile kernel, at most 80 weight rows in rows of 128 channels (the network-output conv, model/nn.py:194),
- * loss_C <= wrows, no res / mul / act / y2 / LayerNorm fusion.  Otherwise callers run the conv and c2w_mse_loss_grad[_noise]. */
+/* 1 when c2w_conv_forward can run args with the fused training loss (loss_sum / loss_eps / loss_gscale / loss_C / loss_lde): 16-bit,
+ * 3x3 stride-1 on the 16x16-tile kernel, at most 80 weight rows in rows of 128 channels (the network-output conv, model/nn.py:194),
+ * loss_C == wrows (the epilogue takes every channel below loss_lde into the loss: channels [wrows, loss_lde) are zero in the tile and in
+ * loss_eps, channels [loss_C, wrows) would not be), no res / mul / act / y2 / LayerNorm fusion.  Otherwise callers run the conv and
+ * c2w_mse_loss_grad[_noise]. */
 int c2w_conv_loss_supported(const C2wConvArgs* args, int dtype);
 /* Workgroups per output tile c2w_conv_forward can deal the K chunks of these arguments to (1: no split -- geometry outside the 8x16-tile
  * kernels, fused epilogues other than bias / activation / mul / res, or a launch that already has a workgroup per CU), and through

@@ -35,6 +35,25 @@ dm receives the fp32 rows before the residual (:283, :362).  LayerNorm (pointwis
 q = sum c^2, rs = 1/sqrt(q/den + eps), out = c rs -- the statistics' errors propagate through these same rules, so (x - mean) * rstd
 carries the error of the mean in c and the error of q in rs.
 
+ReLU adds no rounding and is 1-Lipschitz, so the error of its argument passes through unchanged: C2W_ACT_RELU is max(v, 0) on the
+accumulator + bias before the rounding into the tile (conv_epilogue.h:48 / :86; the split-K reduction conv_patch.hip:1199; the direct
+kernel conv_igemm.hip:281); C2W_ACT_RELU_PAIR is y = max(a, 0) of the value a as stored, after the multiplier / residual and the rounding
+of :599 (:614-625; conv_igemm.hip:295-300).  Its second output y2 = (a > 0) is discontinuous and gets no numeric bound: the rule is
+consistency with the first, y2 == (y > 0) on every element (assert_mask_consistent) -- with y held to its bound the mask is determined.
+NaN passes through max(., 0) as it does through torch.relu (common.h relu_f); assert_nan_footprint holds the kernel to the reference's NaNs.
+
+Kept statistics (finish_ln_rows_stored, conv_epilogue.h:311-359): the operands are the normalised rows xhat and their 1/sigma rs, exact as
+given; g is the tile as stored (:330).  sum g and sum g * xhat are fp32 sums over the row's 128 channels (:335-336, the 16 lanes by
+sub16); c0 = sum g * (1/128) * rs and c2 = sum(g xhat) * (1/den) * rs are two products each (:339-340); o = g * rs - c0 - xhat * c2
+(:344-345: two products, two subtractions -- where the compiler fuses a product with its subtraction one rounding leaves, so the bound
+holds either way); dm receives the fp32 rows (:346), the residual is added in fp32 (:352) and the sum rounded once (:356).
+
+Chain form (finish_lnf<RESN>, conv_epilogue.h:417-513): the residual is rebuilt from the normalised rows h (exact operands) as
+x = h * rcp(rstd) + (mean - m): rcp is a 1-ulp instruction, counted as K_ULP ulps (:454), one subtraction and a product + a sum (:475;
+fused into one fma it rounds once less).  u = tile + x in fp32 (:478).  Where y is written it is u rounded to T (:481) and the LayerNorm
+reads that value back (:486); with C2W_CONV_NO_Y nothing is rounded and the LayerNorm sees the fp32 sum (:479-487).  The LayerNorm is the
+arithmetic above (:488-504); its mean (:494) and 1/sigma (:501) are stored as fp32 (:509-510).
+
 Attention (attention.hip, attention_mfma.hip): three routes with different arithmetic -- VALU (fp32 P / dP / dS, expf), T64 (one
 64-key block: P normalised then rounded to T, delta inside the kernel) and BLOCKS (online softmax: P rounded unnormalised, accumulators
 rescaled by alpha, delta from rowdot) -- each restated in attention_forward / attention_backward, whose docstrings cite every rounding
@@ -62,7 +81,7 @@ C_ACC = 8.0
 K_ULP = 4.0
 SILU_SLOPE, DSILU_SLOPE = 1.0998, 0.5
 CONV_1X1, CONV_S1, CONV_S2, CONV_UP, CONV_TS2 = 0, 1, 2, 3, 4  # include/c2w_hip.h
-ACT_NONE, ACT_SILU, ACT_SILU_PAIR = 0, 1, 2
+ACT_NONE, ACT_SILU, ACT_SILU_PAIR, ACT_RELU, ACT_RELU_PAIR = 0, 1, 2, 3, 4
 MUL_PLAIN, MUL_DSILU = 0, 1
 STORAGE = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}  # the library's dtype codes
 D = torch.float64
@@ -134,6 +153,17 @@ def _silu(a):
     s = _sigmoid(a.v)
     v = a.v * s
     return V(v, SILU_SLOPE * a.e + K_ULP * U32 * v.abs())
+
+
+def _relu(a):
+    """max(v, 0): 1-Lipschitz and exact, so the argument's error passes through; NaN stays NaN (torch.relu)"""
+    return V(torch.relu(a.v), a.e)
+
+
+def _rcp(a):
+    """v_rcp_f32 of an exact operand: a 1-ulp instruction under K_ULP"""
+    v = 1.0 / a.v
+    return V(v, K_ULP * U32 * v.abs())
 
 
 def _dsilu(a):
@@ -260,6 +290,15 @@ def ln_backward_rows(g, u, C, eps, unbiased):
     return o
 
 
+def ln_backward_rows_stored(g, xh, rs, C, unbiased):
+    """the fp32 rows o = rs * (g - mean(g) - xhat * sum(g xhat) / den) of finish_ln_rows_stored (conv_epilogue.h:335-346): g the stored
+    tile as V rows, xh (rows, C) and rs (rows,) the kept operands in fp64, exact as given"""
+    xh, rs = V(xh), V(rs.unsqueeze(1).expand_as(g.v))
+    c0 = _mul(_bc(_scale(_sum(g, 1), 1.0 / C), g), rs)                                          # :339
+    c2 = _mul(_bc(_scale(_sum(_mul(g, xh), 1), 1.0 / (C - 1 if unbiased else C)), g), rs)        # :340
+    return _sub(_sub(_mul(g, rs), c0), _mul(xh, c2))                                              # :344-345
+
+
 def dm_sums(o, npix, HW, C, ldm):
     """dm[b] (or dm) += the pixel sum of the rows o: per image with ldm, all pixels into one row without"""
     if ldm:
@@ -280,9 +319,13 @@ def add_bias(acc, bias, g):
 
 
 def conv(x, w, g, dtype, bias=None, act=ACT_NONE, res=None, mul=None, mulmode=MUL_PLAIN, y2=False, pool2=False, lnf=None, ln=None,
-         kvalid=0, pre=None):
-    """c2w_conv_forward's outputs as V: dict with 'y' (rows (npix or npix/4, Cout)), and where asked 'y2', 'hn' + 'rstd' (lnf), 'dm' (ln).
-    lnf / ln: dict(m, ldm, eps, unbiased[, x]) as in ops.conv (ln['x'] = the LayerNorm input rows, recomputed statistics).
+         kvalid=0, pre=None, resn=None, no_y=False):
+    """c2w_conv_forward's outputs as V: dict with 'y' (rows (npix or npix/4, Cout); absent with no_y), and where asked 'y2', 'hn' + 'rstd'
+    + 'mean' (lnf), 'dm' + 'o' (ln).
+    lnf / ln: dict(m, ldm, eps, unbiased[, x]) as in ops.conv (ln['x'] = the LayerNorm input rows, recomputed statistics; with ln['rstd']
+    the normalised rows the forward kept and their 1/sigma).  resn: dict(rstd, mean[, m]) -- `res` holds normalised rows and the residual
+    is rebuilt from them; no_y: the sum is not written and the LayerNorm sees it unrounded (the chain form).
+    act = ACT_RELU_PAIR returns 'y' only: the mask y2 is held by assert_mask_consistent.
     pre: conv_sum(x, w, g, kvalid=...) computed once for several epilogues of the same operands."""
     T = _T(dtype)
     B, Hout, Wout, Cout, ldy = g["B"], g["Hout"], g["Wout"], g["Cout"], g["ldy"]
@@ -290,20 +333,43 @@ def conv(x, w, g, dtype, bias=None, act=ACT_NONE, res=None, mul=None, mulmode=MU
     a = add_bias(pre if pre is not None else conv_sum(x, w, g, None, kvalid), bias, g)
     if act == ACT_SILU:
         a = _silu(a)
+    if act == ACT_RELU:
+        a = _relu(a)  # conv_epilogue.h:48 / :86
     a = _rnd(a, T)  # the LDS tile (conv_epilogue.h:53; fp32 tiles :51)
     out = {}
     if ln is not None:  # fused LayerNorm backward: g = the stored tile, u = ln_x + m (conv_epilogue.h:256-283)
-        u = exact(_rows(ln["x"], npix, ldy)[:, :Cout])
-        m = _mrows(ln.get("m"), npix, HW, Cout, ln.get("ldm", 0))
-        if m is not None:
-            u = _add(u, V(m))
-        o = ln_backward_rows(a, u, Cout, ln["eps"], ln["unbiased"])
+        if ln.get("rstd") is not None:  # the forward kept xhat and 1/sigma (:311-359): ln_m is not read
+            o = ln_backward_rows_stored(a, _rows(ln["x"], npix, ldy)[:, :Cout].to(D), ln["rstd"].reshape(-1)[:npix].to(D), Cout, ln["unbiased"])
+        else:
+            u = exact(_rows(ln["x"], npix, ldy)[:, :Cout])
+            m = _mrows(ln.get("m"), npix, HW, Cout, ln.get("ldm", 0))
+            if m is not None:
+                u = _add(u, V(m))
+            o = ln_backward_rows(a, u, Cout, ln["eps"], ln["unbiased"])
+        out["o"] = o  # the fp32 rows dm is summed from (the planted "tile missing from dm" takes its pixels' rows from here)
         out["dm"] = dm_sums(o, npix, HW, Cout, ln.get("ldm", 0))
         if res is not None:
             o = _add(o, exact(_rows(res, npix, ldy)[:, :Cout]))
         out["y"] = _rnd(o, T)
         return out
     f = a
+    if resn is not None or no_y:  # the chain form: conv_epilogue.h:437-487
+        assert lnf is not None and mul is None and act == ACT_NONE and not y2 and not pool2
+        if resn is not None:
+            h = exact(_rows(res, npix, ldy)[:, :Cout])
+            col = lambda t: t.reshape(-1)[:npix].to(D).unsqueeze(1).expand(npix, Cout)  # noqa: E731
+            rm = _mrows(resn.get("m"), npix, HW, Cout, lnf.get("ldm", 0))
+            shift = _sub(V(col(resn["mean"])), V(rm)) if rm is not None else V(col(resn["mean"]))   # :475 (rmean - rm2)
+            f = _add(f, _add(_mul(h, _rcp(V(col(resn["rstd"])))), shift))                            # :454, :475, :478
+        elif res is not None:
+            f = _add(f, exact(_rows(res, npix, ldy)[:, :Cout]))                                      # :478
+        if not no_y:
+            f = _rnd(f, T)  # :481, read back :486
+            out["y"] = f
+        m = _mrows(lnf.get("m"), npix, HW, Cout, lnf.get("ldm", 0))
+        u = _add(f, V(m)) if m is not None else f
+        out["hn"], out["rstd"], out["mean"] = layernorm(u, Cout, lnf["eps"], lnf["unbiased"], T)
+        return out
     if mul is not None or res is not None:
         if mul is not None:
             mm = exact(_rows(mul, npix, ldy)[:, :Cout])
@@ -313,6 +379,9 @@ def conv(x, w, g, dtype, bias=None, act=ACT_NONE, res=None, mul=None, mulmode=MU
         f = _rnd(f, T)  # conv_epilogue.h:549
     if act == ACT_SILU_PAIR:
         out["y"], out["y2"] = _rnd(_silu(f), T), _rnd(_dsilu(f), T)
+        return out
+    if act == ACT_RELU_PAIR:  # max(a, 0) of the stored value: representable, no rounding (conv_epilogue.h:614-625)
+        out["y"] = _relu(f)
         return out
     if pool2:
         q = f.view(B, Hout // 2, 2, Wout // 2, 2, Cout)
@@ -326,7 +395,7 @@ def conv(x, w, g, dtype, bias=None, act=ACT_NONE, res=None, mul=None, mulmode=MU
     if lnf is not None:  # LN of the stored result (+ the consumer's modulation): conv_epilogue.h:429-455
         m = _mrows(lnf.get("m"), npix, HW, Cout, lnf.get("ldm", 0))
         u = _add(f, V(m)) if m is not None else f
-        out["hn"], out["rstd"], _ = layernorm(u, Cout, lnf["eps"], lnf["unbiased"], T)
+        out["hn"], out["rstd"], out["mean"] = layernorm(u, Cout, lnf["eps"], lnf["unbiased"], T)
     return out
 
 
@@ -700,6 +769,36 @@ def assert_within(got, ref, bound=None, what="", layout=None):
         raise AssertionError(f"{what}: err/bound {worst:.3g} at {loc} ({', '.join(reg)}): got {g:.6g}, fp64 {ref.reshape(-1)[i].item():.6g}, "
                              f"bound {bound.reshape(-1)[i].item():.3g}; {int((r > 1).sum().item())} of {r.numel()} elements violate the bound")
     return worst
+
+
+def assert_mask_consistent(y, y2, what=""):
+    """the rule of C2W_ACT_RELU_PAIR's second output: y2 == (y > 0) exactly, on every element (so 1 or 0, and 0 where y is -0, +0 or NaN).
+    The mask is discontinuous in the pre-activation and gets no numeric bound of its own; y is held to its bound by assert_within."""
+    want = (y > 0).to(y2.dtype)
+    bad = y2 != want
+    n = int(bad.sum().item())
+    if n:
+        i = int(bad.reshape(-1).nonzero()[0].item())
+        raise AssertionError(f"{what}: mask and output disagree on {n} of {bad.numel()} elements; first at flat index {i}: "
+                             f"y {y.reshape(-1)[i].item():.6g}, y2 {y2.reshape(-1)[i].item():.6g}")
+
+
+def assert_nan_footprint(got, ref, bound=None, what="", layout=None):
+    """got is NaN on exactly the elements where the float64 reference is; everywhere else it is finite and within the bound.
+    Returns (largest err / bound outside the footprint, number of NaN elements)."""
+    if isinstance(ref, V):
+        ref, bound = ref.v, ref.e
+    g = got.to(D).reshape(ref.shape)
+    foot = torch.isnan(ref)
+    miss = foot != torch.isnan(g)
+    if bool(miss.any()):
+        i = int(miss.reshape(-1).nonzero()[0].item())
+        loc, reg = _where(i, layout)
+        raise AssertionError(f"{what}: NaN where the reference has none, or none where it has: {int(miss.sum().item())} elements, first at {loc} "
+                             f"({', '.join(reg)}): got {g.reshape(-1)[i].item():.6g}, fp64 {ref.reshape(-1)[i].item():.6g}")
+    assert bool(torch.isfinite(g[~foot]).all()), f"{what}: non-finite values outside the NaN footprint"
+    z = torch.zeros_like(ref)
+    return assert_within(torch.where(foot, z, g), torch.where(foot, z, ref), torch.where(foot, z, bound), what, layout), int(foot.sum().item())
 
 
 def assert_rejects(got_with_defect, ref, bound=None, what=""):

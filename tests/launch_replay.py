@@ -220,6 +220,7 @@ class Report:
         self.packed_resolved = 0
         self.calls = []      # (index, name, flags) of every launch
         self.bounded = Counter()  # launches per name that had a float64 bound
+        self.bounded_flags = Counter()  # the same per "name:flag" (the argument combinations that were seen AND bounded)
 
     def ratio(self, name, what, r):
         d = self.worst.setdefault(name, {})
@@ -251,6 +252,7 @@ class Report:
 class Call:
     def __init__(self, index, name, real, snap, ref):
         self.index, self.name, self.real, self.snap, self.ref = index, name, real, snap, ref
+        self.flags = set()
         self.got = {}  # path -> tensor that stands for the real output in the comparison (the planted defects of the GPU power check)
 
     def out(self, path):
@@ -330,6 +332,7 @@ class Harness:
                 return _on(t, store[sp] if store is refstore else groups[sp][1])
             return f
         call = Call(index, name, real, remap(real, view(None)), remap(real, view(refstore)))
+        call.flags = flags
         try:
             if ret is False:  # "unsupported": nothing may have been written at all
                 rep.refused[name] += 1
@@ -362,6 +365,8 @@ class Harness:
                 f.add("ln.rstd")
             if a.get("lnf") is not None:
                 f.update("lnf." + k for k in ("rstd", "mean") if a["lnf"].get(k) is not None)
+            if a.get("act") in (emu_ops.ACT_RELU, emu_ops.ACT_RELU_PAIR):
+                f.add("relu" if a["act"] == emu_ops.ACT_RELU else "relu_pair")
             if g["ldy"] != g["Cout"]:
                 f.add("ldy!=Cout")
             f.add("mode%d" % g["mode"])
@@ -486,6 +491,8 @@ class Harness:
             n += 1
         if n:
             self.report.bounded[call.name] += 1
+            for f in call.flags:
+                self.report.bounded_flags[f"{call.name}:{f}"] += 1
 
     def _untouched(self, call, groups, written):
         for sp, (now, snap) in groups.items():
@@ -690,25 +697,18 @@ def _dm_rows(dm, g_or_npix, HW, C, ldm):
     return dm.reshape(-1)[:C].view(1, C)
 
 
-def conv_modelled(a):
-    """does fp64_ref.conv model this launch?  The chain form (resn / no_y / lnf.mean), kept statistics (ln.rstd) and ReLU are restated
-    by emu_ops only."""
-    lnf, ln = a.get("lnf"), a.get("ln")
-    return not (a.get("resn") is not None or a.get("no_y") or (lnf is not None and lnf.get("mean") is not None)
-                or (ln is not None and ln.get("rstd") is not None) or a["act"] in (emu_ops.ACT_RELU, emu_ops.ACT_RELU_PAIR))
-
-
 def _b_conv(h, call):
+    """every conv launch has its float64 bound: the chain form (resn / no_y / lnf.mean), kept statistics (ln.rstd) and both ReLU forms
+    included; the ReLU pair's mask is held by its consistency with the bounded first output (fp64_ref.assert_mask_consistent)"""
     a = call.snap
-    if not conv_modelled(a):
-        return
     g, dt = a["g"], a["dtype"]
     T = R._T(dt)
     Cout, ldy = g["Cout"], g["ldy"]
     npix, HW = g["B"] * g["Hout"] * g["Wout"], g["Hout"] * g["Wout"]
     n_out = _conv_out_rows(a)
-    kw = dict(bias=a["bias"], act=a["act"], res=a["res"], mul=a["mul"], mulmode=a["mulmode"], y2=a["y2"] is not None and a["act"] != emu_ops.ACT_SILU_PAIR,
-              pool2=bool(a["pool2"]), kvalid=int(a["kvalid"] or 0))
+    pair = a["act"] in (emu_ops.ACT_SILU_PAIR, emu_ops.ACT_RELU_PAIR)
+    kw = dict(bias=a["bias"], act=a["act"], res=a["res"], mul=a["mul"], mulmode=a["mulmode"], y2=a["y2"] is not None and not pair,
+              pool2=bool(a["pool2"]), kvalid=int(a["kvalid"] or 0), resn=a.get("resn"), no_y=bool(a.get("no_y")))
     if a["lnf"] is not None:
         kw["lnf"] = a["lnf"]
     if a["ln"] is not None:
@@ -718,8 +718,13 @@ def _b_conv(h, call):
     tag = f"launch {call.index} conv"
     y = rows(call.out(("y",)), n_out, ldy)
     loss = a.get("loss")
-    if loss is None:
+    if a.get("no_y"):
+        assert "y" not in ref  # nothing to bound: that the buffer kept its bytes is the harness's step 4
+    elif loss is None:
         yield f"{tag} y", y[:, :Cout], ref["y"], lay
+        if a["act"] == emu_ops.ACT_RELU_PAIR:
+            R.assert_mask_consistent(y[:, :Cout], rows(call.out(("y2",)), n_out, ldy)[:, :Cout], what=f"{tag} y2")
+            h.report.ratio("conv", "fp64 conv relu mask", 0.0)
     else:
         C, lde = loss["C"], loss["lde"]
         pred = R.V(ref["y"].v[:, :C], ref["y"].e[:, :C])
@@ -736,6 +741,8 @@ def _b_conv(h, call):
         yield f"{tag} lnf.y", rows(call.out(("lnf", "y")), npix, ldy)[:, :Cout], ref["hn"], lay
         if a["lnf"].get("rstd") is not None:
             yield f"{tag} lnf.rstd", call.out(("lnf", "rstd")).reshape(-1)[:npix], ref["rstd"], None
+        if a["lnf"].get("mean") is not None:
+            yield f"{tag} lnf.mean", call.out(("lnf", "mean")).reshape(-1)[:npix], ref["mean"], None
     if "dm" in ref and a["ln"].get("dm") is not None:
         ldm = a["ln"].get("ldm", 0)
         yield f"{tag} ln.dm", _dm_rows(call.out(("ln", "dm")), npix, HW, Cout, ldm), R.accumulated(_dm_rows(a["ln"]["dm"], npix, HW, Cout, ldm), ref["dm"]), None
@@ -1007,7 +1014,7 @@ def install(monkeypatch, ops_module, *, mode="default", planted=None) -> Report:
 
 
 def border_tap_defect(select=None):
-    """The power check of the GPU cases: on the first conv launch that is linear in the conv sum (bias / res only, 3x3, fp64-modelled) --
+    """The power check of the GPU cases: on the first conv launch that is linear in the conv sum (bias / res only, 3x3) --
     or the launch ``select(call)`` accepts -- one border tap of input channel 0 of image 0 is removed from the compared output
     (fp64_ref.conv_term, as tests/test_gpu_kernels.py does).  Returns (hook, hit): hit[0] is that launch's index once it ran."""
     hit = []
@@ -1017,7 +1024,7 @@ def border_tap_defect(select=None):
         if hit or call.name != "conv":
             return
         g = a["g"]
-        ok = (conv_modelled(a) and a["act"] == emu_ops.ACT_NONE and a["mul"] is None and a["y2"] is None and a["ln"] is None and a["lnf"] is None
+        ok = (a["act"] == emu_ops.ACT_NONE and a["mul"] is None and a["y2"] is None and a["ln"] is None and a["lnf"] is None
               and not a["pool2"] and a["loss"] is None and g["mode"] == emu_ops.CONV_S1 and g["Hout"] >= 4)
         if select is not None:
             ok = ok and select(call)

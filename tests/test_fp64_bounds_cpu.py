@@ -195,6 +195,252 @@ def test_restatement_is_within_the_bound_epilogues(dt):
     R.assert_rejects(y.double() - R.conv_term(xi, wi, g, 1, slice(0, 64), None, R.tile_mask(H, W)), ref["y"], what="split-K chunk")
 
 
+def _relu_case(dt, seed=1):
+    B, H, W, C = 2, 8, 16, 128
+    g = geom(B, H, W, C, H, W, C, C, C, E.CONV_S1)
+    npix = B * H * W
+    x = rnd((npix, C), dt, seed)
+    w = rnd((C, 9, C), dt, seed + 1, 1.0 / math.sqrt(9 * C))
+    bias = rnd((C,), F32, seed + 2)
+    return g, npix, x, w, bias, dict(B=B, H=H, W=W, C=C)
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16])
+def test_restatement_is_within_the_bound_relu(dt):
+    """C2W_ACT_RELU and C2W_ACT_RELU_PAIR (with multiplier and residual in front of the pair), the mask's consistency rule, and the mutant
+    "ReLU missing on one 8x16 tile" (negatives pass) planted in float64 on the restatement's output"""
+    g, npix, x, w, bias, lay = _relu_case(dt)
+    C = g["Cout"]
+    res, mul = rnd((npix, C), dt, 4), rnd((npix, C), dt, 5)
+    y, pre = torch.zeros((npix, C), dtype=TD[dt]), torch.zeros((npix, C), dtype=TD[dt])
+    E.conv(x, w, bias, y, g, dt, act=E.ACT_RELU)
+    ref = R.conv(x, w, g, dt, bias=bias, act=R.ACT_RELU)
+    worst = R.assert_within(y, ref["y"], what="relu", layout=lay)
+    assert worst > 1e-3 and float(y.min()) == 0.0 and float((y == 0).float().mean()) > 0.2
+    E.conv(x, w, bias, pre, g, dt)
+    bad = y.double().view(2, 8, 16, C).clone()
+    bad[1] = pre.double().view(2, 8, 16, C)[1]  # image 1 is exactly one 8x16 tile
+    R.assert_rejects(bad.view(npix, C), ref["y"], what="ReLU missing on one tile")
+    R.assert_rejects(y.double() - R.conv_term(x, w, g, 0, slice(0, 1), 4, R.border_mask(8, 16)), ref["y"], what="relu, missing border tap")
+    for kw in (dict(), dict(res=res), dict(mul=mul, res=res)):
+        y2 = torch.full((npix, C), 7.0, dtype=TD[dt])
+        E.conv(x, w, bias, y, g, dt, act=E.ACT_RELU_PAIR, y2=y2, **kw)
+        ref = R.conv(x, w, g, dt, bias=bias, act=R.ACT_RELU_PAIR, **kw)
+        assert set(ref) == {"y"}  # the mask has no numeric bound
+        R.assert_within(y, ref["y"], what=f"relu pair {sorted(kw)}", layout=lay)
+        R.assert_mask_consistent(y, y2, what="relu pair")
+        flipped = y2.clone()
+        i = int((y.reshape(-1) > 0).nonzero()[17])
+        flipped.view(-1)[i] = 0
+        with pytest.raises(AssertionError, match="disagree on 1 of"):
+            R.assert_mask_consistent(y, flipped)
+        flipped = y2.clone()
+        flipped.view(-1)[int((y.reshape(-1) == 0).nonzero()[5])] = 1
+        with pytest.raises(AssertionError, match="disagree on 1 of"):
+            R.assert_mask_consistent(y, flipped)
+
+
+def test_nan_footprint_rule():
+    """a NaN in x reaches 3x3 pixels x all weight rows of the float64 reference, through ReLU too; the helper wants exactly those"""
+    dt = BF16
+    g, npix, x, w, bias, lay = _relu_case(dt)
+    x.view(2, 8, 16, 128)[1, 3, 5, 9] = float("nan")
+    y = torch.zeros((npix, 128), dtype=TD[dt])
+    E.conv(x, w, bias, y, g, dt, act=E.ACT_RELU)
+    ref = R.conv(x, w, g, dt, bias=bias, act=R.ACT_RELU)
+    worst, n = R.assert_nan_footprint(y, ref["y"], what="relu nan", layout=lay)
+    assert n == 9 * 128 and worst <= 1.0
+    erased = torch.where(torch.isnan(y), torch.zeros_like(y), y)  # what max(NaN, 0) = 0 does
+    with pytest.raises(AssertionError, match="NaN where"):
+        R.assert_nan_footprint(erased, ref["y"], what="erased")
+    spread = y.clone()
+    spread[0, 0] = float("nan")
+    with pytest.raises(AssertionError, match="NaN where"):
+        R.assert_nan_footprint(spread, ref["y"], what="spread")
+
+
+def _kept_operands(npix, C, dt, unbiased, seed=7):
+    """xhat and 1/sigma as a real LayerNorm forward keeps them: the normalised rows in the storage type, rstd in fp32; image 0's first rows
+    are constant (xhat = 0, rstd = 1/sqrt(eps))"""
+    u = rnd((npix, C), dt, seed).float()
+    u[:32] = 0.75
+    var, mean = torch.var_mean(u, dim=1, unbiased=unbiased, keepdim=True)
+    rs = (var + 1e-5).rsqrt()
+    return ((u - mean) * rs).to(TD[dt]), rs.view(-1).contiguous()
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+def test_restatement_is_within_the_bound_kept_statistics(dt):
+    """the fused LayerNorm backward from kept statistics (ln.rstd), per-sample and shared dm rows, with / without residual; mutants:
+    den = C instead of C - 1, one 8x16 tile missing from dm"""
+    B, H, W, C = 2, 8, 16, 128
+    g = geom(B, H, W, C, H, W, C, C, C, E.CONV_S1)
+    npix = B * H * W
+    x = rnd((npix, C), dt, 1)
+    w = rnd((C, 9, C), dt, 2, 1.0 / math.sqrt(9 * C))
+    res = rnd((npix, C), dt, 4)
+    lay = dict(B=B, H=H, W=W, C=C)
+    for unbiased in (True, False):
+        xh, rs = _kept_operands(npix, C, dt, unbiased)
+        assert rs.max().item() == pytest.approx(1e-5 ** -0.5, rel=1e-6)
+        for ldm in (C + 64, 0):
+            for r in (res, None):
+                dm = torch.zeros((B if ldm else 1, C + 64))
+                ln = dict(x=xh, rstd=rs, ldm=ldm, eps=1e-5, unbiased=unbiased)
+                y = torch.zeros((npix, C), dtype=TD[dt])
+                E.conv(x, w, None, y, g, dt, res=r, ln=dict(ln, dm=dm.view(-1)[32:]))
+                ref = R.conv(x, w, g, dt, res=r, ln=ln)
+                R.assert_within(y, ref["y"], what="kept statistics dx", layout=lay)
+                got_dm = dm[:, 32:32 + C]
+                R.assert_within(got_dm, ref["dm"], what="kept statistics dm")
+                if dt == F16:  # den = C for C - 1 (or the reverse): the restatement with the other flag is what such a kernel writes
+                    yb, dmb = torch.zeros_like(y), torch.zeros_like(dm)
+                    E.conv(x, w, None, yb, g, dt, res=r, ln=dict(ln, unbiased=not unbiased, dm=dmb.view(-1)[32:]))
+                    R.assert_rejects(yb.double(), ref["y"], what="kept statistics, wrong denominator")
+                # one 8x16 tile (image 0) missing from dm
+                gt = geom(1, 8, 16, C, 8, 16, C, C, C, E.CONV_S1)
+                tile = R.conv(x[:128], w, gt, dt, ln=dict(ln, x=xh[:128], rstd=rs[:128], ldm=0))["dm"]
+                bad = got_dm.double().clone()
+                bad[0] -= tile.v[0]
+                R.assert_rejects(bad, ref["dm"], what="kept statistics dm, tile missing")
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+def test_the_dm_bound_sees_the_wrong_denominator_of_the_kept_statistics(dt):
+    """den = C where the LayerNorm was unbiased changes one term of o by 1 / 128 = 2 u_T(bf16) of it: per element that is inside the
+    worst-case propagation of the tile's own rounding, so in bf16 the rows cannot see it on random data.  The modulation gradient can: its
+    bound adds the pixels' roundings in quadrature, the defect adds up coherently where the gradient is aligned with xhat.  Here every pixel
+    holds the same normalised row p and the conv (centre tap = identity) hands g = p through: the exact o is 0 (sum p^2 = C - 1), the
+    mutant's is rs p / C on every pixel."""
+    B, H, W, C = 2, 16, 16, 128
+    g = geom(B, H, W, C, H, W, C, C, C, E.CONV_S1)
+    npix = B * H * W
+    p = rnd((1, C), dt, 5).float()
+    var, mean = torch.var_mean(p, dim=1, unbiased=True, keepdim=True)
+    xh = ((p - mean) * var.rsqrt()).to(TD[dt]).expand(npix, C).contiguous()
+    rs = torch.full((npix,), 1.5)
+    w = torch.zeros((C, 9, C), dtype=TD[dt])
+    w[:, 4] = torch.eye(C, dtype=TD[dt])
+    for ldm in (C, 0):
+        ln = dict(x=xh, rstd=rs, ldm=ldm, eps=1e-5, unbiased=True)
+        dm, dmb, y = torch.zeros((B if ldm else 1, C)), torch.zeros((B if ldm else 1, C)), torch.zeros((npix, C), dtype=TD[dt])
+        E.conv(xh, w, None, y, g, dt, ln=dict(ln, dm=dm))
+        ref = R.conv(xh, w, g, dt, ln=ln)
+        R.assert_within(y, ref["y"], what="aligned rows dx")
+        R.assert_within(dm, ref["dm"], what="aligned rows dm")
+        E.conv(xh, w, None, y, g, dt, ln=dict(ln, unbiased=False, dm=dmb))
+        R.assert_rejects(dmb.double(), ref["dm"], what="kept statistics dm, den = C for C - 1")
+
+
+def _chain_operands(npix, HW, C, dt, ldm, seed=11, const=None):
+    """the block input x0 (never written), its modulation m0 and what the earlier launch emitted: h = LN(x0 + m0) in the storage type with
+    the row's mean and 1/sigma in fp32.  Image 1's first rows of x0 + m0 are constant: h = 0 there and the rebuilt x = mean - m."""
+    nb = npix // HW
+    m0 = rnd((nb if ldm else 1, ldm or C), F32, seed + 1)
+    mrow = m0[:, :C].repeat_interleave(HW, 0) if ldm else m0[:, :C].expand(npix, C)
+    x0 = rnd((npix, C), dt, seed, 2.0).float()
+    const = const or slice(npix // 2, npix // 2 + 32)
+    x0[const] = 0.5 - mrow[const]
+    u = x0 + mrow
+    var, mean = torch.var_mean(u, dim=1, unbiased=True, keepdim=True)
+    rs = (var + 1e-5).rsqrt()
+    h = ((u - mean) * rs).to(TD[dt])
+    h[const], rs[const], mean[const] = 0.0, 1e-5 ** -0.5, 0.5  # what the LayerNorm of an exactly constant row emits
+    return h, rs.view(-1).contiguous(), mean.view(-1).contiguous(), m0, x0
+
+
+CHAIN_FORMS = {  # the four forms of tests/test_gpu_bench_dispatch.py::test_chain_form_of_the_layernorm_emitting_convolution
+    "plain residual, output not written": dict(resn=False, no_y=True, m=True),
+    "rebuilt residual, output not written": dict(resn=True, no_y=True, m=True),
+    "rebuilt residual, output written": dict(resn=True, no_y=False, m=True),
+    "rebuilt residual, plain LayerNorm (up-block consumer)": dict(resn=True, no_y=False, m=False),
+}
+
+
+def chain_launch(conv, form, x, w, bias, g, dt, ops_, fill=3.0, **over):
+    """one chain-form launch through `conv` (emu_ops.conv or ops.conv); ops_ = _chain_operands(...).  Returns (y, hn, rstd, mean, kwargs for
+    fp64_ref.conv)."""
+    h, rs, mean, m0, x0 = ops_
+    f = CHAIN_FORMS[form]
+    npix, C = g["B"] * g["Hout"] * g["Wout"], g["Cout"]
+    ldm = m0.shape[1] if m0.shape[0] > 1 else 0
+    dev = x.device
+    m1 = rnd(tuple(m0.shape), F32, 23).to(dev) if f["m"] else None
+    y = torch.full((npix, C), fill, dtype=TD[dt], device=dev)
+    hn = torch.zeros((npix, C), dtype=TD[dt], device=dev)
+    rstd, mu = torch.zeros(npix, device=dev), torch.zeros(npix, device=dev)
+    lnf = dict(m=m1, ldm=ldm, eps=1e-5, unbiased=True)
+    if f["resn"]:
+        kw = dict(res=h, resn=dict(rstd=rs, mean=mean, m=m0), no_y=f["no_y"])
+    else:
+        kw = dict(res=x0.to(TD[dt]), no_y=f["no_y"])
+    kw.update(over)
+    conv(x, w, bias, y, g, dt, lnf=dict(lnf, y=hn, rstd=rstd, mean=mu), **kw)
+    return y, hn, rstd, mu, dict(kw, lnf=dict(lnf, mean=True))
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+@pytest.mark.parametrize("form", list(CHAIN_FORMS))
+def test_restatement_is_within_the_bound_chain_form(form, dt):
+    """lnf.mean / resn / no_y: hn, rstd, mean and (where written) y of the restatement lie inside the bound, with per-sample and shared
+    modulation rows; mutants: rebuilt residual without - m, rebuilt residual with rstd used as sigma"""
+    B, H, W, C = 2, 8, 16, 128
+    g = geom(B, H, W, C, H, W, C, C, C, E.CONV_S1)
+    npix = B * H * W
+    x = rnd((npix, C), dt, 1)
+    w = rnd((C, 9, C), dt, 2, 1.0 / math.sqrt(9 * C))
+    bias = rnd((C,), F32, 3)
+    lay = dict(B=B, H=H, W=W, C=C)
+    for ldm in (C + 64, 0):
+        co = _chain_operands(npix, H * W, C, dt, ldm)
+        y, hn, rstd, mu, kw = chain_launch(E.conv, form, x, w, bias, g, dt, co)
+        ref = R.conv(x, w, g, dt, bias=bias, **kw)
+        assert ("y" in ref) == (not CHAIN_FORMS[form]["no_y"])
+        if "y" in ref:
+            R.assert_within(y, ref["y"], what="chain y", layout=lay)
+        else:
+            assert bool((y == 3.0).all())
+        R.assert_within(hn, ref["hn"], what="chain hn", layout=lay)
+        R.assert_within(rstd, ref["rstd"], what="chain rstd")
+        R.assert_within(mu, ref["mean"], what="chain mean")
+        if not CHAIN_FORMS[form]["resn"]:
+            continue
+        h, rs, mean, m0, _ = co
+        for what, resn in (("without - m", dict(rstd=rs, mean=mean, m=None)), ("rstd used as sigma", dict(rstd=1.0 / rs, mean=mean, m=m0))):
+            yb, hnb, rsb, mub, _ = chain_launch(E.conv, form, x, w, bias, g, dt, co, resn=resn)
+            if resn["m"] is None:  # (the normalised rows sum to zero: their scale does not reach the mean, it reaches 1/sigma)
+                R.assert_rejects(mub.double(), ref["mean"], what=f"chain mean, rebuilt residual {what}")
+            else:
+                R.assert_rejects(rsb.double(), ref["rstd"], what=f"chain rstd, rebuilt residual {what}")
+            R.assert_rejects(hnb.double(), ref["hn"], what=f"chain hn, rebuilt residual {what}")
+            if "y" in ref:
+                R.assert_rejects(yb.double(), ref["y"], what=f"chain y, rebuilt residual {what}")
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+def test_the_mean_bound_sees_a_layernorm_of_the_rounded_sum_where_none_is_written(dt):
+    """With C2W_CONV_NO_Y the LayerNorm sees the fp32 sum u.  A kernel that rounded u to the storage type first (the form that writes y)
+    would move every element by up to u_T |u| and the row mean by about u_T |u| / sqrt(128).  In hn that is of the size of hn's own rounding
+    u_T |hn|: only the elements next to the row's mean (|hn| << 1, where the bound is small: a sixth of them here) show it, most of hn cannot.  The mean
+    is an fp32 output: its bound is the conv tile's rounding u_T |a| (worst case over the row) plus fp32 terms, so with a block input much
+    larger than the conv result (|x0| ~ 2, |a| ~ 0.01 here, as deep in a residual chain) the mutant's shift of the mean stands out in most
+    rows, and the bound on `mean` must reject it."""
+    B, H, W, C = 2, 8, 16, 128
+    g = geom(B, H, W, C, H, W, C, C, C, E.CONV_S1)
+    npix = B * H * W
+    x = rnd((npix, C), dt, 1)
+    w = rnd((C, 9, C), dt, 2, 0.01 / math.sqrt(9 * C))
+    co = _chain_operands(npix, H * W, C, dt, C + 64)
+    form = "rebuilt residual, output not written"
+    y, hn, rstd, mu, kw = chain_launch(E.conv, form, x, w, None, g, dt, co)
+    ref = R.conv(x, w, g, dt, **kw)
+    R.assert_within(mu, ref["mean"], what="chain mean")
+    R.assert_within(hn, ref["hn"], what="chain hn")
+    _, hnb, _, mub, _ = chain_launch(E.conv, form, x, w, None, g, dt, co, no_y=False)  # normalises the rounded sum
+    R.assert_rejects(mub.double(), ref["mean"], what="no_y form normalising the rounded sum")
+    assert (R.ratio(mub, ref["mean"]) > 1).double().mean().item() > 0.8 > 0.2 > (R.ratio(hnb, ref["hn"]) > 1).double().mean().item()
+
+
 @pytest.mark.parametrize("dt", [F32, BF16, F16])
 @pytest.mark.parametrize("mode", [E.CONV_S1, E.CONV_S2, E.CONV_UP, E.CONV_1X1])
 def test_restatement_is_within_the_bound_wgrad(mode, dt):

@@ -266,10 +266,17 @@ def test_stride2_forward_on_parity_planes_against_the_gather_kernel(case, dt, mo
     w = rnd((Cout, 9, Cin), dt, 2, scale=1.0 / math.sqrt(9 * Cin))
     bias = rnd((Cout,), F32, 3)
     res = rnd((B * Hout * Wout, Cout), dt, 4)
-    for kw in (dict(), dict(act=ops.ACT_SILU), dict(res=res)):
+    relu = [dict(act=ops.ACT_RELU), dict(act=ops.ACT_RELU_PAIR, res=res)] if Cout == 192 and Hin == 32 and B == 2 else []  # the "cout192" case
+    for kw in [dict(), dict(act=ops.ACT_SILU), dict(res=res)] + relu:
         y = torch.full((B * Hout * Wout, Cout), 7.0, dtype=TD[dt], device=dev())
         y_ref, y_g = y.clone(), y.clone()
-        ops.conv(x, w, bias, y, g, dt, **kw)
+        if kw.get("act") == ops.ACT_RELU_PAIR:
+            y2 = torch.full_like(y, 3.0)
+            ops.conv(x, w, bias, y, g, dt, y2=y2, **kw)
+            R.assert_mask_consistent(y, y2, what=f"{name} ReLU pair")
+            kw = dict(kw, y2=torch.empty_like(y))
+        else:
+            ops.conv(x, w, bias, y, g, dt, **kw)
         E.conv(x, w, bias, y_ref, g, dt, **kw)
         monkeypatch.setenv("C2W_CONV_S2_PATCH", "0")
         ops.knobs_reload()
@@ -280,7 +287,7 @@ def test_stride2_forward_on_parity_planes_against_the_gather_kernel(case, dt, mo
         torch.cuda.synchronize()
         close(y, y_ref, TOL[dt], f"{name} {sorted(kw)}")
         close(y, y_g, TOL[dt], f"{name} {sorted(kw)} against the gather kernel")
-        ref = R.conv(x, w, g, dt, bias=bias, **kw)
+        ref = R.conv(x, w, g, dt, bias=bias, **{k: v for k, v in kw.items() if k != "y2"})
         what = f"stride-2 parity planes {name} {sorted(kw)} dt={dt}"
         R.report(what, R.assert_within(y, ref["y"], what=what, layout=dict(R.layout(g), tile=(8, 16 if Wout >= 16 else 8))))
 
@@ -726,6 +733,11 @@ def test_loss_fusion_is_refused_where_the_kernel_does_not_exist():
     y, ls = torch.empty((npix, 128), dtype=torch.bfloat16, device=dev()), torch.zeros(1, device=dev())
     with pytest.raises(_lib.C2wError):  # a channel stride that is not whole 16-byte segments
         ops.conv(x, w, None, y, g_ok, BF16, loss=dict(sum=ls, eps=torch.zeros((npix, 68), dtype=torch.float16, device=dev()), lde=68, gscale=1.0, C=65))
+    # fewer loss channels than weight rows: the epilogue would take channels [loss_C, wrows) into the loss and give them gradient
+    er = torch.zeros((npix, 72), dtype=torch.float16, device=dev())
+    with pytest.raises(_lib.C2wError):
+        ops.conv(x, w, None, y, g_ok, BF16, loss=dict(sum=ls, eps=er, lde=72, gscale=1.0, C=64))
+    assert ls.item() == 0.0  # refused before anything ran
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])
@@ -885,7 +897,7 @@ SPLITK_CASES = [  # (name, pair, B, H, Cin, Cout, expected workgroups per tile)
 
 
 @pytest.mark.parametrize("dt", [BF16, F16, F32])
-@pytest.mark.parametrize("epi", ["bias+silu", "bias+res", "mul(dsilu)+res", "plain"])
+@pytest.mark.parametrize("epi", ["bias+silu", "bias+res", "mul(dsilu)+res", "plain", "bias+relu"])
 @pytest.mark.parametrize("case", SPLITK_CASES, ids=[c[0] for c in SPLITK_CASES])
 def test_split_k_convolution_for_underfilled_launches(case, epi, dt):
     """Round 6 (C2wConvArgs.splitk; model/nn.py:146-159 at the deep levels of a sampler step on a short trajectory, exp/configs/000_on-model-eval/
@@ -896,7 +908,7 @@ def test_split_k_convolution_for_underfilled_launches(case, epi, dt):
     if dt == F32:
         Cin = Cin // 2  # (fp32 chunks are 32 channels: the same chunk counts)
     g = geom(B, H, H, Cin, H, H, Cout, Cout, Cout, S1)
-    act = ops.ACT_SILU if "silu" in epi and "dsilu" not in epi else ops.ACT_NONE
+    act = ops.ACT_RELU if "relu" in epi else (ops.ACT_SILU if "silu" in epi and "dsilu" not in epi else ops.ACT_NONE)
     ns, nbytes = ops.conv_splitk_plan(g, dt, act)
     assert ns == want and nbytes == ns * ((B + 1) // 2 * (H // 8) if pair else B * (H // 8) * (H // 16)) * ((Cout + 127) // 128) * 65536, (ns, nbytes)
     assert ops.conv_dispatch(g, dt) == (PAIR if pair else HALF)
@@ -933,6 +945,10 @@ def test_split_k_convolution_for_underfilled_launches(case, epi, dt):
         chunk = 32 if dt == F32 else 64
         t = R.conv_term(x, w, g, 0, slice(0, chunk), None, R.tile_mask(H, H, tw=8 if pair else 16))
         R.assert_rejects(outs[0].double() - t, ref["y"], what=what + ": one K chunk of one tile missing")
+    if epi == "bias+relu":  # the same defect behind the activation: where the output is positive the chunk's term is missing from it
+        t = R.conv_term(x, w, g, 0, slice(0, 32 if dt == F32 else 64), None, R.tile_mask(H, H, tw=8 if pair else 16))
+        R.assert_rejects(torch.where(outs[0] > 0, outs[0].double() - t, outs[0].double()), ref["y"], what=what + ": one K chunk of one tile missing")
+        assert outs[0].min().item() == 0.0
     with pytest.raises(_lib.C2wError):  # not the plan's answer
         ops.conv(x, w, bias, y, g, dt, splitk=(ws, ns + 1 if ns < 8 else 2), **kw)  # (scratch sized for the plan's answer; the count alone is refused)
     with pytest.raises(_lib.C2wError):  # scratch too small
@@ -981,6 +997,13 @@ def test_eight_wave_tile_kernel_gives_the_four_wave_kernels_bits(case, dt, monke
         y, y2 = torch.full((npix, Cout), 5.0, dtype=TD[dt], device=dev()), torch.full((npix, Cout), 3.0, dtype=TD[dt], device=dev())
         ops.conv(x, w, bias, y, g, dt, act=ops.ACT_SILU_PAIR, y2=y2)
         got += [y, y2]
+        y, y2 = torch.full((npix, Cout), 5.0, dtype=TD[dt], device=dev()), torch.full((npix, Cout), 3.0, dtype=TD[dt], device=dev())
+        ops.conv(x, w, bias, y, g, dt, act=ops.ACT_RELU_PAIR, y2=y2, res=res)
+        R.assert_mask_consistent(y, y2, what=name + " ReLU pair")
+        got += [y, y2]
+        y = torch.full((npix, Cout), 5.0, dtype=TD[dt], device=dev())
+        ops.conv(x, w, bias, y, g, dt, act=ops.ACT_RELU)
+        got.append(y)
         y = torch.full((npix, Cout), 5.0, dtype=TD[dt], device=dev())
         ops.conv(x, w, None, y, g, dt, mul=mul, mulmode=ops.MUL_DSILU, res=res)
         got.append(y)

@@ -20,7 +20,8 @@ import pytest
 import torch
 
 import fp64_ref as R
-from climate2weather_amd import ops
+import test_fp64_bounds_cpu as CB  # the chain form's operands and the four forms, shared with the CPU tier
+from climate2weather_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -219,3 +220,99 @@ def test_loss_sums_colsum_and_sumsq(dt):
     v = rnd((n,), F16, 5).float()
     s = torch.full((1,), 3.0, device=dev())
     twice(lambda: ops.sumsq(v, s, n), s, R.sumsq(v, n).view(1), f"sumsq n={n}", (v[:256].double() ** 2).sum().view(1))
+
+
+# ------------------------------------------------------------------------------ kept statistics and the chain form at small shapes
+
+def _s1(B, H, W, C):
+    return dict(B=B, Hin=H, Win=W, Cin=C, Hout=H, Wout=W, Cout=C, ldy=C, wrows=C, mode=S1)
+
+
+KEPT_CASES = [  # (B, H, W, per-sample rows, kernel family, knob)
+    (3, 16, 16, False, "PATCH_8X16", None),
+    (2, 32, 48, True, "PATCH_8X16", None),
+    (2, 32, 32, False, "PATCH_16X16", ("C2W_CONV_T3", "16")),
+]
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+@pytest.mark.parametrize("use_res", [True, False])
+@pytest.mark.parametrize("unbiased", [True, False])
+@pytest.mark.parametrize("case", KEPT_CASES, ids=["8x16-shared", "8x16-rows", "16x16"])
+def test_fused_layernorm_backward_from_kept_statistics(case, unbiased, use_res, dt, monkeypatch):
+    """finish_ln_rows_stored (conv_epilogue.h:311-359; EPI 6 of the 16x16-tile kernel and the same branch of the 8x16-tile kernel): the
+    operands are the normalised rows and 1/sigma of a real LayerNorm of random rows; image 0 has constant rows (xhat = 0,
+    rstd = 1/sqrt(eps)).  dx inside its bound; dm accumulated twice onto non-zero values, with one 8x16 tile of image 0 missing as the
+    planted defect; nothing written outside the modulation rows.
+    Measured worst err/bound: dx 0.855 (8x16-tile kernel), 0.772 (16x16); dm 0.102."""
+    B, H, W, rows, fam, kn = case
+    C = 128
+    if kn:
+        monkeypatch.setenv(*kn)
+        ops.knobs_reload()
+    g = _s1(B, H, W, C)
+    assert ops.conv_lnbwd_supported(g, dt) and ops.conv_dispatch(g, dt, fused_ln=True) == getattr(_lib, "KERNEL_" + fam)
+    npix, HW = B * H * W, H * W
+    x = rnd((npix, C), dt, 1)
+    w = rnd((C, 9, C), dt, 2, scale=1.0 / math.sqrt(9 * C))
+    res = rnd((npix, C), dt, 4) if use_res else None
+    u = rnd((npix, C), dt, 7).float()
+    u[:HW] = 0.75
+    var, mean = torch.var_mean(u, dim=1, unbiased=unbiased, keepdim=True)
+    rs = (var + 1e-5).rsqrt()
+    xh, rs = ((u - mean) * rs).to(TD[dt]), rs.view(-1).contiguous()
+    assert rs[:HW].min().item() == pytest.approx(1e-5 ** -0.5, rel=1e-6) and xh[:HW].abs().max().item() == 0.0
+    ldm = C + 64 if rows else 0
+    buf = rnd((B if rows else 1, C + 64), ops.DTYPE_F32, 6)
+    guard = buf.clone()
+    dm = buf.view(-1)[32:]
+    ln = dict(x=xh, rstd=rs, ldm=ldm, eps=1e-5, unbiased=unbiased)
+    y = torch.full((npix, C), 7.0, dtype=TD[dt], device=dev())
+    ref = R.conv(x, w, g, dt, res=res, ln=ln)
+    tile = ref["o"].v.view(B, H, W, C)[0, :8, :16].sum((0, 1))
+    defect = torch.zeros_like(ref["dm"].v)
+    defect[0] = tile
+    got = buf[:, 32:32 + C]
+    what = f"kept statistics {case[:4]} unbiased={unbiased} res={use_res} dt={dt}"
+    twice(lambda: ops.conv(x, w, None, y, g, dt, res=res, ln=dict(ln, dm=dm)), got, ref["dm"], what + " dm", defect)
+    R.report(what + " dx", R.assert_within(y, ref["y"], what=what + " dx", layout=R.layout(g)))
+    assert torch.equal(buf[:, :32], guard[:, :32]) and torch.equal(buf[:, 32 + C:], guard[:, 32 + C:])
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("shape", [(2, 32, 32), (1, 16, 48)])
+@pytest.mark.parametrize("form", list(CB.CHAIN_FORMS))
+def test_chain_form_at_small_shapes(form, shape, packed, dt, monkeypatch):
+    """finish_lnf<RESN> (conv_epilogue.h:417-513; EPI 2 and 8 of the 16x16-tile kernel) under C2W_CONV_T3=16: the emitted LayerNorm rows,
+    their 1/sigma and mean and -- where it is written -- the output, each element inside its float64 bound; with C2W_CONV_NO_Y the output
+    buffer keeps its fill to the byte.  The last image's block input is constant (h = 0: the rebuilt residual is mean - m).
+    Measured worst err/bound: hn 0.685, rstd 0.136, mean 0.162, y 0.978."""
+    B, H, W = shape
+    C = 128
+    monkeypatch.setenv("C2W_CONV_T3", "16")
+    ops.knobs_reload()
+    g = _s1(B, H, W, C)
+    assert ops.conv_lnfwd_chain_supported(g, dt) and ops.conv_dispatch(g, dt, fused_ln=True) == _lib.KERNEL_PATCH_16X16
+    npix, HW = B * H * W, H * W
+    x = rnd((npix, C), dt, 1)
+    w = rnd((C, 9, C), dt, 2, scale=1.0 / math.sqrt(9 * C))
+    bias = rnd((C,), ops.DTYPE_F32, 3)
+    wop = w
+    if packed:
+        wop = torch.empty(ops.packed_conv_weights_numel(C, C), dtype=TD[dt], device=dev())
+        ops.pack_conv_weights_batched(w, wop, torch.tensor([[0, 0, C, C]], dtype=torch.int64, device=dev()), 1, dt)
+    const = slice(npix - HW, npix) if B > 1 else slice(npix // 2, npix // 2 + 32)
+    co = tuple(t.to(dev()) for t in CB._chain_operands(npix, HW, C, dt, C + 64, const=const))
+    assert co[0][const].abs().max().item() == 0.0
+    y, hn, rstd, mu, kw = CB.chain_launch(lambda *a, **k: ops.conv(*a, wpacked=packed, **k), form, x, wop, bias, g, dt, co)
+    torch.cuda.synchronize()
+    ref = R.conv(x, w, g, dt, bias=bias, **kw)
+    what = f"chain form [{form}] {shape} packed={packed} dt={dt}"
+    if CB.CHAIN_FORMS[form]["no_y"]:
+        assert "y" not in ref and bool((y == 3.0).all())  # not a byte of the output buffer was touched
+    else:
+        R.report(what + " y", R.assert_within(y, ref["y"], what=what + " y", layout=R.layout(g)))
+    R.report(what + " hn", R.assert_within(hn, ref["hn"], what=what + " hn", layout=R.layout(g)))
+    R.report(what + " rstd", R.assert_within(rstd, ref["rstd"], what=what + " rstd"))
+    R.report(what + " mean", R.assert_within(mu, ref["mean"], what=what + " mean"))

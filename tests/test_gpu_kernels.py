@@ -97,14 +97,15 @@ def test_conv_forward(case, dt, naive):
     bias = rnd((wrows,), F32, 3)
     res = rnd((B * Hout * Wout, ldy), dt, 4)
     mul = rnd((B * Hout * Wout, ldy), dt, 5)
-    pre = R.conv_sum(x, w, g)  # the fp64 reference's accumulator, shared by the five epilogues
-    for variant in range(5):
-        kw = [dict(), dict(act=ops.ACT_SILU), dict(res=res), dict(mul=mul, mulmode=ops.MUL_DSILU, res=res), dict()][variant]
+    pre = R.conv_sum(x, w, g)  # the fp64 reference's accumulator, shared by the seven epilogues
+    for variant in range(7):
+        kw = [dict(), dict(act=ops.ACT_SILU), dict(res=res), dict(mul=mul, mulmode=ops.MUL_DSILU, res=res), dict(), dict(act=ops.ACT_RELU),
+              dict(act=ops.ACT_RELU_PAIR)][variant]
         b = None if variant == 3 else bias
         y = torch.full((B * Hout * Wout, ldy), 7.0, dtype=TD[dt], device=dev())
         y_ref = y.clone()
-        y2 = torch.full_like(y, 3.0) if variant == 4 else None  # dual output: pre-activation + silu
-        y2_ref = y2.clone() if variant == 4 else None
+        y2 = torch.full_like(y, 3.0) if variant in (4, 6) else None  # dual output: pre-activation + silu; the ReLU pair's mask
+        y2_ref = y2.clone() if variant in (4, 6) else None
         ops.conv(x, w, b, y, g, dt, naive=naive, y2=y2, **kw)
         E.conv(x, w, b, y_ref, g, dt, y2=y2_ref, **kw)
         torch.cuda.synchronize()
@@ -116,9 +117,14 @@ def test_conv_forward(case, dt, naive):
         R.report(what, R.assert_within(y[:, :Cout], ref["y"], what=what, layout=R.layout(g)))
         if variant == 4:
             R.report(what + " second output", R.assert_within(y2[:, :Cout], ref["y2"], what=what + " second output", layout=R.layout(g)))
-        if variant == 0:  # power check: one tap of input channel 0 missing at the border pixels of image 0
+        if variant == 6:  # every route takes the pair (none refuses it); the mask is held by its consistency with the bounded y
+            R.assert_mask_consistent(y[:, :Cout], y2[:, :Cout], what=what + " mask")
+            assert (y2[:, Cout:] == 3.0).all() and 0.2 < y2[:, :min(wrows, Cout)].float().mean().item() < 0.8
+        if variant in (0, 5, 6):  # power check: one tap of input channel 0 missing at the border pixels of image 0
             t = R.conv_term(x, w, g, 0, slice(0, 1), None if mode == ops.CONV_1X1 else 4, R.border_mask(Hout, Wout))
-            R.assert_rejects(y[:, :Cout].double() - t, ref["y"], what=what + ", planted missing border tap")
+            yc = y[:, :Cout].double()
+            bad = yc - t if variant == 0 else torch.where(yc > 0, yc - t, yc)  # behind a ReLU: missing where the output is positive
+            R.assert_rejects(bad, ref["y"], what=what + ", planted missing border tap")
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])
@@ -276,6 +282,158 @@ def test_conv_silu_pair_outputs(case, dt, naive):
     close(dx, dx_ref, dt, "plain multiplier epilogue")
     R.report(f"plain multiplier {case} dt={dt}", R.assert_within(dx[:, :Cout], R.conv(y, wT, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN)["y"],
                                                                  what="plain multiplier epilogue", layout=R.layout(gd)))
+
+
+def _relu_outputs(what, x, w, bias, g, dt, pre, conv_kw, **epi):
+    """C2W_ACT_RELU and C2W_ACT_RELU_PAIR of one launch geometry (epi: res / mul in front of the pair): the float64 bound on y, the mask's
+    consistency with the stored y, and the planted missing border tap behind the activation.  Returns the pair's (y, y2)."""
+    npix, Cout, ldy = g["B"] * g["Hout"] * g["Wout"], g["Cout"], g["ldy"]
+    t = R.conv_term(x, w, g, 0, slice(0, 1), 4, R.border_mask(g["Hout"], g["Wout"]))
+    for act in (ops.ACT_RELU, ops.ACT_RELU_PAIR):
+        pair = act == ops.ACT_RELU_PAIR
+        kw = dict(epi) if pair else {}
+        y = torch.full((npix, ldy), 7.0, dtype=TD[dt], device=dev())
+        y2 = torch.full_like(y, 3.0) if pair else None
+        ops.conv(x, w, bias, y, g, dt, act=act, y2=y2, **conv_kw, **kw)
+        torch.cuda.synchronize()
+        ref = R.conv(x, w, g, dt, bias=bias, act=act, pre=pre, **kw)
+        tag = f"{what} {'relu pair ' + str(sorted(kw)) if pair else 'relu'} dt={dt}"
+        R.report(tag, R.assert_within(y[:, :Cout], ref["y"], what=tag, layout=R.layout(g)))
+        yc = y[:, :Cout].double()
+        assert yc.min().item() == 0.0 and (y[:, Cout:] == 7.0).all()
+        if pair:
+            R.assert_mask_consistent(y[:, :Cout], y2[:, :Cout], what=tag + " mask")
+            assert (y2[:, Cout:] == 3.0).all()
+        if not kw:
+            R.assert_rejects(torch.where(yc > 0, yc - t, yc), ref["y"], what=tag + ", planted missing border tap")
+    return y, y2
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+@pytest.mark.parametrize("shape", [(2, 32, 32, 128, 128), (1, 16, 48, 128, 192)])
+def test_relu_on_the_16x16_tile_kernel(shape, dt, monkeypatch):
+    """conv_patch_t3_kernel<16> under C2W_CONV_T3=16 at the smallest shapes that reach it: 2 x 4 tiles of one channel tile, and 3 tiles
+    whose second channel tile is half empty (192 rows).
+    Measured worst err/bound: relu 0.992, relu pair 0.992, pair behind multiplier + residual 0.988 (the plain epilogue's own 0.995: a tie of the
+    tile's rounding)."""
+    B, H, W, Cin, Cout = shape
+    monkeypatch.setenv("C2W_CONV_T3", "16")
+    ops.knobs_reload()
+    g = geom(B, H, W, Cin, H, W, Cout, Cout, Cout, ops.CONV_S1)
+    assert ops.conv_dispatch(g, dt) == _lib.KERNEL_PATCH_16X16
+    npix = B * H * W
+    x = rnd((npix, Cin), dt, 1)
+    w = rnd((Cout, 9, Cin), dt, 2, scale=1.0 / math.sqrt(9 * Cin))
+    bias = rnd((Cout,), F32, 3)
+    pre = R.conv_sum(x, w, g)
+    _relu_outputs(f"16x16 tile {shape}", x, w, bias, g, dt, pre, {})
+    _relu_outputs(f"16x16 tile {shape}", x, w, bias, g, dt, pre, {}, res=rnd((npix, Cout), dt, 4), mul=rnd((npix, Cout), dt, 5), mulmode=ops.MUL_PLAIN)
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16])
+@pytest.mark.parametrize("naive", [0, 1, 2])
+def test_relu_sign_edges(dt, naive):
+    """Zero weight rows, so the pre-activation IS the bias: +0, -0, +t, -t with t the smallest subnormal of the storage type, and for fp16
+    +-2^-25, which rounds to zero in the tile.  y is held to its bound (at +t that leaves nothing but t itself in bf16 / fp32, 0 or t in
+    fp16), -0 and +0 compare equal, and the mask must agree with the stored y: on the 8x16-tile kernel, the direct kernel and the
+    gather kernel.  Measured worst err/bound: 0 (every value exact) except 2^-25 in fp16: 0.9995 (it becomes 0, the tile's floor)."""
+    B, H, W, C = 2, 8, 16, 128
+    g = geom(B, H, W, C, H, W, C, C, C, ops.CONV_S1)
+    tiny = {F32: 2.0 ** -149, BF16: 2.0 ** -133, F16: 2.0 ** -24}[dt]
+    vals = [0.0, -0.0, tiny, -tiny] + ([2.0 ** -25, -2.0 ** -25] if dt == F16 else [])
+    bias = torch.tensor(vals, dtype=torch.float32).repeat(C // len(vals) + 1)[:C].to(dev())
+    assert bias.abs().max().item() == max(abs(v) for v in vals)  # (nothing flushed on the way to the device)
+    x = rnd((B * H * W, C), dt, 1)
+    w = torch.zeros((C, 9, C), dtype=TD[dt], device=dev())
+    for act in (ops.ACT_RELU, ops.ACT_RELU_PAIR):
+        y = torch.full((B * H * W, C), 7.0, dtype=TD[dt], device=dev())
+        y2 = torch.full_like(y, 3.0) if act == ops.ACT_RELU_PAIR else None
+        ops.conv(x, w, bias, y, g, dt, act=act, y2=y2, naive=naive)
+        torch.cuda.synchronize()
+        what = f"relu sign edges act={act} dt={dt} naive={naive}"
+        R.report(what, R.assert_within(y, R.conv(x, w, g, dt, bias=bias, act=act)["y"], what=what, layout=R.layout(g)))
+        assert (y >= 0).all()
+        if y2 is not None:
+            R.assert_mask_consistent(y, y2, what=what + " mask")
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16])
+@pytest.mark.parametrize("naive", [0, 1, 2])
+@pytest.mark.parametrize("case", [(ops.CONV_S1, 2, 16, 16, 64, 128, 128, 128), (ops.CONV_S1, 3, 8, 8, 128, 192, 192, 192),
+                                  (ops.CONV_S1, 1, 24, 32, 64, 128, 128, 128)])
+def test_conv_relu_pair_outputs(case, dt, naive):
+    """training epilogue of a res-block's first conv in a ReLU network: y = max(a, 0), y2 = (a > 0) (C2W_ACT_RELU_PAIR), and the input-
+    gradient conv that multiplies by the mask -- both launches inside their float64 bounds.
+    Measured worst err/bound: pair 0.992, masked input gradient 0.495."""
+    mode, B, Hin, Win, Cin, Cout, wrows, ldy = case
+    g = geom(B, Hin, Win, Cin, Hin, Win, Cout, ldy, wrows, mode)
+    x = rnd((B * Hin * Win, Cin), dt, 1)
+    w = rnd((wrows, 9, Cin), dt, 2, scale=1.0 / math.sqrt(9 * Cin))
+    bias = rnd((wrows,), F32, 3)
+    y, y2 = _relu_outputs(f"relu pair {case} naive={naive}", x, w, bias, g, dt, None, dict(naive=naive))
+    y_ref, y2_ref = torch.empty_like(y), torch.empty_like(y)
+    E.conv(x, w, bias, y_ref, g, dt, act=ops.ACT_RELU_PAIR, y2=y2_ref)
+    close(y, y_ref, dt, "relu output")
+    assert (y2 != y2_ref).float().mean().item() < 1e-3  # the two sums round differently next to zero only
+    dx, dx_ref = torch.empty_like(y), torch.empty_like(y)
+    wT = rnd((Cout, 9, Cout), dt, 4, scale=1.0 / math.sqrt(9 * Cout))
+    gd = geom(B, Hin, Win, ldy, Hin, Win, Cout, ldy, Cout, mode)
+    ops.conv(y, wT, None, dx, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN, naive=naive)
+    E.conv(y, wT, None, dx_ref, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN)
+    close(dx, dx_ref, dt, "mask multiplier epilogue")
+    R.report(f"relu mask multiplier {case} dt={dt} naive={naive}", R.assert_within(dx[:, :Cout], R.conv(y, wT, gd, dt, mul=y2, mulmode=ops.MUL_PLAIN)["y"],
+                                                                                  what="mask multiplier epilogue", layout=R.layout(gd)))
+
+
+NAN_ROUTES = {  # route -> (B, H, W, Cin, Cout, knob, naive, kernel family or None)
+    "gather": (2, 16, 16, 64, 128, None, 2, None),
+    "8x16": (2, 16, 32, 128, 128, None, 0, _lib.KERNEL_PATCH_8X16),
+    "16x16": (2, 32, 32, 128, 128, ("C2W_CONV_T3", "16"), 0, _lib.KERNEL_PATCH_16X16),
+    "split-K": (3, 32, 32, 256, 256, None, 0, _lib.KERNEL_PATCH_8X16),
+}
+
+
+@pytest.mark.parametrize("dt", [BF16, F16])
+@pytest.mark.parametrize("route", list(NAN_ROUTES))
+def test_nan_passes_through_relu(route, dt, monkeypatch):
+    """One NaN in x at an interior pixel of the second image: y must be NaN on exactly the footprint where the float64 reference is (3x3
+    pixels x all weight rows) -- torch.relu, the reference network and tests/emu_ops.py propagate NaN, and a NaN that the next activation
+    erases never reaches the loss, the gradients or the grad scaler -- finite and inside the bound elsewhere; the pair's mask is 0 on the
+    footprint.  fmaxf(v, 0.f) (v_max_f32 under IEEE mode) returned 0 for the NaN: these cases failed before common.h::relu_f.
+    Measured worst err/bound outside the footprint: 0.992 (gather 0.991, 8x16 0.990, 16x16 0.992, split-K 0.991)."""
+    B, H, W, Cin, Cout, kn, naive, fam = NAN_ROUTES[route]
+    if kn:
+        monkeypatch.setenv(*kn)
+        ops.knobs_reload()
+    g = geom(B, H, W, Cin, H, W, Cout, Cout, Cout, ops.CONV_S1)
+    if fam is not None:
+        assert ops.conv_dispatch(g, dt) == fam
+    npix = B * H * W
+    x = rnd((npix, Cin), dt, 1)
+    x.view(B, H, W, Cin)[1, 5, 7, 3] = float("nan")
+    w = rnd((Cout, 9, Cin), dt, 2, scale=1.0 / math.sqrt(9 * Cin))
+    bias = rnd((Cout,), F32, 3)
+    kw = dict(naive=naive)
+    if route == "split-K":
+        ns, nbytes = ops.conv_splitk_plan(g, dt, ops.ACT_RELU)
+        assert ns > 1
+        kw["splitk"] = (torch.empty(nbytes // 4, dtype=torch.float32, device=dev()), ns)
+    foot = torch.zeros((B, H, W, Cout), dtype=torch.bool, device=dev())
+    foot[1, 4:7, 6:9] = True
+    for act in (ops.ACT_RELU,) if route == "split-K" else (ops.ACT_RELU, ops.ACT_RELU_PAIR):  # (the split-K plan takes no second output)
+        y = torch.full((npix, Cout), 7.0, dtype=TD[dt], device=dev())
+        y2 = torch.full_like(y, 3.0) if act == ops.ACT_RELU_PAIR else None
+        ops.conv(x, w, bias, y, g, dt, act=act, y2=y2, **kw)
+        torch.cuda.synchronize()
+        ref = R.conv(x, w, g, dt, bias=bias, act=act)
+        assert torch.equal(torch.isnan(ref["y"].v).view(B, H, W, Cout), foot)
+        what = f"NaN through relu {route} act={act} dt={dt}"
+        worst, n = R.assert_nan_footprint(y, ref["y"], what=what, layout=R.layout(g))
+        assert n == 9 * Cout
+        R.report(what, worst)
+        if y2 is not None:
+            R.assert_mask_consistent(y, y2, what=what + " mask")
+            assert (y2.view(B, H, W, Cout)[foot] == 0).all()
 
 
 @pytest.mark.parametrize("dt", [BF16, F16])
@@ -961,6 +1119,11 @@ def test_gemv_f32_vs_emulation(rows, K, ldk, act):
     torch.cuda.synchronize()
     assert torch.equal(y[rows:].cpu(), ref[rows:])
     close(y[:rows].cpu(), ref[:rows], F32, "gemv")
+    if act == ops.ACT_RELU:  # a NaN in x reaches every row, through the activation too (torch.relu keeps it; fmaxf(s, 0.f) gave 0)
+        x[1] = float("nan")
+        ops.gemv_f32(x, Wm, b, y, rows, K, ldk, act)
+        torch.cuda.synchronize()
+        assert torch.isnan(y[:rows]).all() and torch.equal(y[rows:].cpu(), ref[rows:])
     if ldk % 32 == 0 and K == ldk and act != ops.ACT_RELU:
         y2 = torch.zeros((1, rows), device=dev())
         ops.conv(x.view(1, ldk), Wm, b, y2, geom(1, 1, 1, ldk, 1, 1, rows, rows, rows, ops.CONV_1X1), F32, act=act)

@@ -14,6 +14,7 @@ the two-stream mode moot.  What this proves is kernel against reference at the e
 right arguments (tests/test_engine_emulated.py and the oracle parities), and nothing about races between launches.
 """
 import time
+from collections import Counter
 
 import pytest
 import torch
@@ -39,9 +40,9 @@ REPORTS = {}  # test id -> Report: the final test looks at the families and rout
 FAMILIES = {v: k for k, v in vars(_lib).items() if k.startswith("KERNEL_")}
 
 
-def _net(channels=65, seed=3, **cfg):
+def _net(channels=65, seed=3, activation=torch.nn.SiLU, **cfg):
     torch.manual_seed(seed)
-    return ScoreUNet(channels=channels, spatial=2, activation=torch.nn.SiLU, **dict(CFG, **cfg)).to(DEV)
+    return ScoreUNet(channels=channels, spatial=2, activation=activation, **dict(CFG, **cfg)).to(DEV)
 
 
 def _data(channels=65, H=32, W=32, seed=1, n=B):
@@ -181,9 +182,9 @@ def test_two_training_steps_at_52_channels(monkeypatch, request, precision):
     _expect(rep, "conv:kvalid")
 
 
-def _sampler(precision, gamma, exact=False, steps=2, corrections=1, L=11):
+def _sampler(precision, gamma, exact=False, steps=2, corrections=1, L=11, activation=torch.nn.SiLU):
     F, k = 13, 2
-    net = _net().eval().requires_grad_(False)
+    net = _net(activation=activation).eval().requires_grad_(False)
     net.precision = precision
     pipe = SDAPipeline()
     g = torch.Generator().manual_seed(5)
@@ -218,6 +219,22 @@ def test_two_sampler_steps_with_a_corrector(monkeypatch, request, precision, gam
     assert (rep.flags["guidance:gamma[F]"] > 0) == (gamma == "per-variable")
 
 
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_two_training_steps_of_a_relu_network(monkeypatch, request, precision):
+    """case 9: torch.nn.ReLU, the reference UNet's own default activation (model/nn.py:118): C2W_ACT_RELU_PAIR on every block's first conv,
+    its mask as the multiplier of the input-gradient convs; every conv launch with its float64 bound, the mask by its consistency rule"""
+    rep = _replay(monkeypatch, request, _two_steps(precision, _windows(), cfg=dict(activation=torch.nn.ReLU)))
+    _expect(rep, "conv:relu_pair", "conv:mul", "conv:lnf", "conv:ln.rstd")
+    assert rep.bounded_flags["conv:relu_pair"] == rep.flags["conv:relu_pair"] and rep.bounded["conv"] == rep.checked["conv"]
+
+
+def test_one_sampler_step_of_a_relu_network(monkeypatch, request):
+    """case 10: inference takes C2W_ACT_RELU in the accumulator epilogue, through the split-K reduction too, and the gemv's ReLU"""
+    rep = _replay(monkeypatch, request, _sampler("bf16", 1e-2, steps=1, corrections=0, activation=torch.nn.ReLU))
+    _expect(rep, "conv:relu", "conv:splitk")
+    assert rep.bounded_flags["conv:relu"] == rep.flags["conv:relu"] and rep.bounded["conv"] == rep.checked["conv"]
+
+
 def test_one_sampler_step_with_streamed_exact_guidance(monkeypatch, request):
     """case 7: the window-list kernels and backward(want_dw=False)"""
     rep = _replay(monkeypatch, request, _sampler("bf16", 1e-2, exact=True, steps=1, corrections=0), mode="exact")
@@ -238,7 +255,7 @@ def test_validation_on_two_batches(monkeypatch, request):
     assert rep.seen["sq_err_levels"] == 2
 
 
-CASES = 19  # parametrised cases above
+CASES = 22  # parametrised cases above
 
 
 def test_every_conv_family_and_attention_route_was_reached():
@@ -246,8 +263,13 @@ def test_every_conv_family_and_attention_route_was_reached():
     if len(REPORTS) < CASES:
         return
     fams, routes = set(), set()
+    seen, bounded = Counter(), Counter()
     for rep in REPORTS.values():
         fams |= set(rep.families)
         routes |= set(rep.routes)
+        seen.update(rep.flags)
+        bounded.update(rep.bounded_flags)
+    for flag in ("conv:relu", "conv:relu_pair", "conv:resn", "conv:no_y", "conv:lnf.mean", "conv:ln.rstd"):  # no conv launch left unmodelled
+        assert seen[flag] > 0 and bounded[flag] == seen[flag], f"{flag}: {seen[flag]} launches seen, {bounded[flag]} with a float64 bound"
     assert fams == set(FAMILIES), f"conv families not reached: {[FAMILIES[f] for f in set(FAMILIES) - fams]}"
     assert routes == {"valu", "t64", "blocks"}, routes

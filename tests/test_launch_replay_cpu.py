@@ -17,9 +17,9 @@ from climate2weather_amd.training import Trainer
 CPU = torch.device("cpu")
 
 
-def _net(hidden=(64, 64), blocks=(1, 1)):
+def _net(hidden=(64, 64), blocks=(1, 1), activation=torch.nn.SiLU):
     torch.manual_seed(3)
-    return ScoreUNet(channels=6, spatial=2, activation=torch.nn.SiLU, embedding_dim=64, hidden_channels=list(hidden), hidden_blocks=list(blocks),
+    return ScoreUNet(channels=6, spatial=2, activation=activation, embedding_dim=64, hidden_channels=list(hidden), hidden_blocks=list(blocks),
                      attention_levels=[1], kernel_size=3, padding_mode="zeros")
 
 
@@ -28,14 +28,14 @@ def _batch(B=2, seed=1):
     return torch.randn(B, 6, 16, 16, generator=gen) * 0.5 + 0.5, torch.rand(B, generator=gen), torch.randn(B, 6, 16, 16, generator=gen)
 
 
-def _train(monkeypatch, planted=None, packed=False, steps=1, precision="bf16"):
+def _train(monkeypatch, planted=None, packed=False, steps=1, precision="bf16", activation=torch.nn.SiLU):
     emu_ops.install(monkeypatch, c2w_ops)
     monkeypatch.delenv("C2W_DETERMINISTIC", raising=False)
     if packed:
         monkeypatch.setattr(emu_ops, "PACKED_FROM_PIXELS", 1)
     rep = LR.install(monkeypatch, c2w_ops, mode="default", planted=planted)
     x, t, eps = _batch()
-    tr = Trainer(_net(), lr=1e-3, precision=precision, ema_rates=[0.9])
+    tr = Trainer(_net(activation=activation), lr=1e-3, precision=precision, ema_rates=[0.9])
     for _ in range(steps):
         tr.step(x, t=t, eps=eps)
     return rep
@@ -54,7 +54,18 @@ def test_every_launch_of_a_bf16_training_step_is_checked_with_ratio_zero(monkeyp
         assert rep.seen[name] > 0, name
     assert set(rep.unchecked) <= set(LR.UNCHECKED) | {n for n in rep.unchecked if LR.is_host_query(n)}
     assert not _all_zero(rep), _all_zero(rep)
-    assert rep.bounded["conv"] > 0 and rep.bounded["conv_wgrad"] + rep.bounded["conv_wgrad_grouped"] > 0 and rep.bounded["adamw_ema"] > 0
+    assert rep.bounded["conv"] == rep.checked["conv"] and rep.bounded["conv_wgrad"] + rep.bounded["conv_wgrad_grouped"] > 0 and rep.bounded["adamw_ema"] > 0
+
+
+def test_every_launch_of_a_relu_training_step_is_checked_with_ratio_zero(monkeypatch):
+    """the reference UNet's own default activation: the ReLU pair in training (the mask's consistency rule runs on every such launch), and
+    no conv launch without its float64 bound"""
+    rep = _train(monkeypatch, activation=torch.nn.ReLU)
+    rep.assert_clean()
+    assert rep.seen == rep.checked and not _all_zero(rep), _all_zero(rep)
+    assert rep.flags["conv:relu_pair"] > 0 and rep.bounded_flags["conv:relu_pair"] == rep.flags["conv:relu_pair"]
+    assert rep.worst["conv"]["fp64 conv relu mask"] == 0.0
+    assert rep.bounded["conv"] == rep.checked["conv"]
 
 
 def test_every_launch_of_a_deterministic_step_is_checked(monkeypatch):
