@@ -40,17 +40,13 @@ plotting, more than 64 members on the kernel (the general route takes them), and
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
-from .ssim import _dense32
-from .wasserstein import MOMENT_CHUNK_ELEMS
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
+from .ensemble_host import VariableReport, check_ensemble, chunk_step, dense32, scratch, variable_names
+from .ensemble_host import on_device as _on_device
 
 
 def consistency_factor(M: int) -> float:
@@ -71,7 +67,7 @@ def _general(x: torch.Tensor, y: torch.Tensor, sums: torch.Tensor, cells: Option
         return
     k = torch.arange(1, M, dtype=torch.float64, device=x.device)
     w = (k * (M - k))[:, None, None, None]
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, M * F * hw))
+    step = chunk_step(M * F * hw)
     for i in range(0, T, step):
         xs, ys = x[:, i:i + step].double(), y[i:i + step].double()
         ok = torch.isfinite(xs).all(dim=0) & torch.isfinite(ys)
@@ -93,16 +89,7 @@ def _general(x: torch.Tensor, y: torch.Tensor, sums: torch.Tensor, cells: Option
 def _launch(x, y, sums, cells, M, T, F, hw) -> bool:
     if not ops.crps_supported(hw, M):
         return False
-    nbytes = ops.crps_scratch_bytes(T, F, hw)
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device) if nbytes else None
-    return ops.crps_terms(x, y, sums, cells, scratch, M, T, F, hw)
-
-
-def _check(samples: torch.Tensor, truth: torch.Tensor) -> None:
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (T, F, H, W)")
-    if not (samples.is_floating_point() and truth.is_floating_point()):
-        raise ValueError(f"samples ({samples.dtype}) and truth ({truth.dtype}) must be floating point")
+    return ops.crps_terms(x, y, sums, cells, scratch(ops.crps_scratch_bytes(T, F, hw), x.device), M, T, F, hw)
 
 
 def ensemble_terms(samples: torch.Tensor, truth: torch.Tensor, *, cells: bool = False):
@@ -113,10 +100,10 @@ def ensemble_terms(samples: torch.Tensor, truth: torch.Tensor, *, cells: bool = 
 
     On the GPU, ``H W`` a multiple of 4 and ``1 <= M <= 64`` take the kernel; everything else and CPU tensors take the same definition
     in float64.  No members (``M = 0``) gives NaN throughout."""
-    _check(samples, truth)
+    check_ensemble(samples, truth, floating=True)
     M, T, F, H, W = (int(s) for s in samples.shape)
     hw = H * W
-    x, y = _dense32(samples).view(M, T, F, hw), _dense32(truth).view(T, F, hw)
+    x, y = dense32(samples).view(M, T, F, hw), dense32(truth).view(T, F, hw)
     sums = torch.empty((T, F, 4), dtype=torch.float64, device=x.device)
     per_cell = torch.empty((4, T, F, hw), dtype=torch.float32, device=x.device) if cells else None
     if T * F * hw == 0:
@@ -153,20 +140,11 @@ def spread_skill(samples: torch.Tensor, truth: torch.Tensor) -> Tuple[torch.Tens
     return _spread_skill_of(tot[:, 2], tot[:, 3], T * hw, M)
 
 
-class CrpsReport:
+class CrpsReport(VariableReport):
     """Per variable, as device tensors: ``crps``, ``crps_fair``, ``rmse``, ``spread``, ``ratio`` (0-d float64, over all times and cells)
     and ``crps_by_time (T,)``.  There is no ``all_variables``: a score in a variable's own unit has no meaning across units."""
 
     KEYS = ("crps", "crps_fair", "rmse", "spread", "ratio")
-
-    def __init__(self, names: Sequence[str], variables: List[dict]):
-        self.names, self.variables = list(names), variables
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
 
     def as_dict(self, prefix: str = "crps") -> dict:
         """flat ``{f"{prefix}/{name}/{key}": float}`` for a logger, ``key`` in ``KEYS`` (one device-to-host copy)"""
@@ -180,11 +158,9 @@ def crps_report(samples: torch.Tensor, truth: torch.Tensor, names: Optional[Sequ
     """The scores of an ensemble ``samples (M, L, F, H, W)`` against ``truth (L, F, H, W)`` per variable, from one pass over the fields.
     The fields are expected DE-NORMALISED, as the reference's are: CRPS, RMSE and spread carry the variable's unit.  ``names``: one per
     variable, default ``var0 ...``."""
-    _check(samples, truth)
+    check_ensemble(samples, truth, floating=True)
     M, T, F, H, W = (int(s) for s in samples.shape)
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     sums = ensemble_terms(samples, truth)
     hw = H * W
     tot = sums.sum(dim=0)  # (F, 4)

@@ -3,8 +3,7 @@ c2w_vario_*), in the style of ``ops.py``; the host side that calls them is ``mul
 from __future__ import annotations
 
 from . import _lib
-from ._lib import check
-from .ops import _p, _stream
+from .ops import _accepted, _nbytes, _p, _stream
 
 
 def escore_supported(hw: int, M: int) -> bool:
@@ -21,12 +20,7 @@ def escore_pairs(x, y, d2, scratch, M, planes, hw) -> bool:
     (M, planes, hw) and y (planes, hw) -- dense fp32, 16-byte aligned (include/c2w_hip.h::c2w_escore_pairs: the definition, the pair
     order, the fixed summation order).  scratch: a float64 device tensor of at least ``escore_scratch_bytes`` bytes, or None where that
     is 0.  False if hw or M is not supported -- nothing is written and the caller takes the general definition."""
-    nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    rc = _lib.load().c2w_escore_pairs(_p(x), _p(y), _p(d2), _p(scratch), nbytes, M, planes, hw, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_escore_pairs")
-    return True
+    return _accepted(_lib.load().c2w_escore_pairs(_p(x), _p(y), _p(d2), _p(scratch), _nbytes(scratch), M, planes, hw, _stream()), "c2w_escore_pairs")
 
 
 def vario_supported(H: int, W: int, R: int, M: int, order2: int) -> bool:
@@ -43,9 +37,5 @@ def vario_terms(x, y, V, scratch, M, planes, H, W, R, order2) -> bool:
     ``((g_y - g_x)^2, g_y, g_x)`` at the order ``order2 / 2``, from x (M, planes, H, W) and y (planes, H, W), dense fp32
     (include/c2w_hip.h::c2w_vario_terms).  scratch as for ``escore_pairs``.  False if the shape, R, M or the order is not supported --
     nothing is written and the caller takes the general definition."""
-    nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    rc = _lib.load().c2w_vario_terms(_p(x), _p(y), _p(V), _p(scratch), nbytes, M, planes, H, W, R, order2, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_vario_terms")
-    return True
+    rc = _lib.load().c2w_vario_terms(_p(x), _p(y), _p(V), _p(scratch), _nbytes(scratch), M, planes, H, W, R, order2, _stream())
+    return _accepted(rc, "c2w_vario_terms")

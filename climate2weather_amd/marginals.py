@@ -39,12 +39,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .ssim import _dense32
-from .wasserstein import MOMENT_CHUNK_ELEMS
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
+from .ensemble_host import VariableReport, check_ensemble, chunk_step, datasets, dense32, scratch, variable_names
+from .ensemble_host import on_device as _on_device
 
 
 def _factor(n: int, bw_method) -> float:
@@ -71,7 +67,7 @@ def bandwidth(values: torch.Tensor, bw_method="scott") -> torch.Tensor:
     R = int(x.shape[0])
     mean = x.sum(dim=(1, 3), dtype=torch.float64) / n
     ss = torch.zeros((R, F), dtype=torch.float64, device=values.device)
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, R * F * H * W))
+    step = chunk_step(R * F * H * W)
     for i in range(0, T, step):
         ss += ((x[:, i:i + step].double() - mean[:, None, :, None]) ** 2).sum(dim=(1, 3))
     return (factor * torch.sqrt(ss / (n - 1))).view(lead + (F,))
@@ -83,7 +79,7 @@ def _general(x: Optional[torch.Tensor], y: Optional[torch.Tensor], grid: torch.T
     n_rep, T, F, hw = x.shape
     N = int(grid.shape[1])
     n = T * hw
-    step = max(1, MOMENT_CHUNK_ELEMS // N)
+    step = chunk_step(N)
     for ds in range(int(dens.shape[0])):
         f = ds % F if ds < n_rep * F else ds - n_rep * F
         v = (x[ds // F, :, f] if ds < n_rep * F else y[:, f]).reshape(-1)
@@ -99,9 +95,8 @@ def _launch(x, y, grid, h, dens, n_rep, T, F, hw, N) -> bool:
         return False
     pivot = (0.5 * (grid[:, 0] + grid[:, -1])).to(torch.float32)
     offsets = (grid - pivot.double()[:, None]).to(torch.float32).contiguous()
-    nbytes = ops.kde_scratch_bytes(int(dens.shape[0]), T * hw, N)
-    scratch = torch.empty((max(1, nbytes // 8),), dtype=torch.float64, device=x.device)
-    return ops.kde_eval(x, y, offsets, pivot, h, scratch, dens, n_rep, T, F, hw, N)
+    ws = scratch(ops.kde_scratch_bytes(int(dens.shape[0]), T * hw, N), x.device, optional=False)
+    return ops.kde_eval(x, y, offsets, pivot, h, ws, dens, n_rep, T, F, hw, N)
 
 
 def gaussian_kde(values: torch.Tensor, grid: torch.Tensor, *, bw_method="scott", truth: Optional[torch.Tensor] = None):
@@ -115,23 +110,14 @@ def gaussian_kde(values: torch.Tensor, grid: torch.Tensor, *, bw_method="scott",
     float64.  A data set with a NaN or inf value, fewer than two values or zero spread is NaN throughout."""
     if values.dim() < 4 or grid.dim() != 2 or int(grid.shape[0]) != int(values.shape[-3]) or int(grid.shape[1]) < 1:
         raise ValueError(f"values {tuple(values.shape)} must be (..., T, F, H, W) and grid {tuple(grid.shape)} (F, N) with N >= 1")
-    if truth is not None and tuple(truth.shape) != tuple(values.shape[-4:]):
-        raise ValueError(f"truth {tuple(truth.shape)} must be {tuple(values.shape[-4:])} = (T, F, H, W) of the values")
-    lead = tuple(values.shape[:-4])
+    x, y, lead = datasets(values, truth)
     T, F, H, W = (int(s) for s in values.shape[-4:])
-    hw, N = H * W, int(grid.shape[1])
+    n_rep, hw, N = int(x.shape[0]), H * W, int(grid.shape[1])
     if T * hw < 1 or F < 1:
         raise ValueError("an empty data set has no density")
-    x = _dense32(values)
-    y = None if truth is None else _dense32(truth)
     grid = grid.to(device=x.device, dtype=torch.float64).contiguous()
-    n_rep = 1
-    for s in lead:
-        n_rep *= int(s)
-    x = x.view(n_rep, T, F, hw)
     h = bandwidth(x.view(n_rep, T, F, H, W), bw_method).reshape(-1)
     if y is not None:
-        y = y.view(T, F, hw)
         h = torch.cat([h, bandwidth(y.view(T, F, H, W), bw_method)])
     h = h.contiguous()
     dens = torch.empty((int(h.shape[0]), N), dtype=torch.float64, device=x.device)
@@ -146,7 +132,7 @@ def _pit_general(x: torch.Tensor, y: torch.Tensor, counts: torch.Tensor) -> None
     M, T, F, hw = x.shape
     counts.zero_()
     bin0 = (torch.arange(F, device=x.device) * (M + 1))[None, :, None]
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, M * F * hw))
+    step = chunk_step(M * F * hw)
     for i in range(0, T, step):
         r = (x[:, i:i + step] <= y[None, i:i + step]).sum(dim=0)  # (t, F, hw) int64
         counts.view(-1).scatter_add_(0, (r + bin0).reshape(-1), torch.ones(r.numel(), dtype=torch.int64, device=x.device))
@@ -156,10 +142,9 @@ def pit_counts(samples: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
     """``samples (M, T, F, H, W)`` against ``truth (T, F, H, W)`` -> ``counts (F, M + 1)`` int64 on the same device: per variable the
     number of (time, cell) at which exactly ``r`` members are ``<=`` the truth (module docstring).  ``counts.sum(-1) == T H W``.  On the
     GPU ``H W`` a multiple of 4 and ``M <= 64`` take the kernel."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape) or int(samples.shape[0]) < 1:
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M >= 1,) + truth {tuple(truth.shape)} = (T, F, H, W)")
+    check_ensemble(samples, truth, members="M >= 1")
     M, T, F, H, W = (int(s) for s in samples.shape)
-    x, y = _dense32(samples).view(M, T, F, H * W), _dense32(truth).view(T, F, H * W)
+    x, y = dense32(samples).view(M, T, F, H * W), dense32(truth).view(T, F, H * W)
     counts = torch.empty((F, M + 1), dtype=torch.int64, device=x.device)
     if T * F * H * W == 0:
         return counts.zero_()
@@ -172,20 +157,15 @@ def _pit_density(counts: torch.Tensor, M: int) -> torch.Tensor:
     return counts.double() * M / counts.sum(dim=-1, keepdim=True).double()
 
 
-class MarginalsReport:
+class MarginalsReport(VariableReport):
     """Per variable, what the reference's ``kde_and_pmf`` saves and draws, as device tensors: ``x (N,)`` the grid, ``gt (N,)`` the truth's
     density and ``samples (M, N)`` the members' (the three arrays of ``kde_1000.npz``, exp/figures.py:81-83); ``counts (M + 1,)`` int64
     the rank histogram and ``density (M + 1,)`` its ``density=True`` form (:180-192).  ``all_variables``: ``counts`` and ``density`` over
     all variables together (:226-241)."""
 
     def __init__(self, names: Sequence[str], variables: List[dict], all_variables: dict):
-        self.names, self.variables, self.all_variables = list(names), variables, all_variables
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
+        super().__init__(names, variables)
+        self.all_variables = all_variables
 
     def as_dict(self, prefix: str = "marginals") -> dict:
         """flat ``{name: float}`` for a logger (one device-to-host copy): per variable and for all variables together ``pit_mean``, the
@@ -231,16 +211,13 @@ def marginals_report(samples: torch.Tensor, truth: torch.Tensor, *, n_points: in
     computes them: the densities of the truth and of every member at ``n_points`` points between the joint minimum and maximum of each
     variable, and the rank histogram per variable and over all variables.  The fields are expected DE-NORMALISED, as the reference's
     are.  ``names``: one per variable, default ``var0 ...``."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape) or int(samples.shape[0]) < 1:
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M >= 1,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    check_ensemble(samples, truth, time="L", members="M >= 1")
     M, F = int(samples.shape[0]), int(truth.shape[1])
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     n_points = int(n_points)
     if n_points < 1:
         raise ValueError("n_points >= 1")
-    s, g = _dense32(samples), _dense32(truth)
+    s, g = dense32(samples), dense32(truth)
     grid = report_grid(s, g, n_points)
     dens_s, dens_g = gaussian_kde(s, grid, truth=g)  # (M, F, N), (F, N)
     counts = pit_counts(s, g)                        # (F, M + 1)

@@ -56,15 +56,11 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import escore_ops
-from .ssim import _dense32
-from .wasserstein import MOMENT_CHUNK_ELEMS
+from .ensemble_host import VariableReport, check_ensemble, chunk_step, dense32, scratch, variable_names
+from .ensemble_host import on_device as _on_device
 
 NAN = float("nan")
 KERNEL_ORDERS = {0.5: 1, 1.0: 2, 2.0: 4}  # p -> the kernel's order2 = 2 p
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
 
 
 def offsets(radius: int) -> List[Tuple[int, int]]:
@@ -81,19 +77,12 @@ def pair_index(M: int, i: int, j: int) -> int:
     return i * (2 * (M + 1) - i - 1) // 2 + (j - i - 1)
 
 
-def _check(samples: torch.Tensor, truth: torch.Tensor) -> None:
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (T, F, H, W)")
-    if not (samples.is_floating_point() and truth.is_floating_point()):
-        raise ValueError(f"samples ({samples.dtype}) and truth ({truth.dtype}) must be floating point")
-
-
 # ---------------------------------------------------------------------------------------------------------------- energy score
 
 def _general_pairs(x: torch.Tensor, y: torch.Tensor, d2: torch.Tensor) -> None:
     """The definition for any shape, any M and any device, float64 end to end: x (M, T, F, hw), y (T, F, hw), d2 (T, F, P)."""
     M, T, F, hw = x.shape
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, (M + 1) * F * hw))
+    step = chunk_step((M + 1) * F * hw)
     for t0 in range(0, T, step):
         rows = torch.cat([y[None, t0:t0 + step], x[:, t0:t0 + step]]).double()  # (M + 1, t, F, hw)
         bad = ~torch.isfinite(rows).all(dim=-1)                                   # (M + 1, t, F)
@@ -110,9 +99,7 @@ def _general_pairs(x: torch.Tensor, y: torch.Tensor, d2: torch.Tensor) -> None:
 def _launch_pairs(x, y, d2, M, planes, hw) -> bool:
     if not escore_ops.escore_supported(hw, M):
         return False
-    nbytes = escore_ops.escore_scratch_bytes(planes, hw, M)
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device) if nbytes else None
-    return escore_ops.escore_pairs(x, y, d2, scratch, M, planes, hw)
+    return escore_ops.escore_pairs(x, y, d2, scratch(escore_ops.escore_scratch_bytes(planes, hw, M), x.device), M, planes, hw)
 
 
 def pair_sqdist(samples: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
@@ -120,10 +107,10 @@ def pair_sqdist(samples: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
     the squared Euclidean distance of every pair ``i < j`` of the rows ``truth, member 1 .. member M``, row-major (``pair_index``), so
     the first ``M`` entries are truth against member.  Any float dtype and any strides: a strided or 16-bit input costs one dense fp32
     copy.  No members gives ``P = 0``."""
-    _check(samples, truth)
+    check_ensemble(samples, truth, floating=True)
     M, T, F, H, W = (int(s) for s in samples.shape)
     hw = H * W
-    x, y = _dense32(samples).view(M, T, F, hw), _dense32(truth).view(T, F, hw)
+    x, y = dense32(samples).view(M, T, F, hw), dense32(truth).view(T, F, hw)
     d2 = torch.empty((T, F, M * (M + 1) // 2), dtype=torch.float64, device=x.device)
     if d2.numel() == 0:
         return d2
@@ -151,7 +138,7 @@ def truth_scale(truth: torch.Tensor) -> torch.Tensor:
     n = T * H * W
     mean = truth.sum(dim=(0, 2, 3), dtype=torch.float64) / n
     ss = torch.zeros(F, dtype=torch.float64, device=truth.device)
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, F * H * W))
+    step = chunk_step(F * H * W)
     for i in range(0, T, step):
         ss += ((truth[i:i + step].double() - mean[None, :, None, None]) ** 2).sum(dim=(0, 2, 3))
     return torch.sqrt(ss / n)
@@ -210,7 +197,7 @@ def _general_vario(x: torch.Tensor, y: torch.Tensor, V: torch.Tensor, R: int, p:
     if M == 0:
         V.fill_(NAN)
         return
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, (M + 1) * F * H * W))
+    step = chunk_step((M + 1) * F * H * W)
     for t0 in range(0, T, step):
         xs, ys = x[:, t0:t0 + step].double(), y[t0:t0 + step].double()
         bad = ~(torch.isfinite(xs).all(dim=0) & torch.isfinite(ys))  # (t, F, H, W)
@@ -233,9 +220,7 @@ def _launch_vario(x, y, V, M, planes, H, W, R, p) -> bool:
     order2 = KERNEL_ORDERS.get(p)
     if order2 is None or not escore_ops.vario_supported(H, W, R, M, order2):
         return False
-    nbytes = escore_ops.vario_scratch_bytes(planes, H, W, R)
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device) if nbytes else None
-    return escore_ops.vario_terms(x, y, V, scratch, M, planes, H, W, R, order2)
+    return escore_ops.vario_terms(x, y, V, scratch(escore_ops.vario_scratch_bytes(planes, H, W, R), x.device), M, planes, H, W, R, order2)
 
 
 def variogram_terms(samples: torch.Tensor, truth: torch.Tensor, *, radius: int, p: float = 0.5) -> torch.Tensor:
@@ -243,11 +228,11 @@ def variogram_terms(samples: torch.Tensor, truth: torch.Tensor, *, radius: int, 
     offset of ``offsets(radius)`` the sums over the cell pairs inside the field of ``((g_y - g_x)^2, g_y, g_x)`` at order ``p`` (module
     docstring).  An offset that does not fit into the field has no pairs and three zeros.  Any float dtype and any strides.  No members
     gives NaN throughout."""
-    _check(samples, truth)
+    check_ensemble(samples, truth, floating=True)
     p = _check_order(p)
     offs = offsets(radius)
     M, T, F, H, W = (int(s) for s in samples.shape)
-    x, y = _dense32(samples), _dense32(truth)
+    x, y = dense32(samples), dense32(truth)
     V = torch.empty((T, F, len(offs), 3), dtype=torch.float64, device=x.device)
     if T * F == 0:
         return V
@@ -311,7 +296,7 @@ def variogram_by_lag(samples: torch.Tensor, truth: torch.Tensor, *, radius: int,
 
 # ---------------------------------------------------------------------------------------------------------------- report
 
-class MultivariateReport:
+class MultivariateReport(VariableReport):
     """Per variable, as device tensors: ``energy``, ``energy_fair``, ``variogram`` (0-d float64, the mean over the times) and
     ``energy_by_time``, ``variogram_by_time (T,)``, ``variogram_truth``, ``variogram_ensemble (L,)`` by ``lag (L,)``.  ``joint`` holds
     the energy score of all variables as one scaled vector: ``energy``, ``energy_fair`` (0-d) and ``energy_by_time (T,)``.  There is no
@@ -321,13 +306,8 @@ class MultivariateReport:
     JOINT_KEYS = ("energy", "energy_fair")
 
     def __init__(self, names: Sequence[str], variables: List[dict], joint: dict, lag: torch.Tensor):
-        self.names, self.variables, self.joint, self.lag = list(names), variables, joint, lag
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
+        super().__init__(names, variables)
+        self.joint, self.lag = joint, lag
 
     def as_dict(self, prefix: str = "multivariate") -> dict:
         """flat ``{f"{prefix}/{name}/{key}": float}`` for a logger, ``key`` in ``KEYS``, and ``f"{prefix}/joint/{key}"``, ``key`` in
@@ -347,12 +327,10 @@ def multivariate_report(samples: torch.Tensor, truth: torch.Tensor, names: Optio
     kernel over the fields.  The fields are expected DE-NORMALISED, as the reference's are: the energy score carries the variable's
     unit, the variogram score its unit to the power ``2 p``; the joint energy score divides variable ``f`` by ``scale[f]`` (default: the
     truth's population standard deviation).  ``names``: one per variable, default ``var0 ...``."""
-    _check(samples, truth)
+    check_ensemble(samples, truth, floating=True)
     beta = _check_beta(beta)
     M, T, F, H, W = (int(s) for s in samples.shape)
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     w = _weights(weights, radius, samples.device)
     d2 = pair_sqdist(samples, truth)
     V = variogram_terms(samples, truth, radius=radius, p=p)

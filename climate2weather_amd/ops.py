@@ -28,6 +28,19 @@ def _p(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _nbytes(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else t.numel() * t.element_size()
+
+
+def _accepted(rc: int, what: str) -> bool:
+    """the return code of an entry point that may decline its arguments: False for -3 (not supported: nothing was written and the caller
+    takes its general route), an error for any other failure, else True"""
+    if rc == -3:
+        return False
+    check(rc, what)
+    return True
+
+
 def _stream():
     # the raw handle of torch's current stream on the current device: 0.5 us, against 7 us through torch.cuda.current_stream() (a
     # Stream object per call) -- 640 launches per training step, and every one of the first launches of a step sits on the host's
@@ -253,10 +266,6 @@ def ln_forward(x, m, y, npix, HW, C, ldm, eps, unbiased, dtype):
     check(_lib.load().c2w_ln_forward(_p(x), _p(m), _p(y), npix, HW, C, ldm, eps, int(unbiased), dtype, _stream()), "c2w_ln_forward")
 
 
-def _nbytes(t: torch.Tensor) -> int:
-    return t.numel() * t.element_size()
-
-
 def ln_backward_det_scratch_bytes(npix, HW, C, ldm) -> int:
     return int(_lib.load().c2w_ln_backward_det_scratch_bytes(npix, HW, C, ldm))
 
@@ -331,30 +340,21 @@ def philox_normal(out, n, seed):
 def nchw_to_nhwc_noise(x, seed, musig, y, B, C, HW, ldc, dtype) -> bool:
     """nchw_to_nhwc with eps := philox stream of ``seed``; False if the shape is not supported (caller materialises the stream)."""
     rc = _lib.load().c2w_nchw_to_nhwc_noise(_p(x), int(seed), _p(musig), _p(y), B, C, HW, ldc, dtype, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_nchw_to_nhwc_noise")
-    return True
+    return _accepted(rc, "c2w_nchw_to_nhwc_noise")
 
 
 def nchw_to_nhwc_noise_rows(x, img_off, seed, musig, y, erows, B, C, HW, ldc, lde, dtype) -> bool:
     """nchw_to_nhwc_noise (``img_off`` None) / windows_to_nhwc_noise that also writes the noise it mixed in, rounded to half precision,
     as NHWC rows ``erows`` [B*HW][lde] float16 -- and mixes THAT rounded noise (include/c2w_hip.h).  False: shape not supported."""
     rc = _lib.load().c2w_nchw_to_nhwc_noise_rows(_p(x), _p(img_off), int(seed), _p(musig), _p(y), _p(erows), B, C, HW, ldc, lde, dtype, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_nchw_to_nhwc_noise_rows")
-    return True
+    return _accepted(rc, "c2w_nchw_to_nhwc_noise_rows")
 
 
 def windows_to_nhwc_noise(data, img_off, seed, musig, y, B, C, HW, ldc, dtype) -> bool:
     """nchw_to_nhwc_noise reading image b from ``data`` at float offset ``img_off[b]`` (int64 device tensor): the training batch is
     never gathered.  False if the shape is not supported (caller gathers and takes the dense path)."""
     rc = _lib.load().c2w_windows_to_nhwc_noise(_p(data), _p(img_off), int(seed), _p(musig), _p(y), B, C, HW, ldc, dtype, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_windows_to_nhwc_noise")
-    return True
+    return _accepted(rc, "c2w_windows_to_nhwc_noise")
 
 
 def mse_loss_grad_noise(y, seed, dy, loss_sum, B, C, HW, ldc, gscale, dtype, scaler=None, det: Optional[torch.Tensor] = None) -> bool:
@@ -363,10 +363,7 @@ def mse_loss_grad_noise(y, seed, dy, loss_sum, B, C, HW, ldc, gscale, dtype, sca
                                                      _nbytes(det), dtype, _stream())
     else:
         rc = _lib.load().c2w_mse_loss_grad_noise(_p(y), int(seed), _p(dy), _p(loss_sum), B, C, HW, ldc, gscale, _p(scaler), dtype, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_mse_loss_grad_noise")
-    return True
+    return _accepted(rc, "c2w_mse_loss_grad_noise")
 
 
 def sq_err(y, eps, out, loss_sum, B, C, HW, ldc, dtype, det: Optional[torch.Tensor] = None) -> bool:
@@ -381,10 +378,7 @@ def sq_err(y, eps, out, loss_sum, B, C, HW, ldc, dtype, det: Optional[torch.Tens
         rc = _lib.load().c2w_sq_err_noise(_p(y), int(eps), _p(out), _p(loss_sum), B, C, HW, ldc, dtype, _stream())
     else:
         rc = _lib.load().c2w_sq_err(_p(y), _p(eps), _p(out), _p(loss_sum), B, C, HW, ldc, dtype, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_sq_err")
-    return True
+    return _accepted(rc, "c2w_sq_err")
 
 
 def sq_err_levels_scratch_bytes(B, C, HW) -> int:
@@ -402,12 +396,9 @@ def sq_err_levels(y, eps, t, table, count, per_image, B, C, HW, ldc, K, scratch,
     if isinstance(eps, int):
         rc = _lib.load().c2w_sq_err_levels_noise(_p(y), int(eps), _p(t), _p(table), _p(count), _p(per_image), B, C, HW, ldc, K, _p(scratch),
                                                  _nbytes(scratch), dtype, _stream())
-        if rc == -3:
-            return False
-    else:
-        rc = _lib.load().c2w_sq_err_levels(_p(y), _p(eps), _p(t), _p(table), _p(count), _p(per_image), B, C, HW, ldc, K, _p(scratch),
-                                           _nbytes(scratch), dtype, _stream())
-    check(rc, "c2w_sq_err_levels")
+        return _accepted(rc, "c2w_sq_err_levels")
+    check(_lib.load().c2w_sq_err_levels(_p(y), _p(eps), _p(t), _p(table), _p(count), _p(per_image), B, C, HW, ldc, K, _p(scratch),
+                                        _nbytes(scratch), dtype, _stream()), "c2w_sq_err_levels")
     return True
 
 
@@ -420,10 +411,7 @@ def rapsd(x, spec, n_fields, H, W) -> bool:
     (include/c2w_hip.h::c2w_rapsd: the definition, the fixed summation order).  False if the shape is not supported -- nothing is
     written and the caller takes the general definition (spectra.rapsd)."""
     rc = _lib.load().c2w_rapsd(_p(x), _p(spec), n_fields, H, W, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_rapsd")
-    return True
+    return _accepted(rc, "c2w_rapsd")
 
 
 def ssim_supported(H: int, W: int, win: int) -> bool:
@@ -436,10 +424,7 @@ def ssim(x, y, data_range, out, n_pairs, n_truth, H, W, win) -> bool:
     (include/c2w_hip.h::c2w_ssim: the definition, the pivot, the fixed summation order).  False if the shape or the window is not
     supported -- nothing is written and the caller takes the general definition (ssim.ssim)."""
     rc = _lib.load().c2w_ssim(_p(x), _p(y), _p(data_range), _p(out), n_pairs, n_truth, H, W, win, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_ssim")
-    return True
+    return _accepted(rc, "c2w_ssim")
 
 
 def swd_supported(d: int, P: int, T: int) -> bool:
@@ -452,20 +437,14 @@ def swd_project(x, theta, shift, scale, proj, n_rep, T, F, d, P) -> bool:
     fixed summation order).  shift, scale: device tensors of F fp32.  False if d or P is not supported -- nothing is written and the
     caller takes the general definition (wasserstein.sliced_wasserstein)."""
     rc = _lib.load().c2w_swd_project(_p(x), _p(theta), _p(shift), _p(scale), _p(proj), n_rep, T, F, d, P, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_swd_project")
-    return True
+    return _accepted(rc, "c2w_swd_project")
 
 
 def swd_project_pair(x, y, theta, shift, scale, proj_x, proj_y, n_rep, T, F, d, P) -> bool:
     """``swd_project`` of the samples x (n_rep, T, F, d) into proj_x and of the truth y (T, F, d) into proj_y (F, P, T) in one launch:
     the same bits as two calls, without a launch that fills an eighth of the chip (include/c2w_hip.h::c2w_swd_project_pair)."""
     rc = _lib.load().c2w_swd_project_pair(_p(x), _p(y), _p(theta), _p(shift), _p(scale), _p(proj_x), _p(proj_y), n_rep, T, F, d, P, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_swd_project_pair")
-    return True
+    return _accepted(rc, "c2w_swd_project_pair")
 
 
 def swd_distance(proj_x, proj_y, out, n_rep, F, P, T) -> bool:
@@ -473,10 +452,7 @@ def swd_distance(proj_x, proj_y, out, n_rep, F, P, T) -> bool:
     T contiguous; include/c2w_hip.h::c2w_swd_distance).  A NaN in either column gives NaN.  False if T is not supported -- nothing is
     written."""
     rc = _lib.load().c2w_swd_distance(_p(proj_x), _p(proj_y), _p(out), n_rep, F, P, T, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_swd_distance")
-    return True
+    return _accepted(rc, "c2w_swd_distance")
 
 
 def kde_supported(hw: int, N: int) -> bool:
@@ -495,31 +471,22 @@ def kde_eval(x, y, offsets, pivot, h, scratch, dens, n_rep, T, F, hw, N) -> bool
     (include/c2w_hip.h::c2w_kde_eval: the definition, the pivot, the fixed summation order).  scratch: a float64 device tensor of at
     least ``kde_scratch_bytes`` bytes.  False if hw or N is not supported -- nothing is written and the caller takes the general
     definition (marginals.gaussian_kde)."""
-    rc = _lib.load().c2w_kde_eval(_p(x), _p(y), _p(offsets), _p(pivot), _p(h), _p(scratch), scratch.numel() * scratch.element_size(), _p(dens),
+    rc = _lib.load().c2w_kde_eval(_p(x), _p(y), _p(offsets), _p(pivot), _p(h), _p(scratch), _nbytes(scratch), _p(dens),
                                   n_rep, T, F, hw, N, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_kde_eval")
-    return True
+    return _accepted(rc, "c2w_kde_eval")
 
 
 def kde_partial(x, y, offsets, pivot, h, scratch, n_rep, T, F, hw, N) -> bool:
     """the first launch of ``kde_eval`` alone: the chunk sums into scratch (include/c2w_hip.h::c2w_kde_partial)"""
-    rc = _lib.load().c2w_kde_partial(_p(x), _p(y), _p(offsets), _p(pivot), _p(h), _p(scratch), scratch.numel() * scratch.element_size(), n_rep, T, F,
+    rc = _lib.load().c2w_kde_partial(_p(x), _p(y), _p(offsets), _p(pivot), _p(h), _p(scratch), _nbytes(scratch), n_rep, T, F,
                                      hw, N, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_kde_partial")
-    return True
+    return _accepted(rc, "c2w_kde_partial")
 
 
 def kde_fold(scratch, h, dens, D, n, N) -> bool:
     """the second launch of ``kde_eval`` alone: dens (D, N) from the chunk sums in scratch (include/c2w_hip.h::c2w_kde_fold)"""
     rc = _lib.load().c2w_kde_fold(_p(scratch), _p(h), _p(dens), D, n, N, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_kde_fold")
-    return True
+    return _accepted(rc, "c2w_kde_fold")
 
 
 def pit_supported(hw: int, M: int) -> bool:
@@ -531,10 +498,7 @@ def pit_counts(x, y, counts, M, T, F, hw) -> bool:
     truth y (T, F, hw) (dense fp32, 16-byte aligned; include/c2w_hip.h::c2w_pit_counts).  The call zeroes counts first.  False if hw or
     M is not supported -- nothing is written."""
     rc = _lib.load().c2w_pit_counts(_p(x), _p(y), _p(counts), M, T, F, hw, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_pit_counts")
-    return True
+    return _accepted(rc, "c2w_pit_counts")
 
 
 def quantile_supported(hw: int, Q: int) -> bool:
@@ -555,11 +519,8 @@ def quantiles(x, y, q, skipna, scratch, out, stats, n_valid, n_rep, T, F, hw) ->
     the general definition (quantiles.quantile)."""
     levels = (ctypes.c_double * len(q))(*[float(v) for v in q])
     rc = _lib.load().c2w_quantiles(_p(x), _p(y), ctypes.cast(levels, ctypes.c_void_p), len(q), int(bool(skipna)), _p(scratch),
-                                   scratch.numel() * scratch.element_size(), _p(out), _p(stats), _p(n_valid), n_rep, T, F, hw, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_quantiles")
-    return True
+                                   _nbytes(scratch), _p(out), _p(stats), _p(n_valid), n_rep, T, F, hw, _stream())
+    return _accepted(rc, "c2w_quantiles")
 
 
 def crps_supported(hw: int, M: int) -> bool:
@@ -577,12 +538,8 @@ def crps_terms(x, y, sums, cells, scratch, M, T, F, hw) -> bool:
     fixed summation order); cells, if not None: (4, T, F, hw) fp32, the four terms per cell.  scratch: a float64 device tensor of at
     least ``crps_scratch_bytes`` bytes, or None where that is 0.  False if hw or M is not supported -- nothing is written and the
     caller takes the general definition (crps.ensemble_terms)."""
-    nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    rc = _lib.load().c2w_crps_terms(_p(x), _p(y), _p(sums), _p(cells), _p(scratch), nbytes, M, T, F, hw, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_crps_terms")
-    return True
+    rc = _lib.load().c2w_crps_terms(_p(x), _p(y), _p(sums), _p(cells), _p(scratch), _nbytes(scratch), M, T, F, hw, _stream())
+    return _accepted(rc, "c2w_crps_terms")
 
 
 def timestep_embedding(t, out, n, dim, max_period=10000.0):

@@ -29,14 +29,11 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
-from .ssim import _dense32
+from .ensemble_host import VariableReport, check_ensemble, datasets, scratch, variable_names
+from .ensemble_host import on_device as _on_device
 
 REFERENCE_LEVELS = (0.0, 0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 1.0)  # data/xarray_preproc.py::compute_quantiles
 SORT_CHUNK_ELEMS = 1 << 24  # values per float64 sort of the general route (128 MiB of float64 and as much of indices alive at a time)
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
 
 
 def _levels(q) -> List[float]:
@@ -94,9 +91,8 @@ def _general(x: torch.Tensor, y: Optional[torch.Tensor], q: Sequence[float], ski
 def _launch(x, y, q, skipna, out, stats, n_valid, n_rep, T, F, hw) -> bool:
     if not ops.quantile_supported(hw, len(q)):
         return False
-    nbytes = ops.quantile_scratch_bytes(int(out.shape[0]), len(q))
-    scratch = torch.empty((max(1, nbytes // 8),), dtype=torch.int64, device=x.device)
-    return ops.quantiles(x, y, q, skipna, scratch, out, stats, n_valid, n_rep, T, F, hw)
+    ws = scratch(ops.quantile_scratch_bytes(int(out.shape[0]), len(q)), x.device, torch.int64, optional=False)
+    return ops.quantiles(x, y, q, skipna, ws, out, stats, n_valid, n_rep, T, F, hw)
 
 
 def quantile(values: torch.Tensor, q, *, truth: Optional[torch.Tensor] = None, skipna: bool = True, return_stats: bool = False):
@@ -110,21 +106,11 @@ def quantile(values: torch.Tensor, q, *, truth: Optional[torch.Tensor] = None, s
     On the GPU, ``H W`` a multiple of 4 and ``Q <= 16`` take the kernels; everything else and CPU tensors take the same definition
     through a float64 sort, and give the same numbers.  A level outside ``[0, 1]`` raises ``ValueError`` before anything is launched."""
     q = _levels(q)
-    if values.dim() < 4:
-        raise ValueError(f"values {tuple(values.shape)} must be (..., T, F, H, W)")
-    if truth is not None and tuple(truth.shape) != tuple(values.shape[-4:]):
-        raise ValueError(f"truth {tuple(truth.shape)} must be {tuple(values.shape[-4:])} = (T, F, H, W) of the values")
-    lead = tuple(values.shape[:-4])
-    T, F, H, W = (int(s) for s in values.shape[-4:])
-    hw, Q = H * W, len(q)
+    x, y, lead = datasets(values, truth)
+    n_rep, T, F, hw = (int(s) for s in x.shape)
+    Q = len(q)
     if T * hw < 1 or F < 1:
         raise ValueError("an empty data set has no quantile")
-    x = _dense32(values)
-    y = None if truth is None else _dense32(truth).view(T, F, hw)
-    n_rep = 1
-    for s in lead:
-        n_rep *= int(s)
-    x = x.view(n_rep, T, F, hw)
     D = n_rep * F + (F if y is not None else 0)
     out = torch.empty((D, Q), dtype=torch.float64, device=x.device)
     stats = torch.empty((D, Q, 2), dtype=torch.float32, device=x.device)
@@ -139,18 +125,13 @@ def quantile(values: torch.Tensor, q, *, truth: Optional[torch.Tensor] = None, s
     return first if truth is None else (first, second)
 
 
-class QuantileReport:
+class QuantileReport(VariableReport):
     """Per variable the tails of an ensemble against the truth, as device tensors: ``truth (Q,)`` the truth's quantiles, ``samples
     (M, Q)`` every member's and ``diff (M, Q)`` = ``samples - truth``, all float64; ``levels`` the Q levels."""
 
     def __init__(self, names: Sequence[str], levels: Sequence[float], variables: List[dict]):
-        self.names, self.levels, self.variables = list(names), tuple(levels), variables
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
+        super().__init__(names, variables)
+        self.levels = tuple(levels)
 
     def as_dict(self, prefix: str = "quantiles") -> dict:
         """flat ``{name: float}`` for a logger (one device-to-host copy): per variable and level ``q<level>/truth``, ``/mean`` (the
@@ -173,12 +154,9 @@ def quantile_report(samples: torch.Tensor, truth: torch.Tensor, q=REFERENCE_LEVE
     """The quantiles of every member of an ensemble ``samples (M, L, F, H, W)`` and of the ``truth (L, F, H, W)`` per variable -- by
     default at the reference's nine levels, 1 % and 99 % among them -- from one launch sequence.  The fields are expected
     DE-NORMALISED.  ``names``: one per variable, default ``var0 ...``."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape) or int(samples.shape[0]) < 1:
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M >= 1,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    check_ensemble(samples, truth, time="L", members="M >= 1")
     F = int(truth.shape[1])
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     levels = _levels(q)
     qs, qt = quantile(samples, levels, truth=truth)  # (M, F, Q), (F, Q)
     variables = [dict(truth=qt[f], samples=qs[:, f], diff=qs[:, f] - qt[f][None]) for f in range(F)]

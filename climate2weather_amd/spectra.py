@@ -26,12 +26,14 @@ exp/metrics.py is in ``climate2weather_amd.ssim``, its sliced-Wasserstein score 
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import ops
+from .ensemble_host import VariableReport, check_ensemble, dense32, member_mean_std, variable_names
+from .ensemble_host import on_device as _on_device
 
 FFT_CHUNK_ELEMS = 1 << 23  # complex values per fallback chunk (64 MiB of complex64)
 _TABLES: Dict[tuple, torch.Tensor] = {}
@@ -61,10 +63,6 @@ def frequencies(H: int, W: int, d: float = 1.0) -> np.ndarray:
 def wavelengths(H: int, W: int, d: float = 1.0) -> np.ndarray:
     with np.errstate(divide="ignore"):
         return 1.0 / frequencies(H, W, d)
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
 
 
 def _bin_table(H: int, W: int, device) -> torch.Tensor:
@@ -107,12 +105,7 @@ def rapsd(fields: torch.Tensor, normalize: bool = True, d: float = 1.0, return_f
         raise ValueError("rapsd needs (..., H, W)")
     H, W = int(fields.shape[-2]), int(fields.shape[-1])
     lead, R = tuple(fields.shape[:-2]), num_bins(H, W)
-    x = fields
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        x = torch.empty(fields.shape, dtype=torch.float32, device=fields.device).copy_(fields)  # the one copy: dense and fp32 at once
-    if x.data_ptr() % 16 != 0:
-        x = x.clone()
-    x = x.view(-1, H, W)
+    x = dense32(fields).view(-1, H, W)
     n = x.shape[0]
     spec = torch.empty((n, R), dtype=torch.float32, device=x.device)
     if n > 0 and not (_on_device(x) and ops.rapsd(x, spec, n, H, W)):
@@ -147,31 +140,16 @@ def melr(sample_spec: torch.Tensor, truth_spec: torch.Tensor, mode: str = "mean"
 MELR_MODES = ("mean", "weighted", "max")
 
 
-class SpectralReport:
+class SpectralReport(VariableReport):
     """Per variable, the dictionary the reference's ``rapsd()`` saves (exp/metrics.py:104-110) as device tensors --
     ``wavelengths (R,)``, ``obs_wavelengths``, ``sample_rapsd_over_time (M, T, R)``, ``gt_rapsd_over_time (T, R)``,
     ``obs_rapsd_over_time (T, R_obs)`` (the two ``obs_*`` entries are None without observations) -- plus ``melr``: ``{mode: (M,)}``."""
 
-    def __init__(self, names: Sequence[str], variables: List[dict]):
-        self.names, self.variables = list(names), variables
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
-
     def as_dict(self, prefix: str = "spectra") -> dict:
         """flat ``{name: float}`` for a logger (one device-to-host copy): per variable and mode the mean and the standard deviation of
         MELR over the members, as the reference prints them (exp/metrics.py:291: numpy's population std)"""
-        stack = torch.stack([v["melr"][m] for v in self.variables for m in MELR_MODES]).cpu().numpy()
-        out, i = {}, 0
-        for name in self.names:
-            for m in MELR_MODES:
-                out[f"{prefix}/{name}/melr_{m}"] = float(stack[i].mean())
-                out[f"{prefix}/{name}/melr_{m}_std"] = float(stack[i].std())
-                i += 1
-        return out
+        return member_mean_std([v["melr"][m] for v in self.variables for m in MELR_MODES],
+                               [f"{prefix}/{name}/melr_{m}" for name in self.names for m in MELR_MODES])
 
 
 def spectral_report(samples: torch.Tensor, truth: torch.Tensor, obs: Optional[torch.Tensor] = None, *, t_step: int = 1,
@@ -181,12 +159,9 @@ def spectral_report(samples: torch.Tensor, truth: torch.Tensor, obs: Optional[to
     restricts its scores to the observation times (exp/metrics.py:239-240).  ``obs (T, F, h, w)``, one field per kept frame, gets its own
     spectra at the spacing ``d * s_step`` (``s_step`` defaults to ``H // h``; the reference's is 16).  The fields are expected
     DE-NORMALISED, as the reference's are (``QuantileNormalizer.unnormalize`` first).  ``names``: one per variable, default ``var0 ...``."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    check_ensemble(samples, truth, time="L")
     M, L, F, H, W = samples.shape
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     t_step = int(t_step)
     if t_step < 1:
         raise ValueError("t_step >= 1")

@@ -35,26 +35,15 @@ exp/metrics.py is in ``climate2weather_amd.wasserstein``.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
 from . import ops
+from .ensemble_host import VariableReport, check_ensemble, dense32, member_mean_std, variable_names
+from .ensemble_host import on_device as _on_device
 
 POOL_CHUNK_ELEMS = 1 << 21  # values of one field stack per general-route chunk (16 MiB of float64, about ten such stacks alive)
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
-
-
-def _dense32(t: torch.Tensor) -> torch.Tensor:
-    x = t
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        x = torch.empty(t.shape, dtype=torch.float32, device=t.device).copy_(t)  # the one copy: dense and fp32 at once
-    if x.data_ptr() % 16 != 0:
-        x = x.clone()
-    return x
 
 
 def global_range(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -116,7 +105,7 @@ def ssim(samples: torch.Tensor, truth: torch.Tensor, *, data_range=None, win_siz
     if win != win_size or win < 3 or win % 2 == 0 or win > min(H, W):
         raise ValueError(f"win_size {win_size!r}: an odd number from 3 to min(H, W) = {min(H, W)}")
     lead, tlead = tuple(samples.shape[:-2]), tuple(truth.shape[:-2])
-    x, y = _dense32(samples), _dense32(truth)
+    x, y = dense32(samples), dense32(truth)
     out = torch.empty(lead, dtype=torch.float64, device=x.device)
     n, nt = out.numel(), 1
     for d in tlead:
@@ -136,28 +125,14 @@ def ssim(samples: torch.Tensor, truth: torch.Tensor, *, data_range=None, win_siz
     return out
 
 
-class SsimReport:
+class SsimReport(VariableReport):
     """Per variable, what the reference's ``ssim()`` computes (exp/metrics.py:198-212) as device tensors: ``ssim_over_time (M, T)``,
     its ``ssim_values``, and ``ssim (M,)``, their mean over time, which is what it returns; plus ``data_range`` (0-dim), the range used."""
-
-    def __init__(self, names: Sequence[str], variables: List[dict]):
-        self.names, self.variables = list(names), variables
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
 
     def as_dict(self, prefix: str = "ssim") -> dict:
         """flat ``{name: float}`` for a logger (one device-to-host copy): per variable the mean and the standard deviation of the score
         over the members, as the reference prints them (exp/metrics.py:291: numpy's population std)"""
-        stack = torch.stack([v["ssim"] for v in self.variables]).cpu().numpy()
-        out = {}
-        for i, name in enumerate(self.names):
-            out[f"{prefix}/{name}/ssim"] = float(stack[i].mean())
-            out[f"{prefix}/{name}/ssim_std"] = float(stack[i].std())
-        return out
+        return member_mean_std([v["ssim"] for v in self.variables], [f"{prefix}/{name}/ssim" for name in self.names])
 
 
 def ssim_report(samples: torch.Tensor, truth: torch.Tensor, *, t_step: int = 1, win_size: int = 15,
@@ -167,16 +142,13 @@ def ssim_report(samples: torch.Tensor, truth: torch.Tensor, *, t_step: int = 1, 
     restricts its scores to the observation times (exp/metrics.py:239-240) -- before the range is taken, as there.  The fields are
     expected DE-NORMALISED, as the reference's are (``QuantileNormalizer.unnormalize`` first): the range and the two constants are in
     the variable's own units.  ``names``: one per variable, default ``var0 ...``."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    check_ensemble(samples, truth, time="L")
     F = int(truth.shape[1])
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     t_step = int(t_step)
     if t_step < 1:
         raise ValueError("t_step >= 1")
-    s, g = _dense32(samples[:, ::t_step]), _dense32(truth[::t_step])
+    s, g = dense32(samples[:, ::t_step]), dense32(truth[::t_step])
     rng = global_range(s, g)                                   # (T, F), the same along T
     over_time = ssim(s, g, data_range=rng, win_size=win_size)  # (M, T, F)
     mean = over_time.mean(dim=1)                               # (M, F)

@@ -36,21 +36,17 @@ is never taken), more than 128 projections on the kernel (the general route take
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+import math
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
-from .ssim import _dense32
-
-MOMENT_CHUNK_ELEMS = 1 << 22  # values per chunk of the float64 passes (32 MiB of float64 alive at a time)
+from .ensemble_host import VariableReport, check_ensemble, chunk_step, dense32, member_mean_std, variable_names
+from .ensemble_host import on_device as _on_device
 
 _THETA = {}
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
 
 
 def projections(d: int, n_projections: int = 100, seed: int = 0, device=None) -> torch.Tensor:
@@ -77,7 +73,7 @@ def truth_moments(truth: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     T, F = int(truth.shape[0]), int(truth.shape[1])
     HW = int(truth.shape[2]) * int(truth.shape[3])
     n = T * HW
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, F * HW))
+    step = chunk_step(F * HW)
     mean = truth.sum(dim=(0, 2, 3), dtype=torch.float64) / n
     ss = torch.zeros(F, dtype=torch.float64, device=truth.device)
     for i in range(0, T, step):
@@ -134,13 +130,13 @@ def sliced_wasserstein(samples: torch.Tensor, truth: torch.Tensor, *, n_projecti
     T, F, H, W = (int(s) for s in truth.shape)
     d = H * W
     lead = tuple(samples.shape[:-4])
-    x, y = _dense32(samples), _dense32(truth)
+    x, y = dense32(samples), dense32(truth)
     if theta is None:
         theta = projections(d, n_projections, seed, x.device)
     else:
         if theta.dim() != 2 or int(theta.shape[1]) != d:
             raise ValueError(f"theta {tuple(theta.shape)} must be (P, {d})")
-        theta = _dense32(theta.to(x.device))
+        theta = dense32(theta.to(x.device))
     P = int(theta.shape[0])
     if (shift is None) != (scale is None):
         raise ValueError("shift and scale: both or neither")
@@ -148,9 +144,7 @@ def sliced_wasserstein(samples: torch.Tensor, truth: torch.Tensor, *, n_projecti
         shift, scale = truth_moments(y)
     else:
         shift, scale = _per_variable(shift, F, x.device, "shift"), _per_variable(scale, F, x.device, "scale")
-    n_rep = 1
-    for s in lead:
-        n_rep *= int(s)
+    n_rep = math.prod(lead)
     out = torch.empty((n_rep, F, P), dtype=torch.float64, device=x.device)
     if n_rep > 0 and T > 0 and F > 0:
         x, y = x.view(n_rep, T, F, d), y.view(T, F, d)
@@ -160,28 +154,14 @@ def sliced_wasserstein(samples: torch.Tensor, truth: torch.Tensor, *, n_projecti
     return out if per_projection else torch.sqrt(out.mean(dim=-1))
 
 
-class WassersteinReport:
+class WassersteinReport(VariableReport):
     """Per variable, what the reference's ``compute_wasserstein_nd`` returns after the normalisation of ``run`` (exp/metrics.py:254-264)
     as device tensors: ``wasserstein (M,)``; plus ``shift`` and ``scale`` (0-dim), the truth's mean and 1 / std that were applied."""
-
-    def __init__(self, names: Sequence[str], variables: List[dict]):
-        self.names, self.variables = list(names), variables
-
-    def __getitem__(self, name: str) -> dict:
-        return self.variables[self.names.index(name)]
-
-    def __iter__(self):
-        return iter(zip(self.names, self.variables))
 
     def as_dict(self, prefix: str = "wasserstein") -> dict:
         """flat ``{name: float}`` for a logger (one device-to-host copy): per variable the mean and the standard deviation of the
         distance over the members, as the reference prints them (exp/metrics.py:291: numpy's population std)"""
-        stack = torch.stack([v["wasserstein"] for v in self.variables]).cpu().numpy()
-        out = {}
-        for i, name in enumerate(self.names):
-            out[f"{prefix}/{name}/wasserstein"] = float(stack[i].mean())
-            out[f"{prefix}/{name}/wasserstein_std"] = float(stack[i].std())
-        return out
+        return member_mean_std([v["wasserstein"] for v in self.variables], [f"{prefix}/{name}/wasserstein" for name in self.names])
 
 
 def swd_report(samples: torch.Tensor, truth: torch.Tensor, *, t_step: int = 1, n_projections: int = 100, seed: int = 0,
@@ -191,16 +171,13 @@ def swd_report(samples: torch.Tensor, truth: torch.Tensor, *, t_step: int = 1, n
     t_step-th frame of both, as the reference restricts its scores to the observation times (exp/metrics.py:239-240) -- before the
     moments are taken, as there.  The fields are expected DE-NORMALISED, as the reference's are.  ``names``: one per variable, default
     ``var0 ...``."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    check_ensemble(samples, truth, time="L")
     F = int(truth.shape[1])
-    names = [f"var{f}" for f in range(F)] if names is None else list(names)
-    if len(names) != F:
-        raise ValueError(f"{len(names)} names for {F} variables")
+    names = variable_names(names, F)
     t_step = int(t_step)
     if t_step < 1:
         raise ValueError("t_step >= 1")
-    s, g = _dense32(samples[:, ::t_step]), _dense32(truth[::t_step])
+    s, g = dense32(samples[:, ::t_step]), dense32(truth[::t_step])
     shift, scale = truth_moments(g)
     w = sliced_wasserstein(s, g, n_projections=n_projections, seed=seed, shift=shift, scale=scale)  # (M, F)
     return WassersteinReport(names, [dict(wasserstein=w[:, f], shift=shift[f], scale=scale[f]) for f in range(F)])

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .ops import _p, _stream
+from .ops import _accepted, _nbytes, _p, _stream
 
 
 def wind_supported(hw: int, K: int) -> bool:
@@ -48,9 +48,6 @@ def wind_power(fields, F, u_index, v_index, table, K, hub, sums, derived, scratc
     summation order); table: the device copy of ``wind_table``'s bytes; derived, if not None: (planes, 2, hw) fp32, speed and power per
     cell.  scratch: a float64 device tensor of at least ``wind_scratch_bytes`` bytes, or None where that is 0.  False if hw or K is not
     supported -- nothing is written and the caller takes the general definition (windpower.wind_fields)."""
-    nbytes = 0 if scratch is None else scratch.numel() * scratch.element_size()
-    rc = _lib.load().c2w_wind_power(_p(fields), F, u_index, v_index, _p(table), K, hub, _p(sums), _p(derived), _p(scratch), nbytes, planes, hw, _stream())
-    if rc == -3:
-        return False
-    check(rc, "c2w_wind_power")
-    return True
+    rc = _lib.load().c2w_wind_power(_p(fields), F, u_index, v_index, _p(table), K, hub, _p(sums), _p(derived), _p(scratch), _nbytes(scratch), planes, hw,
+                                    _stream())
+    return _accepted(rc, "c2w_wind_power")

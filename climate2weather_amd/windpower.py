@@ -39,12 +39,8 @@ import numpy as np
 import torch
 
 from . import marginals, wind_ops
-from .ssim import _dense32
-from .wasserstein import MOMENT_CHUNK_ELEMS
-
-
-def _on_device(x: torch.Tensor) -> bool:
-    return x.is_cuda
+from .ensemble_host import check_ensemble, chunk_step, dense32, scratch
+from .ensemble_host import on_device as _on_device
 
 
 def hub_factor(hub_height: float = 100.0, reference_height: float = 10.0, alpha: float = 1.0 / 7.0) -> float:
@@ -116,7 +112,7 @@ def _general(x: torch.Tensor, curve: PowerCurve, u: int, v: int, c: float, deriv
     """The definition for any shape, any curve and any device, float64 end to end: x (P, F, hw), derived (P, 2, hw) or None, sums
     (P, 2)."""
     P, F, hw = x.shape
-    step = max(1, MOMENT_CHUNK_ELEMS // max(1, hw))
+    step = chunk_step(hw)
     for i in range(0, P, step):
         uu, vv = x[i:i + step, u].double(), x[i:i + step, v].double()
         speed = torch.sqrt(uu * uu + vv * vv) * c
@@ -132,9 +128,8 @@ def _launch(x, F, u, v, curve, c, sums, derived, planes, hw) -> bool:
     table = curve.device_table(x.device)
     if table is None:
         return False
-    nbytes = wind_ops.wind_scratch_bytes(planes, hw)
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device) if nbytes else None
-    return wind_ops.wind_power(x, F, u, v, table, curve.K, c, sums, derived, scratch, planes, hw)
+    ws = scratch(wind_ops.wind_scratch_bytes(planes, hw), x.device)
+    return wind_ops.wind_power(x, F, u, v, table, curve.K, c, sums, derived, ws, planes, hw)
 
 
 def _check(values: torch.Tensor, curve: PowerCurve, u: int, v: int) -> None:
@@ -166,7 +161,7 @@ def wind_fields(values: torch.Tensor, curve: PowerCurve, *, u: int, v: int, hub_
     F, H, W = (int(s) for s in values.shape[-3:])
     hw = H * W
     planes = int(np.prod(lead, dtype=np.int64)) if lead else 1
-    x = _dense32(values).view(planes, F, hw)
+    x = dense32(values).view(planes, F, hw)
     sums = torch.empty((planes, 2), dtype=torch.float64, device=x.device)
     derived = torch.empty((planes, 2, hw), dtype=torch.float32, device=x.device) if maps else None
     if planes * hw == 0:
@@ -252,8 +247,7 @@ def wind_report(samples: torch.Tensor, truth: torch.Tensor, curve: PowerCurve, *
     ``single_location`` does: the cell is sliced first, the observation at both indices divided by ``H // h`` (:1204-1208), and the
     per-cell entries lose their two cell dimensions.  The densities come from ``marginals.gaussian_kde``: members and truth in one call,
     the observation in its own."""
-    if samples.dim() != 5 or truth.dim() != 4 or tuple(samples.shape[1:]) != tuple(truth.shape):
-        raise ValueError(f"samples {tuple(samples.shape)} must be (M,) + truth {tuple(truth.shape)} = (L, F, H, W)")
+    check_ensemble(samples, truth, time="L")
     F = int(truth.shape[1])
     if observation is not None and (observation.dim() != 4 or int(observation.shape[1]) != F):
         raise ValueError(f"observation {tuple(observation.shape)} must be (L', F = {F}, h, w)")

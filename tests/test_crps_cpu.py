@@ -5,17 +5,16 @@ rule's negative control (a straight fp32 port fails it), the report, the argumen
 compiled for the host (csrc/crps_core.h) under the address and undefined-behaviour sanitizers, and the C declarations against the
 ctypes prototypes."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_crps_ops
 import fp64_crps_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import crps as C
 from climate2weather_amd import ops as c2w_ops
 
@@ -271,24 +270,11 @@ def test_unsupported_shapes_take_the_general_route(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels' maps
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_crps(tmp_path_factory):
     """a stand-alone program under the address and undefined-behaviour sanitizers; it is run directly, never loaded into Python.
     -ffp-contract=off: the kernel fuses no multiply with an add either (crps_core.h says so to its own compiler)."""
-    exe = tmp_path_factory.mktemp("host_crps") / "host_crps"
-    subprocess.run(_cxx() + ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", "host_crps_main.cpp"), "-o", str(exe)],
-                   check=True, timeout=600)
-    return exe
+    return host_program.build(tmp_path_factory, "crps", sanitize=True, fp_contract_off=True, timeout=600)
 
 
 @pytest.mark.parametrize("M,T,F,hw", [(1, 2, 2, 4), (8, 3, 2, 100), (9, 2, 2, 1028), (16, 1, 3, 4100), (17, 2, 1, 520), (32, 1, 2, 4100), (33, 2, 1, 260),
@@ -342,25 +328,5 @@ def test_support_predicate_and_chunking_agree():
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_ulonglong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong, "unsigned long long": c_ulonglong}[arg.rsplit(" ", 1)[0]]
-
     names = {"c2w_crps_supported": "int", "c2w_crps_scratch_bytes": "long long", "c2w_crps_terms": "int"}
-    for name, ret in names.items():
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == ret
-        assert (ret == "long long") == name.endswith("_bytes")  # what _lib.load() derives the return type from
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert set(names) <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "crps.hip" in c2w_build.SOURCES
-    for fn in ("crps_supported", "crps_scratch_bytes", "crps_terms"):
-        assert callable(getattr(c2w_ops, fn))
+    c_abi.assert_declared(names, "crps.hip", c2w_ops, ("crps_supported", "crps_scratch_bytes", "crps_terms"))

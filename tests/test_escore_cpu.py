@@ -5,18 +5,17 @@ for the HIP kernels -- against the float64 definitions by the rules of tests/fp6
 fp32 Gram form fails it), the report, the argument checks, the kernels' own index maps and arithmetic compiled for the host
 (csrc/escore_core.h) under the address and undefined-behaviour sanitizers, and the C declarations against the ctypes prototypes."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_escore_ops
 import fp64_crps_ref as CR
 import fp64_escore_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import crps as C
 from climate2weather_amd import escore_ops
 from climate2weather_amd import multivariate as MV
@@ -379,24 +378,11 @@ def test_unsupported_shapes_take_the_general_route(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels' maps
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_escore(tmp_path_factory):
     """a stand-alone program under the address and undefined-behaviour sanitizers; it is run directly, never loaded into Python.
     -ffp-contract=off: the kernels fuse no multiply with an add either (escore_core.h says so to its own compiler)."""
-    exe = tmp_path_factory.mktemp("host_escore") / "host_escore"
-    subprocess.run(_cxx() + ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", "host_escore_main.cpp"), "-o", str(exe)],
-                   check=True, timeout=600)
-    return exe
+    return host_program.build(tmp_path_factory, "escore", sanitize=True, fp_contract_off=True, timeout=600)
 
 
 @pytest.mark.parametrize("M,planes,hw", [(1, 2, 4), (2, 3, 64), (3, 2, 260), (7, 4, 192), (8, 2, 1028), (16, 2, 516), (33, 1, 260), (64, 2, 4100)])
@@ -469,26 +455,6 @@ def test_support_predicates_and_maps_agree():
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_ulonglong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong, "unsigned long long": c_ulonglong}[arg.rsplit(" ", 1)[0]]
-
     names = {"c2w_escore_supported": "int", "c2w_escore_scratch_bytes": "long long", "c2w_escore_pairs": "int",
              "c2w_vario_supported": "int", "c2w_vario_scratch_bytes": "long long", "c2w_vario_terms": "int"}
-    for name, ret in names.items():
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == ret
-        assert (ret == "long long") == name.endswith("_bytes")  # what _lib.load() derives the return type from
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert set(names) <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "escore.hip" in c2w_build.SOURCES
-    for fn in ("escore_supported", "escore_scratch_bytes", "escore_pairs", "vario_supported", "vario_scratch_bytes", "vario_terms"):
-        assert callable(getattr(escore_ops, fn))
+    c_abi.assert_declared(names, "escore.hip", escore_ops, ("escore_supported", "escore_scratch_bytes", "escore_pairs", "vario_supported", "vario_scratch_bytes", "vario_terms"))

@@ -5,17 +5,16 @@ reference's figure code, the exact cases of the rank histogram, the rule's negat
 maps and arithmetic compiled for the host (csrc/kde_core.h) under the address and undefined-behaviour sanitizers, and the C declarations
 against the ctypes prototypes."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_kde_ops
 import fp64_kde_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import marginals as Mg
 from climate2weather_amd import ops as c2w_ops
 
@@ -317,23 +316,10 @@ def test_the_kernel_s_arithmetic_passes_where_the_straight_port_fails(monkeypatc
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels' maps
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_kde(tmp_path_factory):
     """a stand-alone program under the address and undefined-behaviour sanitizers; it is run directly, never loaded into Python"""
-    exe = tmp_path_factory.mktemp("host_kde") / "host_kde"
-    subprocess.run(_cxx() + ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", "host_kde_main.cpp"), "-o", str(exe)],
-                   check=True, timeout=300)
-    return exe
+    return host_program.build(tmp_path_factory, "kde", sanitize=True, timeout=300)
 
 
 @pytest.mark.parametrize("n_rep,T,F,hw,N", [(2, 3, 2, 100, 1000), (1, 13, 1, 256, 300), (3, 1, 4, 4, 1), (1, 7, 3, 36, 1024)])
@@ -404,24 +390,6 @@ def test_support_predicates_and_chunking_agree():
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_ulonglong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong, "unsigned long long": c_ulonglong}[arg.rsplit(" ", 1)[0]]
-
     names = {"c2w_kde_supported": "int", "c2w_kde_scratch_bytes": "long long", "c2w_kde_eval": "int", "c2w_kde_partial": "int", "c2w_kde_fold": "int", "c2w_pit_supported": "int",
              "c2w_pit_counts": "int"}
-    for name, ret in names.items():
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == ret
-        assert (ret == "long long") == name.endswith("_bytes")  # what _lib.load() derives the return type from
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert set(names) <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "kde.hip" in c2w_build.SOURCES
+    c_abi.assert_declared(names, "kde.hip")

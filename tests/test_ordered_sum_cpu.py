@@ -2,13 +2,13 @@
 address and undefined-behaviour sanitizers, its phases run one thread after the other by tests/host_ordered_sum_main.cpp, against
 tests/emu_ordered_sum.py bit for bit -- the LDS layout, the order of the additions, the sum over the parts and the two write policies."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import emu_ordered_sum as E
+import host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POLICIES = {"nan_if_nan": (0, E.nan_if_nan), "nan_if_not_finite": (1, E.nan_if_not_finite)}
@@ -17,23 +17,10 @@ ODD_NAN_BITS = 0xfff4000000c0ffee
 ODD_NAN = np.array([ODD_NAN_BITS], np.uint64).view(np.float64)[0]  # the sign bit set, a payload, the quiet bit clear
 
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     """a stand-alone program under the address and undefined-behaviour sanitizers; it is run directly, never loaded into Python"""
-    exe = tmp_path_factory.mktemp("host_ordered_sum") / "host_ordered_sum"
-    subprocess.run(_cxx() + ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", "host_ordered_sum_main.cpp"), "-o", str(exe)],
-                   check=True, timeout=600)
-    return exe
+    return host_program.build(tmp_path_factory, "ordered_sum", sanitize=True, fp_contract_off=True, timeout=600)
 
 
 def _bits(a):

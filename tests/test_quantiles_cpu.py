@@ -5,8 +5,6 @@ the data against one built from numpy's values, the report, the argument checks,
 host (csrc/quantile_core.h) under the address and undefined-behaviour sanitizers, and the C declarations against the ctypes prototypes.
 Everything is exact: no tolerance appears."""
 import os
-import re
-import shutil
 import subprocess
 import warnings
 
@@ -14,9 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_quantile_ops
 import fp64_quantile_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import normalize as Nm
 from climate2weather_amd import ops as c2w_ops
 from climate2weather_amd import quantiles as Qt
@@ -235,23 +234,10 @@ def test_support_predicates_and_constants_agree():
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels' maps
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_quantile(tmp_path_factory):
     """a stand-alone program under the address and undefined-behaviour sanitizers; it is run directly, never loaded into Python"""
-    exe = tmp_path_factory.mktemp("host_quantile") / "host_quantile"
-    subprocess.run(_cxx() + ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", "host_quantile_main.cpp"), "-o", str(exe)],
-                   check=True, timeout=300)
-    return exe
+    return host_program.build(tmp_path_factory, "quantile", sanitize=True, timeout=300)
 
 
 @pytest.mark.parametrize("n_rep,T,F,hw,slabs", [(2, 6, 2, 100, 6), (1, 13, 1, 256, 4), (3, 7, 4, 4, 3), (1, 5, 3, 4100, 2), (2, 10, 1, 8, 7)])
@@ -287,25 +273,5 @@ def test_select_phases_on_the_host_match_the_reference(host_quantile, tmp_path, 
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_ulonglong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong, "unsigned long long": c_ulonglong}[arg.rsplit(" ", 1)[0]]
-
     names = {"c2w_quantile_supported": "int", "c2w_quantile_scratch_bytes": "long long", "c2w_quantiles": "int"}
-    for name, ret in names.items():
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == ret
-        assert (ret == "long long") == name.endswith("_bytes")  # what _lib.load() derives the return type from
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert set(names) <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "quantile.hip" in c2w_build.SOURCES
-    for fn in ("quantile_supported", "quantile_scratch_bytes", "quantiles"):
-        assert callable(getattr(c2w_ops, fn))
+    c_abi.assert_declared(names, "quantile.hip", c2w_ops, ("quantile_supported", "quantile_scratch_bytes", "quantiles"))

@@ -3,22 +3,19 @@ spectra.rapsd -- the general torch.fft one and the launcher's, with tests/emu_sp
 table, the half-spectrum shortcut against the cell-by-cell definition, MELR against a line-by-line restatement of the reference, the
 report's layout, the kernel's own arithmetic compiled for the host (csrc/spectrum_core.h), and the C declarations against the ctypes
 prototypes."""
-import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_spectrum_ops
 import fp64_spectrum_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import ops as c2w_ops
 from climate2weather_amd import spectra
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_SIZES = (8, 16, 32, 64, 128)
 
 
@@ -232,21 +229,9 @@ def test_report_without_obs_and_its_argument_checks():
 
 # ------------------------------------------------------------------------------------------------------------------ the kernel's arithmetic
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_spectrum(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("host_spectrum") / "host_spectrum"
-    subprocess.run(_cxx() + ["-O1", "-std=c++17", "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"),
-                             os.path.join(ROOT, "tests", "host_spectrum_main.cpp"), "-o", str(exe)], check=True, timeout=300)
-    return exe
+    return host_program.build(tmp_path_factory, "spectrum", sanitize=False, timeout=300)
 
 
 @pytest.mark.parametrize("N", KERNEL_SIZES)
@@ -271,21 +256,5 @@ def test_kernel_phases_on_the_host_meet_the_tolerance(host_spectrum, tmp_path, N
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong}[arg.rsplit(" ", 1)[0]]
-
-    for name in ("c2w_rapsd_supported", "c2w_rapsd"):
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == "int"
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert {"c2w_rapsd_supported", "c2w_rapsd"} <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "spectrum.hip" in c2w_build.SOURCES
+    names = {"c2w_rapsd_supported": "int", "c2w_rapsd": "int"}
+    c_abi.assert_declared(names, "spectrum.hip")

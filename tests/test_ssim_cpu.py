@@ -2,22 +2,19 @@
 launcher's, with tests/emu_ssim_ops.py standing in for the HIP kernel -- against the float64 definition, the report against a
 line-by-line restatement of the reference's loop, the argument checks, the rule's negative control, the kernel's own arithmetic compiled
 for the host (csrc/ssim_core.h), and the C declarations against the ctypes prototypes."""
-import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_ssim_ops
 import fp64_ssim_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import ops as c2w_ops
 from climate2weather_amd import ssim as ssim_mod
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # Both CPU routes are float64 end to end on the fp32 numbers the reference sees.  The straight u_xx - u_x^2 loses offset^2 / variance
 # of float64's 1.1e-16 -- 1e10 / 9e4 on the pressure-like pair's noise -- times a few tens of operations: 1e-10 at the worst.
 ROUTE_TOL = 1e-9
@@ -191,21 +188,9 @@ def test_an_unpivoted_fp32_port_fails_the_rule_on_the_pressure_like_pair():
 
 # ------------------------------------------------------------------------------------------------------------------ the kernel's arithmetic
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_ssim(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("host_ssim") / "host_ssim"
-    subprocess.run(_cxx() + ["-O1", "-std=c++17", "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"),
-                             os.path.join(ROOT, "tests", "host_ssim_main.cpp"), "-o", str(exe)], check=True, timeout=300)
-    return exe
+    return host_program.build(tmp_path_factory, "ssim", sanitize=False, timeout=300)
 
 
 def _run_host(exe, tmp_path, x, y, rng, win):
@@ -249,22 +234,6 @@ def test_kernel_phases_on_the_host_pairing_and_slots(host_ssim, tmp_path):
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong}[arg.rsplit(" ", 1)[0]]
-
-    for name in ("c2w_ssim_supported", "c2w_ssim"):
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == "int"
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert {"c2w_ssim_supported", "c2w_ssim"} <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "ssim.hip" in c2w_build.SOURCES
+    names = {"c2w_ssim_supported": "int", "c2w_ssim": "int"}
+    c_abi.assert_declared(names, "ssim.hip")
 

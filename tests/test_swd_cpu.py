@@ -4,17 +4,16 @@ the rule of tests/fp64_swd_ref.py, the projection generator, the report against 
 exact cases, the rule's negative control, the argument checks, the kernels' own index maps and arithmetic compiled for the host
 (csrc/swd_core.h), and the C declarations against the ctypes prototypes."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_swd_ops
 import fp64_swd_ref as R
-from climate2weather_amd import _lib
+import host_program
 from climate2weather_amd import ops as c2w_ops
 from climate2weather_amd import wasserstein as W
 
@@ -253,21 +252,9 @@ def test_unsupported_shapes_take_the_general_route(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels' maps
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_swd(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("host_swd") / "host_swd"
-    subprocess.run(_cxx() + ["-O1", "-std=c++17", "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"),
-                             os.path.join(ROOT, "tests", "host_swd_main.cpp"), "-o", str(exe)], check=True, timeout=300)
-    return exe
+    return host_program.build(tmp_path_factory, "swd", sanitize=False, timeout=300)
 
 
 def _host_project(exe, tmp, x, th, shift, scale):
@@ -362,22 +349,5 @@ def test_support_predicates_agree():
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong}[arg.rsplit(" ", 1)[0]]
-
-    names = ("c2w_swd_supported", "c2w_swd_project", "c2w_swd_project_pair", "c2w_swd_distance")
-    for name in names:
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == "int"
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert set(names) <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "swd.hip" in c2w_build.SOURCES
+    names = {"c2w_swd_supported": "int", "c2w_swd_project": "int", "c2w_swd_project_pair": "int", "c2w_swd_distance": "int"}
+    c_abi.assert_declared(names, "swd.hip")

@@ -2,7 +2,6 @@
 tests/emu_eval_ops.py: the plan, the fp32 bin rule, the table against the oracle's unreduced loss, no side effects on training, the EMA
 copy, the two-rank all-reduce, and the C declarations against the ctypes prototypes."""
 import os
-import re
 import socket
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import c_abi
 import emu_eval_ops
 from climate2weather_amd import _lib
 from climate2weather_amd import ops as c2w_ops
@@ -253,20 +253,5 @@ def test_two_ranks_all_reduce_to_the_merge_of_their_shards(emu, tmp_path):
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_int, c_longlong, c_ulonglong, c_void_p
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        base = arg.rsplit(" ", 1)[0]
-        return {"int": c_int, "long long": c_longlong, "unsigned long long": c_ulonglong}[base]
-
-    for name, ret in (("c2w_sq_err_levels_scratch_bytes", "long long"), ("c2w_sq_err_levels", "int"), ("c2w_sq_err_levels_noise", "int")):
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == ret
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert {"c2w_sq_err_levels_scratch_bytes", "c2w_sq_err_levels", "c2w_sq_err_levels_noise"} <= set(_lib.exported_symbols())
+    names = {"c2w_sq_err_levels_scratch_bytes": "long long", "c2w_sq_err_levels": "int", "c2w_sq_err_levels_noise": "int"}
+    c_abi.assert_declared(names)

@@ -5,16 +5,16 @@ restatement of the reference's lines, the argument checks, the library's table b
 table, lookup, index maps and arithmetic compiled for the host (csrc/wind_core.h) under the address and undefined-behaviour
 sanitizers, and the C declarations against the ctypes prototypes."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import c_abi
 import emu_wind_ops
 import fp64_wind_ref as R
+import host_program
 from climate2weather_amd import _lib
 from climate2weather_amd import wind_ops
 from climate2weather_amd import windpower as W
@@ -363,24 +363,11 @@ def test_a_nan_poisons_its_own_entry_only(route):
 
 # ------------------------------------------------------------------------------------------------------------------ the table
 
-def _cxx():
-    for cand in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if cand and shutil.which(cand):
-            return [shutil.which(cand)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # what the library itself is built with; host-only C++ here
-    assert os.path.exists(hipcc), "no host C++ compiler found (c++ / g++ / clang++ / hipcc)"
-    return [hipcc, "-x", "c++"]
-
-
 @pytest.fixture(scope="module")
 def host_wind(tmp_path_factory):
     """a stand-alone program under the address and undefined-behaviour sanitizers; it is run directly, never loaded into Python.
     -ffp-contract=off: the kernel fuses no multiply with an add either (wind_core.h says so to its own compiler)."""
-    exe = tmp_path_factory.mktemp("host_wind") / "host_wind"
-    subprocess.run(_cxx() + ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             "-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", "host_wind_main.cpp"), "-o", str(exe)],
-                   check=True, timeout=600)
-    return exe
+    return host_program.build(tmp_path_factory, "wind", sanitize=True, fp_contract_off=True, timeout=600)
 
 
 BAD_CURVES = [([3.0, 3.0], [0.0, 1.0]), ([3.0, 2.0], [0.0, 1.0]), ([1.0, np.nan], [0.0, 1.0]), ([1.0, np.inf], [0.0, 1.0]), ([1.0, 2.0], [0.0, np.nan]),
@@ -487,28 +474,8 @@ def test_support_predicate_scratch_and_chunking_agree():
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 
 def test_new_entry_points_have_matching_argument_lists():
-    from ctypes import c_float, c_int, c_longlong, c_ulonglong, c_void_p
-    hdr = open(os.path.join(ROOT, "include", "c2w_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return c_void_p
-        return {"int": c_int, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float}[arg.rsplit(" ", 1)[0]]
-
     names = {"c2w_wind_supported": "int", "c2w_wind_table_bytes": "long long", "c2w_wind_table": "int", "c2w_wind_scratch_bytes": "long long",
              "c2w_wind_power": "int"}
-    for name, ret in names.items():
-        m = re.search(r"([\w ]+?)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m is not None, name
-        assert " ".join(m.group(1).split()) == ret
-        assert (ret == "long long") == name.endswith("_bytes")  # what _lib.load() derives the return type from
-        assert [ctype(a) for a in m.group(2).split(",")] == _lib._PROTOS[name], name
-    assert set(names) <= set(_lib.exported_symbols())
-    from climate2weather_amd import build as c2w_build
-    assert "wind.hip" in c2w_build.SOURCES
-    for fn in ("wind_supported", "wind_table_bytes", "wind_table", "wind_scratch_bytes", "wind_power"):
-        assert callable(getattr(wind_ops, fn))
+    c_abi.assert_declared(names, "wind.hip", wind_ops, ("wind_supported", "wind_table_bytes", "wind_table", "wind_scratch_bytes", "wind_power"))
     from climate2weather_amd import ops as c2w_ops
     assert not any(hasattr(c2w_ops, fn) for fn in ("wind_supported", "wind_power"))  # ops.py's launchers are pinned by the launch replay
