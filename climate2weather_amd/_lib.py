@@ -131,6 +131,9 @@ _PROTOS = {
     "c2w_vario_supported": [c_int, c_int, c_int, c_int, c_int],
     "c2w_vario_scratch_bytes": [c_longlong, c_int, c_int, c_int],
     "c2w_vario_terms": [c_void_p, c_void_p, c_void_p, c_void_p, c_ulonglong, c_int, c_longlong, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_tincr_supported": [c_int, c_int],
+    "c2w_tincr_scratch_bytes": [c_longlong, c_int, c_int, c_int, c_int],
+    "c2w_tincr_terms": [c_void_p, c_void_p, c_void_p, c_void_p, c_ulonglong, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

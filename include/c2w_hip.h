@@ -609,6 +609,43 @@ int c2w_vario_supported(int H, int W, int R, int M, int order2); /* 1 or 0 */
 long long c2w_vario_scratch_bytes(long long planes, int H, int W, int R);
 int c2w_vario_terms(const float* x, const float* y, double* V, double* scratch, unsigned long long scratch_bytes, int M, long long planes,
                     int H, int W, int R, int order2, void* stream);
+/* Temporal increments of an ensemble: what a field does from one hour to a later one, which no score above sees -- each of them judges
+ * one (t, f) plane at a time.  The definitions are elementary and verified by known answers (README, statement 11).
+ *
+ * Definitions.  x is [n_rep][T][F][hw], y is [T][F][hw] or NULL, both dense fp32 read as exact numbers.  The rows are r_0 = y when a
+ * truth is given, then r_1 .. r_n = x (as c2w_escore_pairs has them); D = n_rep + 1 with a truth, n_rep without.  For row d, anchor
+ * time t, variable f and lag tau = 1 .. L with t + tau < T, over the hw cells c of the plane
+ *   dx_c = r_d[t + tau][f][c] - r_d[t][f][c],  dy_c the same increment of the truth
+ *   S[d][t][f][tau - 1][0] = sum_c |dx_c|            (A1)
+ *   S[d][t][f][tau - 1][1] = sum_c dx_c^2            (A2)
+ *   S[d][t][f][tau - 1][2] = sum_c (dx_c - dy_c)^2   (E2)
+ * S is double, [D][T][F][L][3], every entry written.  The truth's own row has E2 = +0.0; without a truth column 2 is +0.0; an entry
+ * with t + tau >= T is +0.0 in all three columns: there is no pair, and the host knows the count.  From S, the caller's in float64
+ * (climate2weather_amd.temporal): the structure functions S_p(tau) = sum_t A_p / ((T - tau) hw), the variability ratios
+ * sqrt(S_2^m / S_2^y) and S_1^m / S_1^y, the tendency RMSE sqrt(sum_t E2 / ((T - tau) hw)) and the means by phase of an observation
+ * period.
+ * Non-finite values: a NaN or an infinity in plane (d, t, f) makes exactly these entries NaN, written explicitly: (d, t, f, tau) for
+ * every tau that has a pair, (d, t - tau, f, tau) for every tau <= t, and, when the plane is the truth's, column 2 of the same entries
+ * of every row (of the truth's own too); no other entry is touched.  The kernel sees it on the result -- every term is >= 0 and an
+ * increment with a non-finite end is not finite, so a sum is non-finite exactly then and is written as NaN; a dx^2 that overflows fp32
+ * (an increment beyond 1.8e19) ends as NaN as well.
+ * tincr_terms_kernel: a workgroup of 256 owns one (d, t, f) anchor plane, or one chunk of 4096 cells of it (a function of hw alone).
+ * The lags go in passes of 4; in a pass a thread loads 4 adjacent cells of the anchor plane, of the pass's four later planes and, with
+ * a truth, of the truth's five, 16 bytes a load (a lag past L or past the end of the series reads plane T - 1 again and forms no term).
+ * dx = b - a, |dx| and dx * dx, e = dx - dy and e * e are fp32, no multiply fused with an add; every fp32 term is added straight into
+ * its double accumulator, cells in ascending order: no fp32 chain is kept.  The 12 sums of a pass fold by the fixed-order sum of
+ * csrc/ordered_sum.h (sixteen threads at a time, then the sixteen group totals), and when a plane has several chunks
+ * fold_parts_kernel adds them in index order: at most two launches on the caller's stream, no atomics, no host read-back, the same
+ * bits for an entry wherever its plane lies in the launch.  A plane is read up to L + 1 times as an anchor and as a later plane; the
+ * re-reads are left to the caches.  Error against float64 (tests/fp64_temporal_ref.py): A1 within 2 * 2^-24 of itself, A2 within
+ * 3 * 2^-24 of itself, E2 within 6 * 2^-24 sum_c (|dx_c| + |dy_c|)^2 -- the error of E2 scales with the increments, not with their
+ * difference -- each plus one fp32 denormal per cell.  scratch: c2w_tincr_scratch_bytes(rows, T, F, hw, L) bytes, rows = D (0 while a
+ * plane is one chunk: the pointer may then be NULL), 8-byte aligned, every byte of it written before it is read.  Supported: hw a
+ * multiple of 4, 1 <= L <= 24 (x, y 16-byte aligned).  Everything unsupported returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_tincr_supported(int hw, int L); /* 1 or 0 */
+long long c2w_tincr_scratch_bytes(long long rows, int T, int F, int hw, int L);
+int c2w_tincr_terms(const float* x, const float* y, double* S, double* scratch, unsigned long long scratch_bytes, int n_rep, int T, int F,
+                    int hw, int L, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
