@@ -134,6 +134,12 @@ _PROTOS = {
     "c2w_tincr_supported": [c_int, c_int],
     "c2w_tincr_scratch_bytes": [c_longlong, c_int, c_int, c_int, c_int],
     "c2w_tincr_terms": [c_void_p, c_void_p, c_void_p, c_void_p, c_ulonglong, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_qmap_supported": [c_int, c_int, c_int],
+    "c2w_qmap_scratch_bytes": [c_longlong, c_int, c_int],
+    "c2w_qmap_nodes": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ulonglong, c_longlong, c_int, c_int, c_int, c_int,
+                       c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_qmap_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                       c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

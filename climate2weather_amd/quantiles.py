@@ -18,8 +18,8 @@ numpy by tests/test_quantiles_cpu.py; a zero result may carry either sign, and a
 ``False`` makes any NaN turn its data set's whole row NaN, as ``numpy.quantile`` does.  A data set without a valid value is a NaN row.
 That ``xarray.Dataset.quantile(skipna=None)`` skips NaNs for float data is recalled, not verified (README, seventh statement).
 
-Nothing here synchronises.  Out of scope: netCDF I/O, quantile mapping / bias correction, more than 16 levels on the kernel (the
-general route takes them), and collectives -- members are rank-local.
+Nothing here synchronises.  Out of scope: netCDF I/O, more than 16 levels on the kernel (the general route takes them), and
+collectives -- members are rank-local.  Per-cell quantiles over time and quantile mapping are ``biascorrect.py``.
 """
 from __future__ import annotations
 

@@ -646,6 +646,45 @@ int c2w_tincr_supported(int hw, int L); /* 1 or 0 */
 long long c2w_tincr_scratch_bytes(long long rows, int T, int F, int hw, int L);
 int c2w_tincr_terms(const float* x, const float* y, double* S, double* scratch, unsigned long long scratch_bytes, int n_rep, int T, int F,
                     int hw, int L, void* stream);
+/* Empirical quantile mapping per cell (climate2weather_amd.biascorrect): the step that turns a coarse climate-model series into the
+ * bias-corrected series the sampler is conditioned on.  x: [n_rep][T][F][hw] fp32.  A SERIES is the values of one variable at one cell
+ * over the times of one group (a calendar month, say; G = 1: no grouping).  The groups are given as a list: tidx[Tu] (int, device) holds
+ * the times that have a group, sorted by group, and goff[G + 1] (int, device) where each group's part begins; group g is
+ * tidx[goff[g] .. goff[g + 1]), goff[0] = 0, goff[G] = Tu <= T, and max_len is the longest group.  The kernels clamp every index they
+ * read from the two lists, so a wrong list gives wrong numbers and never an access outside the arrays.
+ * Nodes.  levels[K] (double, device), p_0 < .. < p_{K-1} in [0, 1].  q[rep][g][f][c][k] is the quantile at p_k of series
+ * (rep, g, f, c) by the definition of c2w_quantiles above -- numpy.nanquantile(series.astype(float64), p_k), method "linear" with
+ * numpy's _lerp: the two order statistics are exact fp32, the interpolation is float64 (csrc/quantile_core.h: rank_of, lerp_of, and
+ * the monotone key the values are sorted by).  skipna != 0 leaves NaNs out; skipna == 0 makes the K nodes of a series with a NaN NaN.
+ * A series without a valid value, an empty group included, is K NaNs.  n_valid[rep][g][f][c] (long long) = the non-NaN values.
+ * c2w_qmap_nodes serves the cells [c0, c1) of every (rep, f) and writes only their entries; the caller walks the cell blocks so that
+ * scratch -- c2w_qmap_scratch_bytes(n_rep F, c1 - c0, Tu) bytes, the series one after the other, fp32 -- stays bounded.  Two
+ * launches: qmap_gather_kernel moves a tile of 64 list positions x 64 cells through LDS (a wave reads 256 contiguous bytes of a
+ * plane and writes 256 contiguous bytes of a series); qmap_sort_kernel, a workgroup per series, loads the keys into LDS (a NaN and the
+ * padding to the next power of two become the key no number has and sort to the top), runs a bitonic network, finds the count by
+ * bisection and has thread k interpolate level k.
+ * Mapping.  xq / yq [G][F][hw][K] (double): the nodes of the model's and of the reference's historical series.  out (the shape of x;
+ * may BE x) gets, for every time t that has a group g, with the tables of (g, f, c), all in float64:
+ *     j = the last node with xq[j] <= x
+ *     no such node (x < xq[0]):  y = x + (yq[0] - xq[0])
+ *     j == K - 1:                y = x + (yq[K-1] - xq[K-1])            (additive constant tails; x == xq[K-1] and +inf included)
+ *     otherwise:                 v = yq[j] + (x - xq[j]) * ((yq[j+1] - yq[j]) / (xq[j+1] - xq[j])),  y = v > yq[j+1] ? yq[j+1] : v
+ * no multiply fused with an add, y rounded once to fp32.  The interval is never degenerate (j is the LAST node <= x), and the clamp
+ * makes the map non-decreasing across node boundaries.  A NaN x or a NaN table row gives NaN; a time without a group is not written.
+ * qmap_apply_kernel: a workgroup of 512 per (g, f, block of C adjacent cells, slab of the group's (rep, time) rows), C in {64 .. 4}
+ * chosen from K so that both tables of its cells fit 72 KiB of LDS; it stages them once, then walks its rows with 16-byte loads, four
+ * in flight, bisects the four values of a load in LDS side by side and stores to the position it loaded from: each input read once,
+ * each output written once.
+ * Both: no atomics, no host read-back, everything on the caller's stream, the same bits wherever a series lies in the launch.
+ * Supported: hw a multiple of 4, 2 <= K <= 128, max_len <= 16384 (x, out 16-byte aligned).  Everything unsupported returns
+ * C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_qmap_supported(int hw, int K, int max_len); /* 1 or 0 */
+long long c2w_qmap_scratch_bytes(long long rows, int cells, int Tu);
+int c2w_qmap_nodes(const float* x, const int* tidx, const int* goff, const double* levels, double* q, long long* n_valid, float* scratch,
+                   unsigned long long scratch_bytes, long long n_rep, int T, int F, int hw, int Tu, int G, int K, int max_len, int skipna,
+                   int c0, int c1, void* stream);
+int c2w_qmap_apply(const float* x, float* out, const double* xq, const double* yq, const int* tidx, const int* goff, long long n_rep, int T,
+                   int F, int hw, int Tu, int G, int K, int max_len, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
