@@ -140,6 +140,10 @@ _PROTOS = {
                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "c2w_qmap_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                        c_void_p],
+    "c2w_event_counts_supported": [c_int, c_int, c_int],
+    "c2w_event_counts": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_fss_supported": [c_int, c_int, c_int, c_int, c_void_p, c_int],
+    "c2w_fss_sums": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

@@ -685,6 +685,41 @@ int c2w_qmap_nodes(const float* x, const int* tidx, const int* goff, const doubl
                    int c0, int c1, void* stream);
 int c2w_qmap_apply(const float* x, float* out, const double* xq, const double* yq, const int* tidx, const int* goff, long long n_rep, int T,
                    int F, int hw, int Tu, int G, int K, int max_len, void* stream);
+/* Event verification of an ensemble (climate2weather_amd.events): was the event forecast?  Every score above is an average over the
+ * whole distribution; these ask about a threshold.  The Brier score, its decomposition and the ROC are elementary and verified by
+ * identities; the fair correction and the FSS of Roberts & Lean (2008) are recalled; the zero-padded box filter is verified against
+ * scipy.ndimage.uniform_filter(mode="constant") (README, statement 13).
+ *
+ * The event.  x is [M][T][F][hw], y is [T][F][hw], dense fp32 read as exact numbers; thr[F][K] fp32 and dir[F][K] int: entry (f, k)
+ * is the event x >= thr (dir != 0, "above") or x <= thr (dir == 0, "below"), IEEE comparisons: infinities compare as numbers, a NaN is
+ * no event in its own row.  Both kernels produce INTEGER tables (long long), added with 64-bit integer adds to an output the call
+ * zeroes first: the result does not depend on any order, and it equals the definition bit for bit.
+ *
+ * c2w_event_counts.  counts[t][f][k][o][j], [T][F][K][2][M + 1]: the cells of plane (t, f) whose truth indicator is o and in which
+ * exactly j of the M members have the event.  invalid[t][f]: the cells with a NaN among their M + 1 values; they are in no bin, so
+ * sum_{o, j} counts[t][f][k] + invalid[t][f] = hw for every k.  event_counts_kernel: a workgroup of 256 owns one plane or one chunk of
+ * 4096 cells of it; a thread loads 4 adjacent cells of the truth (16 bytes), keeps them and streams the members over them, its four
+ * member counts per threshold in the bytes of one register.  The bins live in LDS.  The common bin (0, 0) -- no event, no member -- is
+ * never added in LDS: the threads count their valid cells in a register and bin (0, 0) = valid cells - the other bins.  One 64-bit
+ * add per non-zero bin goes to the output.  Supported: hw a multiple of 4, 1 <= M <= 64, 1 <= K <= 8 (x, y 16-byte aligned).
+ *
+ * c2w_fss_sums.  The rows are d = 0 the truth, d = 1 .. M the members and d = M + 1 the ensemble, whose cell value is the member
+ * count 0 .. M.  For radius r = radii[s] (a HOST array of S ints), n_d(c) = the sum of row d's cell values over the (2r + 1)^2 window
+ * centred on cell c of the H x W plane, cells outside the domain counting 0.  sums[t][f][k][s][d][0..1] = (sum_c n_d(c)^2,
+ * sum_c n_d(c) n_0(c)), [T][F][K][S][M + 2][2]; row 0 holds (OO, OO).  fss_sums_kernel: a workgroup of 256 owns (plane, threshold, tile
+ * of at most 64 x 64 cells) -- the thresholds run over the grid, the planes are re-read from the caches -- and stages the tile plus a
+ * halo of the largest radius, clipped to the domain (at most 96 x 96), as indicators in LDS, where a scan along the rows and one along
+ * the columns make the row's summed-area table (16-bit entries); every radius reads it with four LDS reads per cell.  The truth's
+ * table stays resident while the members go by; the member counts accumulate as bytes and get a 32-bit table at the end.  Products
+ * and sums are 64-bit.  75440 bytes of LDS, two workgroups a CU (csrc/events_core.h has the budget).  Supported: W a multiple of 4, H, W >= 4,
+ * H W <= 2^20, 1 <= M <= 64, 1 <= K <= 8, 1 <= S <= 8 radii in 0 .. 16, and (M (2r + 1)^2)^2 H W < 2^62.
+ * Both: no host read-back, everything on the caller's stream.  Everything unsupported returns C2W_ERR_UNSUPPORTED and writes nothing. */
+int c2w_event_counts_supported(int hw, int M, int K); /* 1 or 0 */
+int c2w_event_counts(const float* x, const float* y, const float* thr, const int* dir, long long* counts, long long* invalid, int M, int T,
+                     int F, int hw, int K, void* stream);
+int c2w_fss_supported(int H, int W, int M, int K, const int* radii, int S); /* 1 or 0 */
+int c2w_fss_sums(const float* x, const float* y, const float* thr, const int* dir, long long* sums, const int* radii, int M, int T, int F,
+                 int H, int W, int K, int S, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
