@@ -720,6 +720,37 @@ int c2w_event_counts(const float* x, const float* y, const float* thr, const int
 int c2w_fss_supported(int H, int W, int M, int K, const int* radii, int S); /* 1 or 0 */
 int c2w_fss_sums(const float* x, const float* y, const float* thr, const int* dir, long long* sums, const int* radii, int M, int T, int F,
                  int H, int W, int K, int S, void* stream);
+/* Event spells of an ensemble (climate2weather_amd.spells): how long does an event last?  The scores above judge one (t, f) plane at a
+ * time or the difference between two times; a calm of 30 hours, a frost of five nights and a gale of two hours can share all of them.
+ * The definitions are elementary and verified by known answers; nothing is taken from a package (README, statement 14).
+ *
+ * The event is that of c2w_event_counts: x is [M][T][F][hw], y is [T][F][hw] or NULL, dense fp32 read as exact numbers; thr[F][K] fp32
+ * and dir[F][K] int, x >= thr (dir != 0) or x <= thr (dir == 0), IEEE comparisons: infinities compare as numbers, a NaN is no event.
+ * Rows: d = 0 is the truth if y is given, then the M members; D = M + 1, or M without a truth.  A SERIES is the indicator e[t] of one
+ * (d, f, k, cell) over all the times seen so far, block after block.  A NaN ends a spell like any non-event; NaN cell-hours are counted
+ * per (d, f) in invalid.  A SPELL is a maximal run of consecutive 1s of a series, its length L the hours in it.
+ *
+ * c2w_spell_update takes one block of T >= 0 times whose first plane is the absolute hour t0 >= 0 (T = 0 does nothing).
+ *   state[4][D][F][K][hw] int: (open, longest, count, hours) of every series -- open the length of the run open at the last time seen
+ *     (0 if none), longest and count over the spells that have ENDED, hours all event hours.  Read at the start, written at the end.
+ *   hist[D][F][K][Lmax] long long, Lmax = max_duration: += the spells that ended in this block with L = b + 1; the last bin holds
+ *     L >= Lmax.  A spell carried in through state.open has its whole length.
+ *   onsets[D][F][K][period] long long (NULL at period = 0): += the spells whose first hour t has (t0 + t) mod period = phi.  A run
+ *     that begins at a series' very first time is an onset there; a run continued from the previous block is none.
+ *   invalid[D][F] long long: += the NaN cell-hours.
+ * hist, onsets and invalid are ACCUMULATORS: the caller zeroes them once and the call adds.  The call never closes a run at the block's
+ * end: a run that touches the last time seen is in state.open alone, and the caller closes it on a copy when it wants the tables
+ * (hist + the bins of min(open, Lmax), count + (open > 0), max(longest, open)) -- censored spells are counted, not dropped.
+ * spell_update_kernel: a workgroup of 256 owns (row, variable, chunk of 1024 cells); a thread owns 4 adjacent cells, keeps their
+ * counters of up to 4 thresholds in 64 registers and walks the T planes in order with 16-byte loads, 8 in flight; an event that starts a
+ * run is one LDS add, a run that ends another, nothing else touches LDS (4484 bytes); one 64-bit integer add per non-zero bin goes to the
+ * accumulators, so no bit depends on any order.  K > 4 is two launches over disjoint entries.  Time is not split over workgroups.  No
+ * scratch, no host read-back, everything on the caller's stream.  Supported: hw a multiple of 4, 1 <= K <= 8, 1 <= max_duration <= 256,
+ * 0 <= period <= 24, M >= 1 (x, y, state 16-byte aligned); everything else returns C2W_ERR_UNSUPPORTED and writes nothing.  T beyond
+ * 2^20 in one call is C2W_ERR_BAD_SHAPE (the LDS bins are 32-bit); the caller keeps the total time under 2^31. */
+int c2w_spell_supported(int hw, int K, int max_duration, int period); /* 1 or 0 */
+int c2w_spell_update(const float* x, const float* y, const float* thr, const int* dir, int* state, long long* hist, long long* onsets,
+                     long long* invalid, int M, int T, int F, int hw, int K, int max_duration, int period, long long t0, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
