@@ -4,9 +4,6 @@
 // (ordered_sum_launch.h) adds the chunks of a plane in index order when there are several.  crps_core.h has the index maps and the arithmetic; this file is the workgroups
 // around them.  No float atomics, no sum whose order depends on the launch.
 #include "ordered_sum_launch.h"
-
-#define CRPS_HD __device__ __attribute__((always_inline))
-#define CRPS_BOTH __host__ __device__ __attribute__((always_inline))
 #include "crps_core.h"
 
 namespace {
@@ -54,13 +51,11 @@ extern "C" long long c2w_crps_scratch_bytes(int T, int F, int hw) {
 extern "C" int c2w_crps_terms(const float* x, const float* y, double* sums, float* cells, double* scratch, unsigned long long scratch_bytes, int M, int T,
                               int F, int hw, void* stream) {
     if (!crps::supported(hw, M)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !sums || T < 1 || F < 1 || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)cells) & 15) != 0 ||
-        (((uintptr_t)sums | (uintptr_t)scratch) & 7) != 0)
-        return C2W_ERR_BAD_ARG;
+    if (!x || !y || !sums || T < 1 || F < 1 || !c2w_aligned(16, x, y, cells) || !c2w_aligned(8, sums, scratch)) return C2W_ERR_BAD_ARG;
     const int nc = crps::chunks(hw);
     const long long planes = (long long)T * F, grid = planes * nc, need = crps::scratch_bytes(T, F, hw);
     if (need > 0 && (!scratch || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     double* out = nc > 1 ? scratch : sums;
     int rc;

@@ -1,5 +1,5 @@
 // Ensemble CRPS and spread-skill: the index maps and the arithmetic of crps.hip, written as barrier-separated phases over "thread tid of
-// a workgroup", as kde_core.h is.  Compiled for the host (CRPS_HD empty) the same phases run one thread after the other over a record
+// a workgroup", as kde_core.h is.  Compiled for the host (core_side.h) the same phases run one thread after the other over a record
 // per thread: tests/host_crps_main.cpp checks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_crps_terms).  One cell (t, f, c) has the members x_1 .. x_M = x[m][t][f][c] and the truth y = y[t][f][c];
@@ -25,12 +25,7 @@
 #ifndef C2W_CRPS_CORE_H
 #define C2W_CRPS_CORE_H
 
-#ifndef CRPS_HD
-#define CRPS_HD
-#define CRPS_BOTH
-#define CRPS_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 
 #if defined(__clang__)
 #define CRPS_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -53,20 +48,20 @@ struct alignas(4 * V) Pack {
     float v[V];
 };
 
-static CRPS_BOTH inline bool supported(int hw, int M) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= MAX_M; }
+static C2W_BOTH inline bool supported(int hw, int M) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= MAX_M; }
 
 // ---------------------------------------------------------------------------------------------------------------- maps
 
-static CRPS_BOTH inline int rows_of(int M) { return M <= 8 ? 8 : M <= 16 ? 16 : M <= 32 ? 32 : 64; }
-static CRPS_BOTH inline int cells_per_thread(int K) { return K <= 16 ? 4 : K == 32 ? 2 : 1; }
-static CRPS_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
-static CRPS_BOTH inline int chunk_begin(int c) { return c * CHUNK; }
-static CRPS_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
+static C2W_BOTH inline int rows_of(int M) { return M <= 8 ? 8 : M <= 16 ? 16 : M <= 32 ? 32 : 64; }
+static C2W_BOTH inline int cells_per_thread(int K) { return K <= 16 ? 4 : K == 32 ? 2 : 1; }
+static C2W_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
+static C2W_BOTH inline int chunk_begin(int c) { return c * CHUNK; }
+static C2W_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
 // rounds of the workgroup over chunk c, and the first of the V cells thread tid owns in round `it`
-static CRPS_BOTH inline int rounds(int hw, int c, int V) { return (chunk_end(hw, c) - chunk_begin(c) + V * THREADS - 1) / (V * THREADS); }
-static CRPS_BOTH inline int cell_of(int c, int it, int tid, int V) { return chunk_begin(c) + (it * THREADS + tid) * V; }
+static C2W_BOTH inline int rounds(int hw, int c, int V) { return (chunk_end(hw, c) - chunk_begin(c) + V * THREADS - 1) / (V * THREADS); }
+static C2W_BOTH inline int cell_of(int c, int it, int tid, int V) { return chunk_begin(c) + (it * THREADS + tid) * V; }
 // bytes of partial sums: none while a plane is one chunk
-static CRPS_BOTH inline long long scratch_bytes(long long T, long long F, int hw) {
+static C2W_BOTH inline long long scratch_bytes(long long T, long long F, int hw) {
     return chunks(hw) > 1 ? T * F * chunks(hw) * 4 * (long long)sizeof(double) : 0;
 }
 
@@ -93,13 +88,13 @@ struct Thread {
 };
 
 template <int K, int V>
-static CRPS_HD inline void t_init(const View& v, Thread<K, V>& th) {
+static C2W_HD inline void t_init(const View& v, Thread<K, V>& th) {
     th.rM = (float)(1.0 / (double)v.M);
     th.rM1 = v.M > 1 ? (float)(1.0 / (double)(v.M - 1)) : 0.f;
     th.acc[0] = th.acc[1] = th.acc[2] = th.acc[3] = 0.0;
 }
 
-static CRPS_HD inline int not_finite(float a) { return !(__builtin_fabsf(a) < __builtin_inff()); }
+static C2W_HD inline int not_finite(float a) { return !(__builtin_fabsf(a) < __builtin_inff()); }
 
 // fn(Row<I>) for I = 0 .. min(M, K) - 1: unrolled at compile time, so a row index is never data (a register array indexed by a
 // variable would go to scratch memory), left at row M by a branch (M is the same for the whole launch)
@@ -108,7 +103,7 @@ struct Row {
     static constexpr int i = I;
 };
 template <int I, int K, typename Fn>
-static CRPS_HD inline void rows_from(int M, Fn&& fn) {
+static C2W_HD inline void rows_from(int M, Fn&& fn) {
     if constexpr (I < K) {
         if (I >= M) return;
         fn(Row<I>{});
@@ -118,41 +113,41 @@ static CRPS_HD inline void rows_from(int M, Fn&& fn) {
 // On the device M goes through an empty asm statement first: every walk then compares rows with a scalar of its own, right where it
 // branches.  Without it the compiler computes the K comparisons once per kernel, keeps them as K lane masks in scalar registers and
 // spills those (seen: 263 spilled scalar registers and 722 lane reads at K = 64).
-#ifdef CRPS_HOST
+#ifdef C2W_CORE_HOST
 static inline int own_scalar(int m) { return m; }
 static inline long long own_scalar(long long m) { return m; }
 #else
-static CRPS_HD inline int own_scalar(int m) {
+static C2W_HD inline int own_scalar(int m) {
     asm volatile("" : "+s"(m));
     return m;
 }
-static CRPS_HD inline long long own_scalar(long long m) {
+static C2W_HD inline long long own_scalar(long long m) {
     asm volatile("" : "+s"(m));
     return m;
 }
 #endif
 template <int I, int K, typename Fn>
-static CRPS_HD inline void rows_below(int M, Fn&& fn) {
+static C2W_HD inline void rows_below(int M, Fn&& fn) {
     rows_from<I, K>(own_scalar(M), fn);
 }
 // the same rows, each behind a branch of its own and none left early: for a walk that fills registers, where leaving early would
 // make every later register a value with K + 1 possible origins
 template <int I, int K, typename Fn>
-static CRPS_HD inline void rows_each_from(int M, Fn&& fn) {
+static C2W_HD inline void rows_each_from(int M, Fn&& fn) {
     if constexpr (I < K) {
         if (I < M) fn(Row<I>{});
         rows_each_from<I + 1, K>(M, fn);
     }
 }
 template <int I, int K, typename Fn>
-static CRPS_HD inline void rows_each(int M, Fn&& fn) {
+static C2W_HD inline void rows_each(int M, Fn&& fn) {
     rows_each_from<I, K>(own_scalar(M), fn);
 }
 #define CRPS_ROW(r) [&](auto r) __attribute__((always_inline))
 
 // the thread's V cells of round `it`: the truth and all M members, as wide as V allows; nothing is used before all are asked for
 template <int K, int V>
-static CRPS_HD inline void t_fetch(const View& v, Thread<K, V>& th, int tid, int it) {
+static C2W_HD inline void t_fetch(const View& v, Thread<K, V>& th, int tid, int it) {
     th.cell = cell_of(v.chunk, it, tid, V);
     th.has = th.cell < chunk_end(v.hw, v.chunk);
     if (!th.has) return;
@@ -185,7 +180,7 @@ static CRPS_HD inline void t_fetch(const View& v, Thread<K, V>& th, int tid, int
 
 // Batcher's odd-even merge sort of the K rows, every one of the V columns at once: 19, 63, 191, 543 pairs at K = 8, 16, 32, 64
 template <int K, int V>
-static CRPS_HD inline void t_sort(Thread<K, V>& th) {
+static C2W_HD inline void t_sort(Thread<K, V>& th) {
 #pragma unroll
     for (int p = 1; p < K; p *= 2)
 #pragma unroll
@@ -205,7 +200,7 @@ static CRPS_HD inline void t_sort(Thread<K, V>& th) {
 
 // the four terms of every column from its sorted rows
 template <int K, int V>
-static CRPS_HD inline void t_terms(const Thread<K, V>& th, int M, float (&o)[4][V]) {
+static C2W_HD inline void t_terms(const Thread<K, V>& th, int M, float (&o)[4][V]) {
     CRPS_NO_CONTRACT
     float a[V], b[V], es[V], ss[V], p[V], ebar[V];
 #pragma unroll
@@ -251,7 +246,7 @@ static CRPS_HD inline void t_terms(const Thread<K, V>& th, int M, float (&o)[4][
 }
 
 template <int K, int V>
-static CRPS_HD inline void t_cells(const View& v, Thread<K, V>& th) {
+static C2W_HD inline void t_cells(const View& v, Thread<K, V>& th) {
     if (!th.has) return;
     t_sort(th);
     float o[4][V];
@@ -271,15 +266,15 @@ static CRPS_HD inline void t_cells(const View& v, Thread<K, V>& th) {
 // the three phases of ordered_sum.h at N = 4: thread s writes the workgroup's entry of sum s, an infinite sum stays; f_fold then
 // writes sums[entry], entry = plane 4 + s, from the chunks in index order
 template <int K, int V>
-static CRPS_HD inline void t_stash(const View& v, const Thread<K, V>& th, int tid) { ordered_sum::stash<4>(v.lds, th.acc, tid); }
-static CRPS_HD inline void t_fold_groups(const View& v, int tid) { ordered_sum::fold_groups<4>(v.lds, tid); }
-static CRPS_HD inline void t_fold_store(const View& v, int tid) {
+static C2W_HD inline void t_stash(const View& v, const Thread<K, V>& th, int tid) { ordered_sum::stash<4>(v.lds, th.acc, tid); }
+static C2W_HD inline void t_fold_groups(const View& v, int tid) { ordered_sum::fold_groups<4>(v.lds, tid); }
+static C2W_HD inline void t_fold_store(const View& v, int tid) {
     if (tid >= 4) return;
     const double t = ordered_sum::fold_total<4>(v.lds, tid);
     const int nc = chunks(v.hw);
     v.out[(v.plane * nc + v.chunk) * 4 + tid] = ordered_sum::nan_if_nan(t);
 }
-static CRPS_HD inline void f_fold(const double* partial, double* sums, long long entry, int nc) {
+static C2W_HD inline void f_fold(const double* partial, double* sums, long long entry, int nc) {
     sums[entry] = ordered_sum::nan_if_nan(ordered_sum::fold_parts(partial, entry, nc, 4));
 }
 

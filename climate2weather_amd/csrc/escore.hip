@@ -6,9 +6,6 @@
 // fold_parts_kernel (ordered_sum_launch.h) adds the chunks or the tiles of a plane in index order.  escore_core.h has the index maps
 // and the arithmetic; this file is the workgroups around them.  No float atomics, no sum whose order depends on the launch.
 #include "ordered_sum_launch.h"
-
-#define ESC_HD __device__ __attribute__((always_inline))
-#define ESC_BOTH __host__ __device__ __attribute__((always_inline))
 #include "escore_core.h"
 
 namespace {
@@ -78,11 +75,11 @@ extern "C" long long c2w_escore_scratch_bytes(long long planes, int hw, int M) {
 extern "C" int c2w_escore_pairs(const float* x, const float* y, double* d2, double* scratch, unsigned long long scratch_bytes, int M, long long planes,
                                 int hw, void* stream) {
     if (!escore::p_supported(hw, M)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !d2 || planes < 1 || (((uintptr_t)x | (uintptr_t)y) & 15) != 0 || (((uintptr_t)d2 | (uintptr_t)scratch) & 7) != 0) return C2W_ERR_BAD_ARG;
+    if (!x || !y || !d2 || planes < 1 || !c2w_aligned(16, x, y) || !c2w_aligned(8, d2, scratch)) return C2W_ERR_BAD_ARG;
     const int nc = escore::p_chunks(hw), P = escore::p_pairs(M);
     const long long grid = planes * nc, need = escore::p_scratch_bytes(planes, hw, M);
     if (need > 0 && (!scratch || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int lds = escore::p_lds_bytes(M);
     if (lds > 65536)
@@ -103,11 +100,11 @@ extern "C" long long c2w_vario_scratch_bytes(long long planes, int H, int W, int
 extern "C" int c2w_vario_terms(const float* x, const float* y, double* V, double* scratch, unsigned long long scratch_bytes, int M, long long planes, int H,
                                int W, int R, int order2, void* stream) {
     if (!escore::v_supported(H, W, R, M, order2)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !V || planes < 1 || (((uintptr_t)x | (uintptr_t)y) & 3) != 0 || (((uintptr_t)V | (uintptr_t)scratch) & 7) != 0) return C2W_ERR_BAD_ARG;
+    if (!x || !y || !V || planes < 1 || !c2w_aligned(4, x, y) || !c2w_aligned(8, V, scratch)) return C2W_ERR_BAD_ARG;
     const int nt = escore::v_tiles(H, W);
     const long long grid = planes * nt, need = escore::v_scratch_bytes(planes, H, W, R);
     if (need > 0 && (!scratch || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
-    if (grid > 0x7fffffffLL || (long long)H * W > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid) || (long long)H * W > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     double* out = nt > 1 ? scratch : V;
     int rc;

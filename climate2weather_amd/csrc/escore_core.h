@@ -1,5 +1,5 @@
 // Energy and variogram scores of an ensemble: the index maps and the arithmetic of escore.hip, written as barrier-separated phases over
-// "thread tid of a workgroup", as crps_core.h is.  Compiled for the host (ESC_HD empty) the same phases run one thread after the other
+// "thread tid of a workgroup", as crps_core.h is.  Compiled for the host (core_side.h) the same phases run one thread after the other
 // over a record per thread: tests/host_escore_main.cpp checks every map below without a GPU.
 //
 // Definitions (c2w_hip.h: c2w_escore_pairs, c2w_vario_terms).  One (t, f) plane has the rows r_0 = y (the truth) and r_1 .. r_M = x_m,
@@ -31,12 +31,7 @@
 #ifndef C2W_ESCORE_CORE_H
 #define C2W_ESCORE_CORE_H
 
-#ifndef ESC_HD
-#define ESC_HD
-#define ESC_BOTH
-#define ESC_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 
 #if defined(__clang__)
 #define ESC_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -65,27 +60,27 @@ constexpr int P_QUADS = P_CHUNK / 4;   // groups of 4 cells
 constexpr int P_PITCH = P_CHUNK + 4;   // floats between two rows in LDS: row blocks start 16 banks apart
 constexpr int P_FOLD_BYTES = 16 * THREADS * 8;
 
-static ESC_BOTH inline bool p_supported(int hw, int M) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= P_MAX_M; }
-static ESC_BOTH inline int p_pairs(int M) { return M * (M + 1) / 2; }
-static ESC_BOTH inline int p_pair_index(int M, int i, int j) { return i * (2 * (M + 1) - i - 1) / 2 + (j - i - 1); }
-static ESC_BOTH inline int p_blocks(int M) { return (M + 1 + 3) / 4; }
-static ESC_BOTH inline int p_tiles(int M) { return p_blocks(M) * (p_blocks(M) + 1) / 2; }
+static C2W_BOTH inline bool p_supported(int hw, int M) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= P_MAX_M; }
+static C2W_BOTH inline int p_pairs(int M) { return M * (M + 1) / 2; }
+static C2W_BOTH inline int p_pair_index(int M, int i, int j) { return i * (2 * (M + 1) - i - 1) / 2 + (j - i - 1); }
+static C2W_BOTH inline int p_blocks(int M) { return (M + 1 + 3) / 4; }
+static C2W_BOTH inline int p_tiles(int M) { return p_blocks(M) * (p_blocks(M) + 1) / 2; }
 // threads a tile: the largest power of two with tiles * S <= 256, at most 64 (one group of cells a round at least)
-static ESC_BOTH inline int p_slices(int M) {
+static C2W_BOTH inline int p_slices(int M) {
     int s = 64;
     while (s * p_tiles(M) > THREADS) s /= 2;
     return s;
 }
-static ESC_BOTH inline int p_chunks(int hw) { return (hw + P_CHUNK - 1) / P_CHUNK; }
-static ESC_BOTH inline int p_lds_bytes(int M) {
+static C2W_BOTH inline int p_chunks(int hw) { return (hw + P_CHUNK - 1) / P_CHUNK; }
+static C2W_BOTH inline int p_lds_bytes(int M) {
     const int stage = (M + 1) * P_PITCH * 4;
     return stage > P_FOLD_BYTES ? stage : P_FOLD_BYTES;
 }
-static ESC_BOTH inline long long p_scratch_bytes(long long planes, int hw, int M) {
+static C2W_BOTH inline long long p_scratch_bytes(long long planes, int hw, int M) {
     return p_chunks(hw) > 1 ? planes * p_chunks(hw) * p_pairs(M) * (long long)sizeof(double) : 0;
 }
 // tile k -> its row blocks (bi <= bj), row-major
-static ESC_BOTH inline void p_tile_blocks(int M, int k, int& bi, int& bj) {
+static C2W_BOTH inline void p_tile_blocks(int M, int k, int& bi, int& bj) {
     const int nb = p_blocks(M);
     bi = 0;
     while (k >= nb - bi) k -= nb - bi, ++bi;
@@ -105,12 +100,12 @@ struct PThread {
     double acc[16];
 };
 
-static ESC_HD inline const float* p_row(const PView& v, int r) {
+static C2W_HD inline const float* p_row(const PView& v, int r) {
     return r == 0 ? v.y + v.plane * v.hw : v.x + ((long long)(r - 1) * v.planes + v.plane) * v.hw;
 }
 
 // the chunk's cells of every row, HBM -> LDS, each value once
-static ESC_HD inline void p_stage(const PView& v, int tid) {
+static C2W_HD inline void p_stage(const PView& v, int tid) {
     float* rows = (float*)v.lds;
     const int n = (v.M + 1) * P_QUADS;
     for (int e = tid; e < n; e += THREADS) {
@@ -121,7 +116,7 @@ static ESC_HD inline void p_stage(const PView& v, int tid) {
     }
 }
 
-static ESC_HD inline void p_pairs_of_tile(const PView& v, PThread& th, int tid) {
+static C2W_HD inline void p_pairs_of_tile(const PView& v, PThread& th, int tid) {
     ESC_NO_CONTRACT
     const int S = p_slices(v.M), tile = tid / S, s = tid % S;
 #pragma unroll
@@ -154,7 +149,7 @@ static ESC_HD inline void p_pairs_of_tile(const PView& v, PThread& th, int tid) 
 }
 
 // after a barrier: the rows are dead, the sums take their place
-static ESC_HD inline void p_stash(const PView& v, const PThread& th, int tid) {
+static C2W_HD inline void p_stash(const PView& v, const PThread& th, int tid) {
     double* fold = (double*)v.lds;
 #pragma unroll
     for (int a = 0; a < 16; ++a) fold[a * THREADS + tid] = th.acc[a];
@@ -162,7 +157,7 @@ static ESC_HD inline void p_stash(const PView& v, const PThread& th, int tid) {
 
 // sum a of tile k is entry k * 16 + a; the threads share the entries round robin: each adds the S threads of the tile in thread order
 // and writes the pair if it is one; p_fold then writes D2[entry], entry = plane P + p, from the chunks in index order
-static ESC_HD inline void p_fold_store(const PView& v, int tid) {
+static C2W_HD inline void p_fold_store(const PView& v, int tid) {
     const int S = p_slices(v.M), n = p_tiles(v.M) * 16;
     for (int e = tid; e < n; e += THREADS) {
         const int tile = e / 16, a = e % 16;
@@ -176,7 +171,7 @@ static ESC_HD inline void p_fold_store(const PView& v, int tid) {
         v.out[(v.plane * p_chunks(v.hw) + v.chunk) * p_pairs(v.M) + p_pair_index(v.M, i, j)] = nan_if_not_finite(t);
     }
 }
-static ESC_HD inline void p_fold(const double* partial, double* d2, long long entry, int nc, int P) {
+static C2W_HD inline void p_fold(const double* partial, double* d2, long long entry, int nc, int P) {
     d2[entry] = nan_if_not_finite(ordered_sum::fold_parts(partial, entry, nc, P));
 }
 
@@ -190,26 +185,26 @@ constexpr int V_SUMS = 3 * V_BATCH;  // sums a thread hands to one fold
 constexpr int V_FOLD_DOUBLES = ordered_sum::lds_doubles<V_SUMS>();
 
 // order2 = 2 p: 1, 2 or 4
-static ESC_BOTH inline bool v_supported(int H, int W, int R, int M, int order2) {
+static C2W_BOTH inline bool v_supported(int H, int W, int R, int M, int order2) {
     return H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && R >= 1 && R <= V_MAX_R && M >= 1 && M <= V_MAX_M &&
            (order2 == 1 || order2 == 2 || order2 == 4);
 }
-static ESC_BOTH inline int v_offsets(int R) { return ((2 * R + 1) * (2 * R + 1) - 1) / 2; }
+static C2W_BOTH inline int v_offsets(int R) { return ((2 * R + 1) * (2 * R + 1) - 1) / 2; }
 // offset o -> (di, dj): di == 0 and dj = 1 .. R first, then di = 1 .. R with dj = -R .. R
-static ESC_BOTH inline void v_offset_of(int R, int o, int& di, int& dj) {
+static C2W_BOTH inline void v_offset_of(int R, int o, int& di, int& dj) {
     if (o < R) {
         di = 0, dj = o + 1;
     } else {
         di = 1 + (o - R) / (2 * R + 1), dj = (o - R) % (2 * R + 1) - R;
     }
 }
-static ESC_BOTH inline int v_tiles_w(int W) { return (W + V_TW - 1) / V_TW; }
-static ESC_BOTH inline int v_tiles(int H, int W) { return (H / V_TH) * v_tiles_w(W); }
-static ESC_BOTH inline int v_patch_h(int R) { return V_TH + R; }
-static ESC_BOTH inline int v_patch_w(int R) { return V_TW + 2 * R; }
-static ESC_BOTH inline int v_patch_floats(int R, int M) { return (M + 1) * v_patch_h(R) * v_patch_w(R); }
-static ESC_BOTH inline int v_lds_bytes(int R, int M) { return (v_patch_floats(R, M) * 4 + 7) / 8 * 8 + V_FOLD_DOUBLES * 8; }
-static ESC_BOTH inline long long v_scratch_bytes(long long planes, int H, int W, int R) {
+static C2W_BOTH inline int v_tiles_w(int W) { return (W + V_TW - 1) / V_TW; }
+static C2W_BOTH inline int v_tiles(int H, int W) { return (H / V_TH) * v_tiles_w(W); }
+static C2W_BOTH inline int v_patch_h(int R) { return V_TH + R; }
+static C2W_BOTH inline int v_patch_w(int R) { return V_TW + 2 * R; }
+static C2W_BOTH inline int v_patch_floats(int R, int M) { return (M + 1) * v_patch_h(R) * v_patch_w(R); }
+static C2W_BOTH inline int v_lds_bytes(int R, int M) { return (v_patch_floats(R, M) * 4 + 7) / 8 * 8 + V_FOLD_DOUBLES * 8; }
+static C2W_BOTH inline long long v_scratch_bytes(long long planes, int H, int W, int R) {
     return v_tiles(H, W) > 1 ? planes * v_tiles(H, W) * v_offsets(R) * 3 * (long long)sizeof(double) : 0;
 }
 
@@ -222,10 +217,10 @@ struct VView {
     unsigned char* lds;  // v_lds_bytes(R, M): the patch [M + 1][8 + R][32 + 2 R] fp32, then the fold's doubles
 };
 
-static ESC_HD inline double* v_fold_area(const VView& v) { return (double*)(v.lds + (v_patch_floats(v.R, v.M) * 4 + 7) / 8 * 8); }
+static C2W_HD inline double* v_fold_area(const VView& v) { return (double*)(v.lds + (v_patch_floats(v.R, v.M) * 4 + 7) / 8 * 8); }
 
 // the tile and its halo of every row, HBM -> LDS; what lies outside the field is 0 and is never used
-static ESC_HD inline void v_stage(const VView& v, int tid) {
+static C2W_HD inline void v_stage(const VView& v, int tid) {
     float* patch = (float*)v.lds;
     const int ph = v_patch_h(v.R), pw = v_patch_w(v.R), n = (v.M + 1) * ph * pw;
     const int i0 = (v.tile / v_tiles_w(v.W)) * V_TH, j0 = (v.tile % v_tiles_w(v.W)) * V_TW - v.R;
@@ -239,7 +234,7 @@ static ESC_HD inline void v_stage(const VView& v, int tid) {
 }
 
 template <int ORDER2>
-static ESC_HD inline float v_power(float d) {
+static C2W_HD inline float v_power(float d) {
     ESC_NO_CONTRACT
     const float a = __builtin_fabsf(d);
     if constexpr (ORDER2 == 1) return __builtin_sqrtf(a);
@@ -249,7 +244,7 @@ static ESC_HD inline float v_power(float d) {
 
 // offsets o0 .. o0 + 3 of the thread's cell: its 12 terms go straight to the fold area, in the layout of ordered_sum::stash<V_SUMS>
 template <int ORDER2>
-static ESC_HD inline void v_terms(const VView& v, int tid, int o0) {
+static C2W_HD inline void v_terms(const VView& v, int tid, int o0) {
     ESC_NO_CONTRACT
     const float* patch = (const float*)v.lds;
     double* fold = v_fold_area(v);
@@ -294,14 +289,14 @@ static ESC_HD inline void v_terms(const VView& v, int tid, int o0) {
 
 // the fold of ordered_sum.h over the fold area at N = V_SUMS: thread q writes sum q, the entry of offset o0 + q / 3; v_fold then
 // writes V[entry], entry = (plane O + o) 3 + s, from the tiles in index order
-static ESC_HD inline void v_fold_groups(const VView& v, int tid) { ordered_sum::fold_groups<V_SUMS>(v_fold_area(v), tid); }
-static ESC_HD inline void v_fold_store(const VView& v, int tid, int o0) {
+static C2W_HD inline void v_fold_groups(const VView& v, int tid) { ordered_sum::fold_groups<V_SUMS>(v_fold_area(v), tid); }
+static C2W_HD inline void v_fold_store(const VView& v, int tid, int o0) {
     if (tid >= V_SUMS) return;
     const double t = ordered_sum::fold_total<V_SUMS>(v_fold_area(v), tid);
     const long long O = v_offsets(v.R);
     v.out[((v.plane * v_tiles(v.H, v.W) + v.tile) * O + o0) * 3 + tid] = nan_if_not_finite(t);
 }
-static ESC_HD inline void v_fold(const double* partial, double* V, long long entry, int nt, int O3) {
+static C2W_HD inline void v_fold(const double* partial, double* V, long long entry, int nt, int O3) {
     V[entry] = nan_if_not_finite(ordered_sum::fold_parts(partial, entry, nt, O3));
 }
 

@@ -4,9 +4,8 @@
 //   2. loss_level_table_kernel       table[bin(t_b)][c] += (double) sum over slabs of part[b][slab][c]   (one workgroup, images in order)
 // Every sum has one order, fixed by (B, C, HW): equal operands give equal bits.  HBM-bound streaming kernels: 16-byte loads of the rows.
 #include <algorithm>
-#include "common.h"
+#include "launch.h"
 #include "philox.h"
-#include "c2w_hip.h"
 
 namespace {
 
@@ -134,14 +133,14 @@ int levels_launch(const void* y, const float* eps, unsigned long long seed, bool
                   float* per_image, int B, int C, int HW, int ldc, int K, float* scratch, unsigned long long scratch_bytes, int dtype, void* stream) {
     const int P = dtype == C2W_DTYPE_F32 ? 4 : 8;
     if (dtype != C2W_DTYPE_F32 && dtype != C2W_DTYPE_BF16 && dtype != C2W_DTYPE_F16) return C2W_ERR_BAD_ARG;
-    if (!y || (!regen && !eps) || !t || !table || !count || ((uintptr_t)y & 15) != 0) return C2W_ERR_BAD_ARG;
+    if (!y || (!regen && !eps) || !t || !table || !count || !c2w_aligned(16, y)) return C2W_ERR_BAD_ARG;
     if (B <= 0 || C <= 0 || HW <= 0 || K <= 0 || ldc < C || ldc % P != 0) return C2W_ERR_BAD_SHAPE;
     const SlabPlan pl = slab_plan(B, HW);
     const size_t lds = ((size_t)ldc * EV_LD + (size_t)C * EV_Q) * sizeof(float);
-    const bool tiled = lds <= EV_LDS_MAX && (HW & 3) == 0 && (regen || ((uintptr_t)eps & 15) == 0);
+    const bool tiled = lds <= EV_LDS_MAX && (HW & 3) == 0 && (regen || c2w_aligned(16, eps));
     if (regen && !tiled) return C2W_ERR_UNSUPPORTED;  // the caller materialises the stream (c2w_philox_normal) and passes it as a tensor
     if (scratch == nullptr || scratch_bytes < (unsigned long long)c2w_sq_err_levels_scratch_bytes(B, C, HW)) return C2W_ERR_BAD_ARG;
-    if ((long long)B * pl.nslab > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits((long long)B * pl.nslab)) return C2W_ERR_BAD_SHAPE;
     const unsigned grid = (unsigned)B * pl.nslab;
     hipStream_t st = (hipStream_t)stream;
 #define EV_STAGE1(T)                                                                                                                            \

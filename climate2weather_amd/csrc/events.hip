@@ -3,9 +3,6 @@
 // tables: the workgroups add to the zeroed output with 64-bit integer adds, which commute, so the bits do not depend on any order.
 // events_core.h has the index maps and the arithmetic; this file is the workgroups around them.
 #include "launch.h"
-
-#define EV_HD __device__ __attribute__((always_inline))
-#define EV_BOTH __host__ __device__ __attribute__((always_inline))
 #include "events_core.h"
 
 namespace {
@@ -70,8 +67,6 @@ __global__ __launch_bounds__(THREADS) void fss_sums_kernel(const float* __restri
     f_flush(v, tid, M + 1);
 }
 
-bool aligned(const void* a, const void* b, uintptr_t mask) { return (((uintptr_t)a | (uintptr_t)b) & mask) == 0; }
-
 }  // namespace
 
 extern "C" int c2w_event_counts_supported(int hw, int M, int K) { return events::counts_supported(hw, M, K) ? 1 : 0; }
@@ -79,11 +74,12 @@ extern "C" int c2w_event_counts_supported(int hw, int M, int K) { return events:
 extern "C" int c2w_event_counts(const float* x, const float* y, const float* thr, const int* dir, long long* counts, long long* invalid, int M, int T,
                                 int F, int hw, int K, void* stream) {
     if (!events::counts_supported(hw, M, K)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !thr || !dir || !counts || !invalid || T < 1 || F < 1 || !aligned(x, y, 15) || !aligned(counts, invalid, 7) || !aligned(thr, dir, 3))
+    if (!x || !y || !thr || !dir || !counts || !invalid || T < 1 || F < 1 || !c2w_aligned(16, x, y) ||
+        !c2w_aligned(8, counts, invalid) || !c2w_aligned(4, thr, dir))
         return C2W_ERR_BAD_ARG;
     const int nc = events::chunks(hw);
     const long long planes = (long long)T * F, grid = planes * nc;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     HIP_CHECK_RET(hipMemsetAsync(counts, 0, (size_t)planes * K * events::bins(M) * sizeof(long long), st));
     HIP_CHECK_RET(hipMemsetAsync(invalid, 0, (size_t)planes * sizeof(long long), st));
@@ -98,11 +94,11 @@ extern "C" int c2w_fss_supported(int H, int W, int M, int K, const int* radii, i
 extern "C" int c2w_fss_sums(const float* x, const float* y, const float* thr, const int* dir, long long* sums, const int* radii, int M, int T, int F,
                             int H, int W, int K, int S, void* stream) {
     if (!radii || !events::fss_supported(H, W, M, K, radii, S)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !thr || !dir || !sums || T < 1 || F < 1 || !aligned(x, y, 15) || !aligned(sums, nullptr, 7) || !aligned(thr, dir, 3))
+    if (!x || !y || !thr || !dir || !sums || T < 1 || F < 1 || !c2w_aligned(16, x, y) || !c2w_aligned(8, sums) || !c2w_aligned(4, thr, dir))
         return C2W_ERR_BAD_ARG;
     const int nt = events::tiles_y(H) * events::tiles_x(W);
     const long long planes = (long long)T * F, grid = planes * K * nt;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     Radii rr;
     for (int s = 0; s < MAX_S; ++s) rr.r[s] = s < S ? radii[s] : 0;
     if (int rc = c2w_lds_optin<fss_sums_kernel>(FSS_LDS_BYTES)) return rc;

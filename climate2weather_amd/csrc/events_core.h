@@ -1,5 +1,5 @@
 // Event verification of an ensemble: the index maps and the integer arithmetic of events.hip, written as barrier-separated phases over
-// "thread tid of a workgroup", as crps_core.h and temporal_core.h are.  Compiled for the host (EV_HD empty) the same phases run one
+// "thread tid of a workgroup", as crps_core.h and temporal_core.h are.  Compiled for the host (core_side.h) the same phases run one
 // thread after the other: tests/host_events_main.cpp walks every map below without a GPU.
 //
 // The event (c2w_hip.h: c2w_event_counts).  thr[F][K] fp32 and dir[F][K] (1: above, x >= thr; 0: below, x <= thr), IEEE comparisons on
@@ -28,11 +28,7 @@
 #ifndef C2W_EVENTS_CORE_H
 #define C2W_EVENTS_CORE_H
 
-#ifndef EV_HD
-#define EV_HD
-#define EV_BOTH
-#define EV_HOST 1
-#endif
+#include "core_side.h"
 
 #ifndef EV_VISIT_CELL  // the host driver counts here: a cell binned by the counts kernel; a region cell staged, a tile cell summed and
 #define EV_VISIT_CELL(plane, k, cell)                // a table corner read by the FSS kernel (domain coordinates, corners 0 .. H / 0 .. W)
@@ -52,22 +48,22 @@ static_assert(MAX_M < 256, "four member counts ride in the bytes of one register
 typedef float F4 __attribute__((vector_size(16)));  // 16 bytes a load
 
 // the indicator: the same bit on every route
-static EV_BOTH inline int event_of(float v, float thr, int above) { return above ? (v >= thr ? 1 : 0) : (v <= thr ? 1 : 0); }
+static C2W_BOTH inline int event_of(float v, float thr, int above) { return above ? (v >= thr ? 1 : 0) : (v <= thr ? 1 : 0); }
 
-#ifdef EV_HOST
+#ifdef C2W_CORE_HOST
 static inline void lds_inc(int* p) { ++*p; }
 static inline void lds_add(int* p, int a) { *p += a; }
 static inline void lds_add64(long long* p, long long a, int) { *p += a; }
 static inline void global_add(long long* p, long long a) { *p += a; }
 #else
-static EV_HD inline void lds_inc(int* p) { atomicAdd(p, 1); }
-static EV_HD inline void lds_add(int* p, int a) { atomicAdd(p, a); }
+static C2W_HD inline void lds_inc(int* p) { atomicAdd(p, 1); }
+static C2W_HD inline void lds_add(int* p, int a) { atomicAdd(p, a); }
 // every thread of the wave comes here: the wave adds first, one lane adds to LDS
-static EV_HD inline void lds_add64(long long* p, long long a, int tid) {
+static C2W_HD inline void lds_add64(long long* p, long long a, int tid) {
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
     if ((tid & 63) == 0 && a) atomicAdd((unsigned long long*)p, (unsigned long long)a);
 }
-static EV_HD inline void global_add(long long* p, long long a) { atomicAdd((unsigned long long*)p, (unsigned long long)a); }
+static C2W_HD inline void global_add(long long* p, long long a) { atomicAdd((unsigned long long*)p, (unsigned long long)a); }
 #endif
 
 // ================================================================================================================ the joint table
@@ -75,14 +71,14 @@ static EV_HD inline void global_add(long long* p, long long a) { atomicAdd((unsi
 constexpr int MAX_BINS = 2 * (MAX_M + 1);                  // (o, j) of one threshold
 constexpr int COUNT_LDS_INTS = MAX_K * MAX_BINS + 2;       // the bins, the valid cells, the invalid cells: 4168 bytes
 
-static EV_BOTH inline bool counts_supported(int hw, int M, int K) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= MAX_M && K >= 1 && K <= MAX_K; }
-static EV_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
-static EV_BOTH inline int chunk_begin(int c) { return c * CHUNK; }
-static EV_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
-static EV_BOTH inline int rounds(int hw, int c) { return (chunk_end(hw, c) - chunk_begin(c) + 4 * THREADS - 1) / (4 * THREADS); }
-static EV_BOTH inline int cell_of(int c, int it, int tid) { return chunk_begin(c) + (it * THREADS + tid) * 4; }
-static EV_BOTH inline int bins(int M) { return 2 * (M + 1); }
-static EV_BOTH inline int bin_of(int o, int j, int M) { return o * (M + 1) + j; }
+static C2W_BOTH inline bool counts_supported(int hw, int M, int K) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= MAX_M && K >= 1 && K <= MAX_K; }
+static C2W_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
+static C2W_BOTH inline int chunk_begin(int c) { return c * CHUNK; }
+static C2W_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
+static C2W_BOTH inline int rounds(int hw, int c) { return (chunk_end(hw, c) - chunk_begin(c) + 4 * THREADS - 1) / (4 * THREADS); }
+static C2W_BOTH inline int cell_of(int c, int it, int tid) { return chunk_begin(c) + (it * THREADS + tid) * 4; }
+static C2W_BOTH inline int bins(int M) { return 2 * (M + 1); }
+static C2W_BOTH inline int bin_of(int o, int j, int M) { return o * (M + 1) + j; }
 
 struct CView {
     const float* x;      // [M][T][F][hw]
@@ -97,11 +93,11 @@ struct CView {
     int* lds;  // COUNT_LDS_INTS
 };
 
-static EV_HD inline void c_zero(const CView& v, int tid) {
+static C2W_HD inline void c_zero(const CView& v, int tid) {
     for (int i = tid; i < COUNT_LDS_INTS; i += THREADS) v.lds[i] = 0;
 }
 
-static EV_HD inline void c_count(const CView& v, int tid) {
+static C2W_HD inline void c_count(const CView& v, int tid) {
     const int f = (int)(v.plane % v.F), nb = bins(v.M);
     float thr[MAX_K];
     int above = 0;
@@ -156,7 +152,7 @@ static EV_HD inline void c_count(const CView& v, int tid) {
 }
 
 // bin (0, 0) of threshold tid = the valid cells - the other bins
-static EV_HD inline void c_derive(const CView& v, int tid) {
+static C2W_HD inline void c_derive(const CView& v, int tid) {
     if (tid >= v.K) return;
     const int nb = bins(v.M);
     int rest = 0;
@@ -164,7 +160,7 @@ static EV_HD inline void c_derive(const CView& v, int tid) {
     v.lds[tid * nb] = v.lds[MAX_K * MAX_BINS] - rest;
 }
 
-static EV_HD inline void c_flush(const CView& v, int tid) {
+static C2W_HD inline void c_flush(const CView& v, int tid) {
     const int n = v.K * bins(v.M);
     for (int i = tid; i < n; i += THREADS)
         if (v.lds[i]) global_add(v.counts + v.plane * n + i, (long long)v.lds[i]);
@@ -194,29 +190,29 @@ static_assert(FSS_LDS_BYTES <= 80 * 1024, "two workgroups share a CU");
 static_assert(CNT_BYTES <= SAT32_BYTES, "the ensemble row's table is built over the member counts");
 static_assert(OFF_SATE % 16 == 0 && OFF_RED % 16 == 0, "aligned parts");
 
-static EV_BOTH inline bool radii_ok(const int* radii, int S) {
+static C2W_BOTH inline bool radii_ok(const int* radii, int S) {
     if (S < 1 || S > MAX_S) return false;
     for (int s = 0; s < S; ++s)
         if (radii[s] < 0 || radii[s] > MAX_R) return false;
     return true;
 }
-static EV_BOTH inline int max_radius(const int* radii, int S) {
+static C2W_BOTH inline int max_radius(const int* radii, int S) {
     int R = 0;
     for (int s = 0; s < S; ++s) R = radii[s] > R ? radii[s] : R;
     return R;
 }
 // (M (2r + 1)^2)^2 H W < 2^62: the largest entry fits an int64 with room for the adds
-static EV_BOTH inline bool fss_no_overflow(int H, int W, int M, int R) {
+static C2W_BOTH inline bool fss_no_overflow(int H, int W, int M, int R) {
     const long long n = (long long)M * (2 * R + 1) * (2 * R + 1);
     return n * n <= ((1LL << 62) - 1) / ((long long)H * W);
 }
-static EV_BOTH inline bool fss_supported(int H, int W, int M, int K, const int* radii, int S) {
+static C2W_BOTH inline bool fss_supported(int H, int W, int M, int K, const int* radii, int S) {
     if (H < 4 || W < 4 || W % 4 != 0 || (long long)H * W > (1LL << 20) || M < 1 || M > MAX_M || K < 1 || K > MAX_K) return false;
     return radii_ok(radii, S) && fss_no_overflow(H, W, M, max_radius(radii, S));
 }
 
-static EV_BOTH inline int tiles_y(int H) { return (H + TILE - 1) / TILE; }
-static EV_BOTH inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
+static C2W_BOTH inline int tiles_y(int H) { return (H + TILE - 1) / TILE; }
+static C2W_BOTH inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
 
 struct Radii {
     int r[MAX_S];
@@ -226,7 +222,7 @@ struct Radii {
 struct Geo {
     int ty0, tx0, th, tw, y0, x0, rh, rw;
 };
-static EV_BOTH inline Geo geo_of(int H, int W, int R, int tile) {
+static C2W_BOTH inline Geo geo_of(int H, int W, int R, int tile) {
     Geo g;
     const int Rx = (R + 3) / 4 * 4;
     g.ty0 = tile / tiles_x(W) * TILE, g.tx0 = tile % tiles_x(W) * TILE;
@@ -250,14 +246,14 @@ struct FView {
     unsigned char* lds;  // FSS_LDS_BYTES
 };
 
-static EV_HD inline unsigned short* sat0_of(const FView& v) { return (unsigned short*)(v.lds + OFF_SAT0); }
-static EV_HD inline unsigned short* satm_of(const FView& v) { return (unsigned short*)(v.lds + OFF_SATM); }
-static EV_HD inline unsigned* cnt_of(const FView& v) { return (unsigned*)(v.lds + OFF_CNT); }
-static EV_HD inline unsigned* sate_of(const FView& v) { return (unsigned*)(v.lds + OFF_SATE); }
-static EV_HD inline long long* red_of(const FView& v) { return (long long*)(v.lds + OFF_RED); }
+static C2W_HD inline unsigned short* sat0_of(const FView& v) { return (unsigned short*)(v.lds + OFF_SAT0); }
+static C2W_HD inline unsigned short* satm_of(const FView& v) { return (unsigned short*)(v.lds + OFF_SATM); }
+static C2W_HD inline unsigned* cnt_of(const FView& v) { return (unsigned*)(v.lds + OFF_CNT); }
+static C2W_HD inline unsigned* sate_of(const FView& v) { return (unsigned*)(v.lds + OFF_SATE); }
+static C2W_HD inline long long* red_of(const FView& v) { return (long long*)(v.lds + OFF_RED); }
 
 // the zero row and column of the two 16-bit tables, the member counts and the sums
-static EV_HD inline void f_zero(const FView& v, int tid) {
+static C2W_HD inline void f_zero(const FView& v, int tid) {
     unsigned short *a = sat0_of(v), *b = satm_of(v);
     unsigned* cnt = cnt_of(v);
     for (int i = tid; i < RS; i += THREADS) {
@@ -269,7 +265,7 @@ static EV_HD inline void f_zero(const FView& v, int tid) {
 }
 
 // row d's indicators over the region: d = 0 the truth into its table; d = 1 .. M a member into the member's table and onto the counts
-static EV_HD inline void f_load(const FView& v, const Geo& g, int tid, int d) {
+static C2W_HD inline void f_load(const FView& v, const Geo& g, int tid, int d) {
     const int f = (int)(v.plane % v.F), above = v.dir[f * v.K + v.k] != 0 ? 1 : 0;
     const float thr = v.thr[f * v.K + v.k];
     const long long hw = (long long)v.H * v.W;
@@ -296,7 +292,7 @@ static EV_HD inline void f_load(const FView& v, const Geo& g, int tid, int d) {
 struct EnsThread {
     unsigned w[ENS_WORDS];
 };
-static EV_HD inline void f_ensemble_take(const FView& v, const Geo& g, int tid, EnsThread& th) {
+static C2W_HD inline void f_ensemble_take(const FView& v, const Geo& g, int tid, EnsThread& th) {
     const unsigned* cnt = cnt_of(v);
     const int qw = g.rw / 4;
 #pragma unroll
@@ -305,7 +301,7 @@ static EV_HD inline void f_ensemble_take(const FView& v, const Geo& g, int tid, 
         th.w[n] = q < g.rh * qw ? cnt[q / qw * CNT_WORDS + q % qw] : 0u;
     }
 }
-static EV_HD inline void f_ensemble_put(const FView& v, const Geo& g, int tid, const EnsThread& th) {
+static C2W_HD inline void f_ensemble_put(const FView& v, const Geo& g, int tid, const EnsThread& th) {
     unsigned* sat = sate_of(v);
     const int qw = g.rw / 4;
     for (int i = tid; i < RS; i += THREADS) sat[i] = 0, sat[i * RS] = 0;  // cells (i + 1, j + 1) below never touch row 0 or column 0
@@ -321,7 +317,7 @@ static EV_HD inline void f_ensemble_put(const FView& v, const Geo& g, int tid, c
 
 // the two scans that turn the staged row into its summed-area table: thread i owns region row i, then thread j region column j
 template <typename E>
-static EV_HD inline void f_scan_rows(E* sat, const Geo& g, int tid) {
+static C2W_HD inline void f_scan_rows(E* sat, const Geo& g, int tid) {
     for (int i = tid; i < g.rh; i += THREADS) {
         E run = 0, a[4];
         E* row = sat + (i + 1) * RS + 1;
@@ -334,7 +330,7 @@ static EV_HD inline void f_scan_rows(E* sat, const Geo& g, int tid) {
     }
 }
 template <typename E>
-static EV_HD inline void f_scan_cols(E* sat, const Geo& g, int tid) {
+static C2W_HD inline void f_scan_cols(E* sat, const Geo& g, int tid) {
     for (int j = tid; j < g.rw; j += THREADS) {
         E run = 0, a[4];
         E* col = sat + RS + j + 1;
@@ -351,7 +347,7 @@ static EV_HD inline void f_scan_cols(E* sat, const Geo& g, int tid) {
 
 // the window sum of radius r centred on region cell (ry, rx): four reads at corners clipped to the region, which is the domain's clip
 template <typename E>
-static EV_HD inline long long window_of(const E* sat, const Geo& g, int ry, int rx, int r, int d, int s) {
+static C2W_HD inline long long window_of(const E* sat, const Geo& g, int ry, int rx, int r, int d, int s) {
     const int a0 = ry - r > 0 ? ry - r : 0, a1 = ry + r + 1 < g.rh ? ry + r + 1 : g.rh;
     const int b0 = rx - r > 0 ? rx - r : 0, b1 = rx + r + 1 < g.rw ? rx + r + 1 : g.rw;
     EV_VISIT_CORNER(d, s, g.y0 + a0, g.x0 + b0);
@@ -364,7 +360,7 @@ static EV_HD inline long long window_of(const E* sat, const Geo& g, int ry, int 
 
 // (sum n_d^2, sum n_d n_0) of row d over the tile's cells at every radius, into the workgroup's sums
 template <typename E>
-static EV_HD inline void f_sums(const FView& v, const Geo& g, int tid, const E* sat, int d) {
+static C2W_HD inline void f_sums(const FView& v, const Geo& g, int tid, const E* sat, int d) {
     const unsigned short* sat0 = sat0_of(v);
     long long pp[MAX_S], po[MAX_S];
 #pragma unroll
@@ -389,7 +385,7 @@ static EV_HD inline void f_sums(const FView& v, const Geo& g, int tid, const E* 
 }
 
 // thread e = 2 s + column adds the workgroup's sum of row d to the output and clears it for the next row
-static EV_HD inline void f_flush(const FView& v, int tid, int d) {
+static C2W_HD inline void f_flush(const FView& v, int tid, int d) {
     if (tid >= 2 * v.S) return;
     long long* red = red_of(v);
     const int s = tid / 2, col = tid % 2;

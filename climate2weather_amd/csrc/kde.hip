@@ -5,10 +5,6 @@
 // pit_count_kernel reads every field once and bins in LDS.  kde_core.h has the index maps and the arithmetic; this file is the
 // workgroups around them.  No float atomics, no sum whose order depends on the launch.
 #include "launch.h"
-
-#define KDE_HD __device__ __attribute__((always_inline))
-#define KDE_BOTH __host__ __device__ __attribute__((always_inline))
-#define ORDERED_SUM_HD KDE_HD
 #include "kde_core.h"
 
 namespace {
@@ -80,12 +76,12 @@ extern "C" long long c2w_kde_scratch_bytes(long long D, long long n, int N) {
 extern "C" int c2w_kde_partial(const float* x, const float* y, const float* offsets, const float* pivot, const double* h, double* scratch,
                                unsigned long long scratch_bytes, long long n_rep, int T, int F, int hw, int N, void* stream) {
     if (!kde::supported(hw, N)) return C2W_ERR_UNSUPPORTED;
-    if (n_rep < 0 || T < 1 || F < 1 || (n_rep > 0 && !x) || !offsets || !pivot || !h || !scratch || (((uintptr_t)x | (uintptr_t)y) & 15) != 0 ||
-        (((uintptr_t)h | (uintptr_t)scratch) & 7) != 0 || (((uintptr_t)offsets | (uintptr_t)pivot) & 3) != 0)
+    if (n_rep < 0 || T < 1 || F < 1 || (n_rep > 0 && !x) || !offsets || !pivot || !h || !scratch || !c2w_aligned(16, x, y) ||
+        !c2w_aligned(8, h, scratch) || !c2w_aligned(4, offsets, pivot))
         return C2W_ERR_BAD_ARG;
     const long long n_x = n_rep * F, D = n_x + (y ? F : 0), n = (long long)T * hw, nc = kde::chunks(n), grid = D * nc;
     if (D == 0) return 0;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     if (scratch_bytes < (unsigned long long)c2w_kde_scratch_bytes(D, n, N)) return C2W_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     switch (kde::points_per_thread(N)) {
@@ -98,10 +94,10 @@ extern "C" int c2w_kde_partial(const float* x, const float* y, const float* offs
 
 extern "C" int c2w_kde_fold(const double* scratch, const double* h, double* dens, long long D, long long n, int N, void* stream) {
     if (N < 1 || N > kde::MAX_N) return C2W_ERR_UNSUPPORTED;
-    if (D < 0 || n < 1 || !scratch || !h || !dens || (((uintptr_t)h | (uintptr_t)scratch | (uintptr_t)dens) & 7) != 0) return C2W_ERR_BAD_ARG;
+    if (D < 0 || n < 1 || !scratch || !h || !dens || !c2w_aligned(8, h, scratch, dens)) return C2W_ERR_BAD_ARG;
     const int per_set = (N + THREADS - 1) / THREADS;
     if (D == 0) return 0;
-    if (D * per_set > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(D * per_set)) return C2W_ERR_BAD_SHAPE;
     kde_fold_kernel<<<(unsigned)(D * per_set), THREADS, 0, (hipStream_t)stream>>>(scratch, h, dens, n, N, per_set);
     return (int)hipGetLastError();
 }
@@ -109,7 +105,7 @@ extern "C" int c2w_kde_fold(const double* scratch, const double* h, double* dens
 extern "C" int c2w_kde_eval(const float* x, const float* y, const float* offsets, const float* pivot, const double* h, double* scratch,
                             unsigned long long scratch_bytes, double* dens, long long n_rep, int T, int F, int hw, int N, void* stream) {
     if (!kde::supported(hw, N)) return C2W_ERR_UNSUPPORTED;
-    if (!dens || ((uintptr_t)dens & 7) != 0) return C2W_ERR_BAD_ARG;
+    if (!dens || !c2w_aligned(8, dens)) return C2W_ERR_BAD_ARG;
     if (int rc = c2w_kde_partial(x, y, offsets, pivot, h, scratch, scratch_bytes, n_rep, T, F, hw, N, stream)) return rc;
     return c2w_kde_fold(scratch, h, dens, n_rep * F + (y ? F : 0), (long long)T * hw, N, stream);
 }
@@ -118,12 +114,12 @@ extern "C" int c2w_pit_supported(int hw, int M) { return kde::pit_supported(hw, 
 
 extern "C" int c2w_pit_counts(const float* x, const float* y, long long* counts, int M, int T, int F, int hw, void* stream) {
     if (!kde::pit_supported(hw, M)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !counts || T < 1 || F < 1 || (((uintptr_t)x | (uintptr_t)y) & 15) != 0 || ((uintptr_t)counts & 7) != 0) return C2W_ERR_BAD_ARG;
+    if (!x || !y || !counts || T < 1 || F < 1 || !c2w_aligned(16, x, y) || !c2w_aligned(8, counts)) return C2W_ERR_BAD_ARG;
     // eight workgroups a CU at most, a whole number of times per variable; the counts are integers, so the grid changes no result
     long long per_var = (long long)c2w_cu_count() * 8 / F;
     per_var = per_var < 1 ? 1 : per_var > T ? T : per_var;
     const long long grid = per_var * F;
-    if (grid > 0x7fffffffLL || ((long long)T + per_var - 1) / per_var * hw > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;  // an LDS bin is an int
+    if (!c2w_grid_fits(grid) || ((long long)T + per_var - 1) / per_var * hw > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;  // an LDS bin is an int
     hipStream_t st = (hipStream_t)stream;
     HIP_CHECK_RET(hipMemsetAsync(counts, 0, (size_t)F * (M + 1) * sizeof(long long), st));
     pit_count_kernel<<<(unsigned)grid, THREADS, 0, st>>>(x, y, counts, M, T, F, hw);

@@ -1,5 +1,5 @@
 // Ensemble marginals: the index maps and the arithmetic of kde.hip (Gaussian kernel density estimates and the rank histogram), written
-// as barrier-separated phases over "thread tid of a workgroup", as swd_core.h is.  Compiled for the host (KDE_HD empty) the same phases
+// as barrier-separated phases over "thread tid of a workgroup", as swd_core.h is.  Compiled for the host (core_side.h) the same phases
 // run one thread after the other over a record per thread: tests/host_kde_main.cpp checks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_kde_eval, c2w_pit_counts).  A data set is one (member, variable) or (truth, variable) over all T times and
@@ -29,12 +29,7 @@
 #ifndef C2W_KDE_CORE_H
 #define C2W_KDE_CORE_H
 
-#ifndef KDE_HD
-#define KDE_HD
-#define KDE_BOTH
-#define KDE_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 #include "ordered_sum.h"
 
 namespace kde {
@@ -57,32 +52,32 @@ constexpr int PIT_HIST = PIT_COPIES * (PIT_MAX_M + 1);
 constexpr double SQRT_HALF_LOG2E = 0.84932180028801904272;  // sqrt(log2(e) / 2)
 constexpr double SQRT_2PI = 2.50662827463100050242;
 
-static KDE_BOTH inline bool supported(int hw, int N) { return hw >= 4 && hw % 4 == 0 && N >= 1 && N <= MAX_N; }
-static KDE_BOTH inline bool pit_supported(int hw, int M) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= PIT_MAX_M; }
+static C2W_BOTH inline bool supported(int hw, int N) { return hw >= 4 && hw % 4 == 0 && N >= 1 && N <= MAX_N; }
+static C2W_BOTH inline bool pit_supported(int hw, int M) { return hw >= 4 && hw % 4 == 0 && M >= 1 && M <= PIT_MAX_M; }
 
 // ---------------------------------------------------------------------------------------------------------------- maps
 
 // values per chunk: n / 64 rounded up to whole tiles, one tile at least; chunk c owns values c len .. min(n, (c + 1) len) - 1
-static KDE_BOTH inline long long chunk_len(long long n) {
+static C2W_BOTH inline long long chunk_len(long long n) {
     const long long per = (n + MAX_CHUNKS - 1) / MAX_CHUNKS;
     const long long len = (per + TILE - 1) / TILE * TILE;
     return len < TILE ? TILE : len;
 }
-static KDE_BOTH inline long long chunks(long long n) { return (n + chunk_len(n) - 1) / chunk_len(n); }
-static KDE_BOTH inline long long chunk_begin(long long n, long long c) { return c * chunk_len(n); }
-static KDE_BOTH inline long long chunk_end(long long n, long long c) {
+static C2W_BOTH inline long long chunks(long long n) { return (n + chunk_len(n) - 1) / chunk_len(n); }
+static C2W_BOTH inline long long chunk_begin(long long n, long long c) { return c * chunk_len(n); }
+static C2W_BOTH inline long long chunk_end(long long n, long long c) {
     const long long e = (c + 1) * chunk_len(n);
     return e < n ? e : n;
 }
 // the float offset of value i of a data set from the data set's first value: time i / hw, cell i % hw; times lie F hw apart
-static KDE_BOTH inline long long value_offset(long long i, int F, int hw) { return (i / hw) * ((long long)F * hw) + i % hw; }
+static C2W_BOTH inline long long value_offset(long long i, int F, int hw) { return (i / hw) * ((long long)F * hw) + i % hw; }
 // the grid point register r of thread tid holds; points past N are computed from point N - 1 and dropped
-static KDE_BOTH inline int point_of(int tid, int r) { return r * THREADS + tid; }
-static KDE_BOTH inline int points_per_thread(int N) { return (N + THREADS - 1) / THREADS; }
+static C2W_BOTH inline int point_of(int tid, int r) { return r * THREADS + tid; }
+static C2W_BOTH inline int points_per_thread(int N) { return (N + THREADS - 1) / THREADS; }
 // rank histogram: workgroup b of G owns variable b % F and times b / F + k (G / F); a cell's bin is its rank, in copy tid % 16
-static KDE_BOTH inline int pit_var(long long b, int F) { return (int)(b % F); }
-static KDE_BOTH inline long long pit_first_t(long long b, int F) { return b / F; }
-static KDE_BOTH inline int pit_slot(int tid, int r, int M) { return (tid % PIT_COPIES) * (M + 1) + r; }
+static C2W_BOTH inline int pit_var(long long b, int F) { return (int)(b % F); }
+static C2W_BOTH inline long long pit_first_t(long long b, int F) { return b / F; }
+static C2W_BOTH inline int pit_slot(int tid, int r, int M) { return (tid % PIT_COPIES) * (M + 1) + r; }
 
 // ---------------------------------------------------------------------------------------------------------------- density: phases
 
@@ -110,10 +105,10 @@ struct KThread {
     int has, bad;
 };
 
-static KDE_BOTH inline int var_of(const KView& v) { return (int)(v.ds < v.n_x ? v.ds % v.F : v.ds - v.n_x); }
+static C2W_BOTH inline int var_of(const KView& v) { return (int)(v.ds < v.n_x ? v.ds % v.F : v.ds - v.n_x); }
 
 template <int P>
-static KDE_HD inline void k_init(const KView& v, KThread<P>& th, int tid) {
+static C2W_HD inline void k_init(const KView& v, KThread<P>& th, int tid) {
     const int f = var_of(v);
     th.base = v.ds < v.n_x ? v.x + ((v.ds / v.F) * v.T * v.F + f) * (long long)v.hw : v.y + (long long)f * v.hw;
     th.n = (long long)v.T * v.hw;
@@ -131,7 +126,7 @@ static KDE_HD inline void k_init(const KView& v, KThread<P>& th, int tid) {
 
 // the thread's 16 bytes of tile `tile` of the chunk (hw % 4 == 0: four neighbouring values share their time)
 template <int P>
-static KDE_HD inline void k_fetch(const KView& v, KThread<P>& th, int tid, long long tile) {
+static C2W_HD inline void k_fetch(const KView& v, KThread<P>& th, int tid, long long tile) {
     const long long i = th.begin + tile * TILE + 4 * tid;
     th.has = i < th.end;
     if (th.has) th.raw = *(const float4*)(th.base + value_offset(i, v.F, v.hw));
@@ -139,7 +134,7 @@ static KDE_HD inline void k_fetch(const KView& v, KThread<P>& th, int tid, long 
 
 // x - c: one rounding, on the loaded value, before anything else
 template <int P>
-static KDE_HD inline void k_stash(const KView& v, KThread<P>& th, int tid) {
+static C2W_HD inline void k_stash(const KView& v, KThread<P>& th, int tid) {
     if (!th.has) return;
     const float4 q = th.raw;
     const float4 o = float4{q.x - th.c, q.y - th.c, q.z - th.c, q.w - th.c};
@@ -147,14 +142,14 @@ static KDE_HD inline void k_stash(const KView& v, KThread<P>& th, int tid) {
     v.lds[tid] = o;
 }
 
-#ifdef KDE_HOST
+#ifdef C2W_CORE_HOST
 static inline float exp2_neg(float s) { return exp2f(-s); }
 #else
-static KDE_HD inline float exp2_neg(float s) { return __builtin_amdgcn_exp2f(-s); }  // v_exp_f32 with the sign as a source modifier
+static C2W_HD inline float exp2_neg(float s) { return __builtin_amdgcn_exp2f(-s); }  // v_exp_f32 with the sign as a source modifier
 #endif
 
 template <int P>
-static KDE_HD inline void k_pair(KThread<P>& th, float xo) {
+static C2W_HD inline void k_pair(KThread<P>& th, float xo) {
 #pragma unroll
     for (int r = 0; r < P; ++r) {
         const float t = __builtin_fmaf(-xo, th.k, th.gk[r]);
@@ -163,14 +158,14 @@ static KDE_HD inline void k_pair(KThread<P>& th, float xo) {
 }
 
 template <int P>
-static KDE_HD inline void k_fold(KThread<P>& th) {
+static C2W_HD inline void k_fold(KThread<P>& th) {
 #pragma unroll
     for (int r = 0; r < P; ++r) th.tot[r] += (double)th.acc[r], th.acc[r] = 0.f;
 }
 
 // the `count` values of the staged tile (a multiple of 4), in value order; every thread reads the same 16 bytes at a time
 template <int P>
-static KDE_HD inline void k_compute(const KView& v, KThread<P>& th, int count) {
+static C2W_HD inline void k_compute(const KView& v, KThread<P>& th, int count) {
     for (int first = 0; first < count; first += FOLD) {
         const int stop = first + FOLD < count ? first + FOLD : count;
 #pragma unroll 2
@@ -183,15 +178,15 @@ static KDE_HD inline void k_compute(const KView& v, KThread<P>& th, int count) {
 }
 
 template <int P>
-static KDE_HD inline long long k_tiles(const KThread<P>& th) { return (th.end - th.begin + TILE - 1) / TILE; }
+static C2W_HD inline long long k_tiles(const KThread<P>& th) { return (th.end - th.begin + TILE - 1) / TILE; }
 template <int P>
-static KDE_HD inline int k_count(const KThread<P>& th, long long tile) {
+static C2W_HD inline int k_count(const KThread<P>& th, long long tile) {
     const long long left = th.end - th.begin - tile * TILE;
     return (int)(left < TILE ? left : TILE);
 }
 
 template <int P>
-static KDE_HD inline void k_store(const KView& v, const KThread<P>& th, int tid, int bad) {
+static C2W_HD inline void k_store(const KView& v, const KThread<P>& th, int tid, int bad) {
     double* row = v.partial + (v.ds * chunks(th.n) + v.chunk) * v.N;
 #pragma unroll
     for (int r = 0; r < P; ++r)
@@ -199,7 +194,7 @@ static KDE_HD inline void k_store(const KView& v, const KThread<P>& th, int tid,
 }
 
 // dens[ds][j]: the chunks in index order, then the normalisation, all in double
-static KDE_HD inline void f_fold(const double* partial, const double* h, double* dens, long long ds, int j, long long n, int N) {
+static C2W_HD inline void f_fold(const double* partial, const double* h, double* dens, long long ds, int j, long long n, int N) {
     const long long nc = chunks(n);
     const double s = ordered_sum::fold_strided(partial + ds * nc * N + j, nc, N);  // fold_parts at entry ds N + j, undivided
     dens[ds * N + j] = s != s ? (double)__builtin_nanf("") : s * (1.0 / ((double)n * h[ds] * SQRT_2PI));
@@ -216,19 +211,19 @@ struct PView {
     int* hist;  // PIT_HIST
 };
 
-#ifdef KDE_HOST
+#ifdef C2W_CORE_HOST
 static inline void lds_inc(int* p) { ++*p; }
 static inline void global_add(long long* p, long long a) { *p += a; }
 #else
-static KDE_HD inline void lds_inc(int* p) { atomicAdd(p, 1); }
-static KDE_HD inline void global_add(long long* p, long long a) { atomicAdd((unsigned long long*)p, (unsigned long long)a); }
+static C2W_HD inline void lds_inc(int* p) { atomicAdd(p, 1); }
+static C2W_HD inline void global_add(long long* p, long long a) { atomicAdd((unsigned long long*)p, (unsigned long long)a); }
 #endif
 
-static KDE_HD inline void pit_zero(const PView& v, int tid) {
+static C2W_HD inline void pit_zero(const PView& v, int tid) {
     for (int i = tid; i < PIT_COPIES * (v.M + 1); i += THREADS) v.hist[i] = 0;
 }
 
-static KDE_HD inline void pit_count(const PView& v, int tid) {
+static C2W_HD inline void pit_count(const PView& v, int tid) {
     const int f = pit_var(v.block, v.F), quads = v.hw / 4;
     const long long plane = (long long)v.F * v.hw, member = (long long)v.T * plane;
     for (long long t = pit_first_t(v.block, v.F); t < v.T; t += v.grid / v.F)
@@ -246,7 +241,7 @@ static KDE_HD inline void pit_count(const PView& v, int tid) {
         }
 }
 
-static KDE_HD inline void pit_flush(const PView& v, int tid) {
+static C2W_HD inline void pit_flush(const PView& v, int tid) {
     if (tid > v.M) return;
     long long s = 0;
     for (int c = 0; c < PIT_COPIES; ++c) s += v.hist[c * (v.M + 1) + tid];

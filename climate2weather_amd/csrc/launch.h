@@ -1,15 +1,26 @@
-// The launch layer: the three host-side chores every launcher of libc2w_hip.so shares ("Launch layer").  Host code only.
+// The launch layer: the host-side chores every launcher of libc2w_hip.so shares ("Launch layer").  Host code only.
 //   c2w_lds_optin<kernel>(bytes)   the dynamic-LDS opt-in a kernel needs before a launch with more than 64 KB, once per device
 //   c2w_by_dtype / c2w_by_dtype16  the C2W_DTYPE_* tag of the C ABI -> the storage type a launcher template is instantiated with
 //   c2w_cu_count()                 the compute units of the current device, where dispatch arithmetic means "one workgroup per CU"
+//   c2w_aligned(bytes, pointers..) the argument check of the metric launchers: every pointer a multiple of `bytes`
+//   c2w_grid_fits(workgroups)      and: the one-dimensional grid is within what a launch takes
 // A new kernel uses these; nothing else in csrc/ calls hipFuncSetAttribute, compares a dtype tag to pick a template, or spells the CU
 // count as a number.
 #pragma once
 #include <atomic>
+#include <cstdint>
 #include "common.h"
 #include "c2w_hip.h"
 
 constexpr int C2W_MAX_DEVICES = 64;  // devices with a table slot; a device index beyond it is served uncached
+
+// `bytes` a power of two.  A null pointer counts as aligned: whether an argument may be null is the entry point's own check.
+template <typename... P>
+bool c2w_aligned(uintptr_t bytes, const P*... p) {
+    return ((uintptr_t(0) | ... | (uintptr_t)p) & (bytes - 1)) == 0;
+}
+
+constexpr bool c2w_grid_fits(long long workgroups) { return workgroups <= 0x7fffffffLL; }
 
 // Raises hipFuncAttributeMaxDynamicSharedMemorySize of `Kernel` to at least `bytes` on the current device; returns the HIP error (0: ok).
 // The runtime keeps the attribute per device, so the table of what was granted is per device too (per kernel: a static of this template).

@@ -1,11 +1,9 @@
 // The second launch of a fixed-order sum (ordered_sum.h, step 5), for every metric whose planes have several chunks or tiles:
 // partial [outer][parts][inner] -> out [outer][inner], the parts added in index order, each entry written through the POLICY the metric
 // names (ordered_sum::nan_if_nan or nan_if_not_finite).  INNER is the inner width where it is a constant of the metric (the division
-// is then a shift), 0 for `inner` at run time.  Included before a *_core.h: ordered_sum.h gets the device qualifiers here.
+// is then a shift), 0 for `inner` at run time.
 #pragma once
 #include "launch.h"
-
-#define ORDERED_SUM_HD __device__ __attribute__((always_inline))
 #include "ordered_sum.h"
 
 namespace {

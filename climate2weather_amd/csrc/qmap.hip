@@ -4,9 +4,6 @@
 // block of adjacent cells in LDS once and maps its group's rows, 16 bytes a load, each value bisected in LDS and mapped in float64.
 // qmap_core.h has the maps and the arithmetic; this file is the workgroups around them.  No atomics, nothing read back by the host.
 #include "launch.h"
-
-#define QMAP_HD __device__ __attribute__((always_inline))
-#define QMAP_BOTH __host__ __device__ __attribute__((always_inline))
 #include "qmap_core.h"
 
 namespace {
@@ -76,12 +73,12 @@ extern "C" int c2w_qmap_nodes(const float* x, const int* tidx, const int* goff, 
                               int c0, int c1, void* stream) {
     if (!qmap::supported(hw, K, max_len)) return C2W_ERR_UNSUPPORTED;
     if (!x || !tidx || !goff || !levels || !q || !n_valid || n_rep < 1 || T < 1 || F < 1 || G < 1 || Tu < 0 || Tu > T || max_len > Tu || c0 < 0 ||
-        c1 > hw || c0 >= c1 || ((uintptr_t)x & 3) != 0 || (((uintptr_t)q | (uintptr_t)n_valid | (uintptr_t)levels) & 7) != 0)
+        c1 > hw || c0 >= c1 || !c2w_aligned(4, x) || !c2w_aligned(8, q, n_valid, levels))
         return C2W_ERR_BAD_ARG;
     const long long rows = n_rep * F, need = Tu > 0 ? qmap::scratch_bytes(rows, c1 - c0, Tu) : 0;
-    if (need > 0 && (!scratch || ((uintptr_t)scratch & 3) != 0 || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
+    if (need > 0 && (!scratch || !c2w_aligned(4, scratch) || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
     const long long series = rows * (c1 - c0) * G;
-    if (rows > 65535 || tiles(c1 - c0) > 65535 || series > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (rows > 65535 || tiles(c1 - c0) > 65535 || !c2w_grid_fits(series)) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     if (Tu > 0) {
         const dim3 grid((unsigned)tiles(Tu), (unsigned)tiles(c1 - c0), (unsigned)rows);
@@ -99,7 +96,7 @@ extern "C" int c2w_qmap_apply(const float* x, float* out, const double* xq, cons
                               int F, int hw, int Tu, int G, int K, int max_len, void* stream) {
     if (!qmap::supported(hw, K, max_len)) return C2W_ERR_UNSUPPORTED;
     if (!x || !out || !xq || !yq || !tidx || !goff || n_rep < 1 || T < 1 || F < 1 || G < 1 || Tu < 0 || Tu > T || max_len > Tu ||
-        (((uintptr_t)x | (uintptr_t)out) & 15) != 0 || (((uintptr_t)xq | (uintptr_t)yq) & 7) != 0)
+        !c2w_aligned(16, x, out) || !c2w_aligned(8, xq, yq))
         return C2W_ERR_BAD_ARG;
     if (Tu == 0) return 0;
     const long long blocks = (long long)G * F * cell_blocks(hw, K);

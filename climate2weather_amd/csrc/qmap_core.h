@@ -1,5 +1,5 @@
 // Quantile mapping per cell: the index maps and the arithmetic of qmap.hip, written as barrier-separated phases over "thread tid of a
-// workgroup", as wind_core.h and temporal_core.h are.  Compiled for the host (QMAP_HD empty) the same phases run one thread after the
+// workgroup", as wind_core.h and temporal_core.h are.  Compiled for the host (core_side.h) the same phases run one thread after the
 // other: tests/host_qmap_main.cpp checks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_qmap_nodes, c2w_qmap_apply).  A series is the values of one variable at one cell over the times of one
@@ -30,12 +30,7 @@
 #ifndef C2W_QMAP_CORE_H
 #define C2W_QMAP_CORE_H
 
-#ifndef QMAP_HD
-#define QMAP_HD
-#define QMAP_BOTH
-#define QMAP_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 
 #if defined(__clang__)
 #define QMAP_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -47,16 +42,6 @@
 #define QMAP_VISIT(index)
 #endif
 
-#ifndef QNT_HD  // quantile_core.h for the same side as this file
-#ifdef QMAP_HOST
-#define QNT_HD
-#define QNT_BOTH
-#define QNT_HOST 1
-#else
-#define QNT_HD QMAP_HD
-#define QNT_BOTH QMAP_BOTH
-#endif
-#endif
 #include "quantile_core.h"
 
 namespace qmap {
@@ -76,42 +61,42 @@ static_assert(THREADS % TILE == 0 && APPLY_THREADS % (MAX_CELLS / 4) == 0, "whol
 
 typedef float F4 __attribute__((vector_size(16)));  // 16 bytes a load
 
-static QMAP_BOTH inline bool supported(int hw, int K, int max_len) {
+static C2W_BOTH inline bool supported(int hw, int K, int max_len) {
     return hw >= 4 && hw % 4 == 0 && K >= 2 && K <= MAX_K && max_len >= 0 && max_len <= MAX_N;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- maps
 
-static QMAP_BOTH inline int padded(int n) {
+static C2W_BOTH inline int padded(int n) {
     int N = 2;
     while (N < n) N <<= 1;
     return N;
 }
-static QMAP_BOTH inline int sort_threads(int N) { return N <= 2048 ? 256 : 1024; }
-static QMAP_BOTH inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-static QMAP_BOTH inline int tiles(int n) { return (n + TILE - 1) / TILE; }
+static C2W_BOTH inline int sort_threads(int N) { return N <= 2048 ? 256 : 1024; }
+static C2W_BOTH inline int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+static C2W_BOTH inline int tiles(int n) { return (n + TILE - 1) / TILE; }
 // bytes of the series-major scratch of a block of `cells` cells: [rows][cells][Tu] fp32
-static QMAP_BOTH inline long long scratch_bytes(long long rows, int cells, int Tu) { return (rows * cells * Tu * 4 + 15) / 16 * 16; }
+static C2W_BOTH inline long long scratch_bytes(long long rows, int cells, int Tu) { return (rows * cells * Tu * 4 + 15) / 16 * 16; }
 // doubles of one table row in LDS, odd
-static QMAP_BOTH inline int table_ld(int K) { return K | 1; }
+static C2W_BOTH inline int table_ld(int K) { return K | 1; }
 // cells of an apply workgroup: the most of 64, 32 .. 4 whose two tables fit APPLY_LDS
-static QMAP_BOTH inline int cells_per_block(int K) {
+static C2W_BOTH inline int cells_per_block(int K) {
     int C = MAX_CELLS;
     while (C > 4 && 2 * C * table_ld(K) * 8 > APPLY_LDS) C >>= 1;
     return C;
 }
-static QMAP_BOTH inline int apply_lds_bytes(int K) { return 2 * cells_per_block(K) * table_ld(K) * 8; }
-static QMAP_BOTH inline int cell_blocks(int hw, int K) { return (hw + cells_per_block(K) - 1) / cells_per_block(K); }
+static C2W_BOTH inline int apply_lds_bytes(int K) { return 2 * cells_per_block(K) * table_ld(K) * 8; }
+static C2W_BOTH inline int cell_blocks(int hw, int K) { return (hw + cells_per_block(K) - 1) / cells_per_block(K); }
 // rows one pass of an apply workgroup covers
-static QMAP_BOTH inline int rows_per_pass(int K) { return APPLY_THREADS / (cells_per_block(K) / 4); }
+static C2W_BOTH inline int rows_per_pass(int K) { return APPLY_THREADS / (cells_per_block(K) / 4); }
 // slabs per (group, variable, cell block): WG_PER_CU workgroups a compute unit, a slab no shorter than one round of LOADS passes
-static QMAP_BOTH inline int slab_count(long long blocks, long long max_rows, int K, int cus) {
+static C2W_BOTH inline int slab_count(long long blocks, long long max_rows, int K, int cus) {
     long long s = (long long)cus * WG_PER_CU / (blocks < 1 ? 1 : blocks);
     const long long most = (max_rows + LOADS * rows_per_pass(K) - 1) / (LOADS * rows_per_pass(K));
     s = s > most ? most : s;
     return (int)(s < 1 ? 1 : s);
 }
-static QMAP_BOTH inline long long slab_begin(long long rows, int slabs, int s) { return rows * s / slabs; }
+static C2W_BOTH inline long long slab_begin(long long rows, int slabs, int s) { return rows * s / slabs; }
 
 // ---------------------------------------------------------------------------------------------------------------- gather: phases
 
@@ -125,7 +110,7 @@ struct GView {
     float* tile;  // LDS: TILE * TILE_LD
 };
 
-static QMAP_HD inline void g_load(const GView& v, int tid) {
+static C2W_HD inline void g_load(const GView& v, int tid) {
     const int col = tid % TILE, c = v.c0 + v.ctile * TILE + col;
     const long long rep = v.row / v.F, f = v.row % v.F;
     for (int i = tid / TILE; i < TILE; i += THREADS / TILE) {
@@ -136,7 +121,7 @@ static QMAP_HD inline void g_load(const GView& v, int tid) {
     }
 }
 
-static QMAP_HD inline void g_store(const GView& v, int tid) {
+static C2W_HD inline void g_store(const GView& v, int tid) {
     const int col = tid % TILE, p = v.ptile * TILE + col;
     for (int j = tid / TILE; j < TILE; j += THREADS / TILE) {
         const int cl = v.ctile * TILE + j;
@@ -159,15 +144,15 @@ struct SView {
     unsigned* keys;  // LDS: padded(n)
 };
 
-static QMAP_HD inline int group_of(const SView& v) { return (int)(v.series % v.G); }
-static QMAP_HD inline int first_of(const SView& v) { return clampi(v.goff[group_of(v)], 0, v.Tu); }
+static C2W_HD inline int group_of(const SView& v) { return (int)(v.series % v.G); }
+static C2W_HD inline int first_of(const SView& v) { return clampi(v.goff[group_of(v)], 0, v.Tu); }
 // the series' length, never beyond the list or what the launch has LDS for
-static QMAP_HD inline int length_of(const SView& v) {
+static C2W_HD inline int length_of(const SView& v) {
     const int n = clampi(v.goff[group_of(v) + 1], 0, v.Tu) - first_of(v);
     return clampi(n, 0, v.max_len);
 }
 
-static QMAP_HD inline void s_load(const SView& v, int tid) {
+static C2W_HD inline void s_load(const SView& v, int tid) {
     const int n = length_of(v), N = padded(n);
     const float* s = v.scratch + (v.series / v.G) * v.Tu + first_of(v);
     for (int i = tid; i < N; i += v.nthr) {
@@ -181,7 +166,7 @@ static QMAP_HD inline void s_load(const SView& v, int tid) {
 }
 
 // one stage of the bitonic network: pairs (l, l | j), ascending where l & k == 0
-static QMAP_HD inline void s_stage(const SView& v, int tid, int k, int j) {
+static C2W_HD inline void s_stage(const SView& v, int tid, int k, int j) {
     const int N = padded(length_of(v));
     for (int i = tid; i < N / 2; i += v.nthr) {
         const int l = 2 * i - (i & (j - 1)), r = l | j;
@@ -191,7 +176,7 @@ static QMAP_HD inline void s_stage(const SView& v, int tid, int k, int j) {
 }
 
 // thread k < K: level k of the sorted series; thread 0 also the count
-static QMAP_HD inline void s_nodes(const SView& v, int tid) {
+static C2W_HD inline void s_nodes(const SView& v, int tid) {
     if (tid >= v.K) return;
     const int n = length_of(v);
     int lo = 0, hi = n;  // the first position that holds TOP: the non-NaN values are below it
@@ -228,7 +213,7 @@ struct AView {
     double* lds;  // 2 * cells_per_block(K) * table_ld(K)
 };
 
-static QMAP_HD inline void a_stage(const AView& v, int tid) {
+static C2W_HD inline void a_stage(const AView& v, int tid) {
     const int C = cells_per_block(v.K), ld = table_ld(v.K);
     const long long base = (((long long)v.g * v.F + v.f) * v.hw + (long long)v.cblock * C) * v.K;
     for (int i = tid; i < C * v.K; i += APPLY_THREADS) {
@@ -240,7 +225,7 @@ static QMAP_HD inline void a_stage(const AView& v, int tid) {
 }
 
 // the nodes with xq <= x are [0, lo): a NaN x, or a NaN row, has none
-static QMAP_BOTH inline int count_le(const double* xq, int K, double x) {
+static C2W_BOTH inline int count_le(const double* xq, int K, double x) {
     int lo = 0, hi = K;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -249,13 +234,13 @@ static QMAP_BOTH inline int count_le(const double* xq, int K, double x) {
     return lo;
 }
 // steps after which the search over K nodes has ended: ceil(log2(K + 1))
-static QMAP_BOTH inline int search_steps(int K) {
+static C2W_BOTH inline int search_steps(int K) {
     int s = 0;
     while ((1 << s) <= K) ++s;
     return s;
 }
 // count_le for the four cells of a quad, step by step side by side: the same comparisons, the four LDS reads of a step in flight together
-static QMAP_BOTH inline void count_le4(const double* xq, int ld, int K, const double* x, int* lo) {
+static C2W_BOTH inline void count_le4(const double* xq, int ld, int K, const double* x, int* lo) {
     int hi[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) lo[e] = 0, hi[e] = K;
@@ -271,7 +256,7 @@ static QMAP_BOTH inline void count_le4(const double* xq, int ld, int K, const do
 }
 
 // the definition, given lo = the number of nodes with xq <= x
-static QMAP_BOTH inline float map_at(const double* xq, const double* yq, int K, double x, int lo) {
+static C2W_BOTH inline float map_at(const double* xq, const double* yq, int K, double x, int lo) {
     QMAP_NO_CONTRACT
     double y;
     if (lo == 0) {
@@ -289,11 +274,11 @@ static QMAP_BOTH inline float map_at(const double* xq, const double* yq, int K, 
     }
     return (float)y;
 }
-static QMAP_BOTH inline float map_one(const double* xq, const double* yq, int K, float xf) {
+static C2W_BOTH inline float map_one(const double* xq, const double* yq, int K, float xf) {
     return map_at(xq, yq, K, (double)xf, count_le(xq, K, (double)xf));
 }
 
-static QMAP_HD inline void a_walk(const AView& v, int tid) {
+static C2W_HD inline void a_walk(const AView& v, int tid) {
     const int C = cells_per_block(v.K), ld = table_ld(v.K), lanes = C / 4, rpp = APPLY_THREADS / lanes;
     const int cl = 4 * (tid % lanes), c = v.cblock * C + cl;
     if (c >= v.hw) return;  // hw % 4 == 0: a quad is whole or absent

@@ -5,9 +5,6 @@
 // read back by the host in between.  quantile_core.h has the maps and the arithmetic; this file is the workgroups around them.
 // Integer counts only: no float atomics, no result that depends on the launch.
 #include "launch.h"
-
-#define QNT_HD __device__ __attribute__((always_inline))
-#define QNT_BOTH __host__ __device__ __attribute__((always_inline))
 #include "quantile_core.h"
 
 namespace {
@@ -105,7 +102,7 @@ extern "C" int c2w_quantiles(const float* x, const float* y, const double* q, in
                              double* out, float* stats, long long* n_valid, long long n_rep, int T, int F, int hw, void* stream) {
     if (!qnt::supported(hw, Q)) return C2W_ERR_UNSUPPORTED;
     if (n_rep < 0 || T < 1 || F < 1 || (n_rep > 0 && !x) || !q || !scratch || !out || !stats || !n_valid ||
-        (((uintptr_t)x | (uintptr_t)y | (uintptr_t)scratch) & 15) != 0 || (((uintptr_t)out | (uintptr_t)n_valid) & 7) != 0 || ((uintptr_t)stats & 3) != 0)
+        !c2w_aligned(16, x, y, scratch) || !c2w_aligned(8, out, n_valid) || !c2w_aligned(4, stats))
         return C2W_ERR_BAD_ARG;
     Levels lv{};
     for (int j = 0; j < Q; ++j) {
@@ -116,7 +113,7 @@ extern "C" int c2w_quantiles(const float* x, const float* y, const double* q, in
     if (D == 0) return 0;
     const int slabs = slab_count(D, T, c2w_cu_count());
     // an LDS counter is an int: a workgroup's slab stays below 2^31 values (and its quads below 2^29)
-    if (D * slabs > 0x7fffffffLL || (long long)slab_planes(T, slabs) * hw > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(D * slabs) || (long long)slab_planes(T, slabs) * hw > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
     const Layout lay = layout(D, Q);
     if (scratch_bytes < (unsigned long long)lay.total) return C2W_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;

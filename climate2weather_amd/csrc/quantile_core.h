@@ -1,5 +1,5 @@
 // Exact order statistics by radix select: the index maps, the key map, the slot logic and the final arithmetic of quantile.hip, written
-// as barrier-separated phases over "thread tid of a workgroup", as kde_core.h is.  Compiled for the host (QNT_HD empty) the same phases
+// as barrier-separated phases over "thread tid of a workgroup", as kde_core.h is.  Compiled for the host (core_side.h) the same phases
 // run one thread after the other: tests/host_quantile_main.cpp checks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_quantiles).  Data set d < n_rep F is x[d / F][t][d % F][:] for all t < T, the others are variable
@@ -19,12 +19,7 @@
 #ifndef C2W_QUANTILE_CORE_H
 #define C2W_QUANTILE_CORE_H
 
-#ifndef QNT_HD
-#define QNT_HD
-#define QNT_BOTH
-#define QNT_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 
 namespace qnt {
 
@@ -40,14 +35,14 @@ constexpr int NONE = 255;          // tab entry: no slot has these top bits
 constexpr int LOADS = 4;          // 16-byte loads a counting thread has in flight
 constexpr int WG_PER_CU = 8;       // counting workgroups per compute unit the slab count aims at
 
-static QNT_BOTH inline bool supported(int hw, int Q) { return hw >= 4 && hw % 4 == 0 && Q >= 1 && Q <= MAX_Q; }
+static C2W_BOTH inline bool supported(int hw, int Q) { return hw >= 4 && hw % 4 == 0 && Q >= 1 && Q <= MAX_Q; }
 
 // ---------------------------------------------------------------------------------------------------------------- key
 
-static QNT_BOTH inline unsigned key_of(unsigned bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
-static QNT_BOTH inline unsigned bits_of(unsigned key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
-static QNT_BOTH inline bool is_nan_bits(unsigned bits) { return (bits & 0x7FFFFFFFu) > 0x7F800000u; }  // v != v, on the bits
-static QNT_BOTH inline float float_of(unsigned bits) { return __builtin_bit_cast(float, bits); }
+static C2W_BOTH inline unsigned key_of(unsigned bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+static C2W_BOTH inline unsigned bits_of(unsigned key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
+static C2W_BOTH inline bool is_nan_bits(unsigned bits) { return (bits & 0x7FFFFFFFu) > 0x7F800000u; }  // v != v, on the bits
+static C2W_BOTH inline float float_of(unsigned bits) { return __builtin_bit_cast(float, bits); }
 
 // ---------------------------------------------------------------------------------------------------------------- scratch
 
@@ -66,7 +61,7 @@ struct Layout {
     long long total;
 };
 
-static QNT_BOTH inline Layout layout(long long D, int Q) {
+static C2W_BOTH inline Layout layout(long long D, int Q) {
     const long long R = 2 * Q;
     Layout l;
     l.table0 = 0;
@@ -84,21 +79,21 @@ static QNT_BOTH inline Layout layout(long long D, int Q) {
 }
 
 // LDS bytes of a counting workgroup: the counters, then (passes 1, 2) the slot prefixes and the table, then the NaN counter
-static QNT_BOTH inline int count_lds_bytes(int pass, int Q) { return pass == 0 ? BINS0 * 4 + 16 : 2 * Q * BINS * 4 + 2 * Q * 4 + BINS0 + 16; }
+static C2W_BOTH inline int count_lds_bytes(int pass, int Q) { return pass == 0 ? BINS0 * 4 + 16 : 2 * Q * BINS * 4 + 2 * Q * 4 + BINS0 + 16; }
 
 // ---------------------------------------------------------------------------------------------------------------- slabs
 
 // slabs per data set: WG_PER_CU workgroups a compute unit over all D data sets, one plane a slab at least
-static QNT_BOTH inline int slab_count(long long D, int T, int cus) {
+static C2W_BOTH inline int slab_count(long long D, int T, int cus) {
     long long s = (long long)cus * WG_PER_CU / (D < 1 ? 1 : D);
     return (int)(s < 1 ? 1 : s > T ? T : s);
 }
-static QNT_BOTH inline int slab_planes(int T, int slabs) { return (T + slabs - 1) / slabs; }
-static QNT_BOTH inline int slab_begin(int T, int slabs, int s) {
+static C2W_BOTH inline int slab_planes(int T, int slabs) { return (T + slabs - 1) / slabs; }
+static C2W_BOTH inline int slab_begin(int T, int slabs, int s) {
     const long long b = (long long)s * slab_planes(T, slabs);
     return (int)(b < T ? b : T);
 }
-static QNT_BOTH inline int slab_end(int T, int slabs, int s) {
+static C2W_BOTH inline int slab_end(int T, int slabs, int s) {
     const long long e = (long long)(s + 1) * slab_planes(T, slabs);
     return (int)(e < T ? e : T);
 }
@@ -122,30 +117,30 @@ struct CView {
     unsigned* lpre;            // LDS: R
     unsigned char* ltab;       // LDS: BINS0
     int* lnan;                 // LDS: 1
-#ifdef QNT_HOST
+#ifdef C2W_CORE_HOST
     int* owner;  // visit mode: the fields hold their own indices; owner[k] is the data set that loaded value k (-1 nobody, -2 twice)
 #endif
 };
 
-#ifdef QNT_HOST
+#ifdef C2W_CORE_HOST
 static inline void lds_add(int* p, int a) { *p += a; }
 static inline void global_add(long long* p, long long a) { *p += a; }
 struct alignas(16) Quad { unsigned x, y, z, w; };
 #else
-static QNT_HD inline void lds_add(int* p, int a) { atomicAdd(p, a); }
+static C2W_HD inline void lds_add(int* p, int a) { atomicAdd(p, a); }
 #ifndef QNT_COMBINE
 #define QNT_COMBINE 1  // on by measurement (profiles/quantiles_measurements.md); -DQNT_COMBINE=0 is the build without it
 #endif
-static QNT_HD inline void global_add(long long* p, long long a) { atomicAdd((unsigned long long*)p, (unsigned long long)a); }
+static C2W_HD inline void global_add(long long* p, long long a) { atomicAdd((unsigned long long*)p, (unsigned long long)a); }
 using Quad = uint4;
 #endif
 
 // one more value in counter p.  QNT_COMBINE: when every active lane of the wave holds the same counter (a constant field in every pass,
 // a pressure field in pass 0) one lane adds the wave's count instead of 64 lanes queueing on one LDS address; the count is the same
-#if defined(QNT_HOST) || !QNT_COMBINE
-static QNT_HD inline void lds_count(int* p) { lds_add(p, 1); }
+#if defined(C2W_CORE_HOST) || !QNT_COMBINE
+static C2W_HD inline void lds_count(int* p) { lds_add(p, 1); }
 #else
-static QNT_HD inline void lds_count(int* p) {
+static C2W_HD inline void lds_count(int* p) {
     const int mine = (int)(size_t)p, first = __builtin_amdgcn_readfirstlane(mine);
     if (__all(mine == first)) {
         const unsigned long long active = __ballot(1);
@@ -156,12 +151,12 @@ static QNT_HD inline void lds_count(int* p) {
 }
 #endif
 
-static QNT_BOTH inline const float* set_base(const CView& v) {
+static C2W_BOTH inline const float* set_base(const CView& v) {
     return v.ds < v.n_x ? v.x + ((v.ds / v.F) * v.T * v.F + v.ds % v.F) * (long long)v.hw : v.y + (v.ds - v.n_x) * (long long)v.hw;
 }
-static QNT_BOTH inline int count_bins(const CView& v) { return v.pass == 0 ? BINS0 : v.ns * BINS; }
+static C2W_BOTH inline int count_bins(const CView& v) { return v.pass == 0 ? BINS0 : v.ns * BINS; }
 
-static QNT_HD inline void c_zero(const CView& v, int tid) {
+static C2W_HD inline void c_zero(const CView& v, int tid) {
     for (int i = tid; i < count_bins(v); i += THREADS) v.hist[i] = 0;
     if (tid == 0) *v.lnan = 0;
     if (v.pass == 0) return;
@@ -171,7 +166,7 @@ static QNT_HD inline void c_zero(const CView& v, int tid) {
 
 // one value: its bin of this pass, if it has one
 template <bool FIRST>
-static QNT_HD inline void c_one(const CView& v, unsigned bits, int& nans) {
+static C2W_HD inline void c_one(const CView& v, unsigned bits, int& nans) {
     if (is_nan_bits(bits)) {
         if (FIRST) ++nans;
         return;
@@ -192,7 +187,7 @@ static QNT_HD inline void c_one(const CView& v, unsigned bits, int& nans) {
 
 // the slab's planes as one list of 16-byte quads (hw % 4 == 0: a quad never leaves its plane), a quad a thread and step
 template <bool FIRST>
-static QNT_HD inline void c_count(const CView& v, int tid) {
+static C2W_HD inline void c_count(const CView& v, int tid) {
     const int t0 = slab_begin(v.T, v.slabs, v.slab), t1 = slab_end(v.T, v.slabs, v.slab);
     const unsigned quads = (unsigned)v.hw / 4;
     const long long items = (long long)(t1 - t0) * quads, plane = (long long)v.F * v.hw;  // items < 2^29: the launcher bounds the slab
@@ -207,7 +202,7 @@ static QNT_HD inline void c_count(const CView& v, int tid) {
             const unsigned t = (unsigned)i / quads, q = (unsigned)i - t * quads;
             const float* p = base + t * plane + 4 * q;
             b[u] = *(const Quad*)p;
-#ifdef QNT_HOST
+#ifdef C2W_CORE_HOST
             if (v.owner)
                 for (int e = 0; e < 4; ++e) v.owner[(long long)p[e]] = v.owner[(long long)p[e]] == -1 ? (int)v.ds : -2;
 #endif
@@ -222,7 +217,7 @@ static QNT_HD inline void c_count(const CView& v, int tid) {
 }
 
 // one 64-bit integer add per non-zero bin
-static QNT_HD inline void c_flush(const CView& v, int tid) {
+static C2W_HD inline void c_flush(const CView& v, int tid) {
     for (int i = tid; i < count_bins(v); i += THREADS)
         if (v.hist[i]) global_add(v.table + i, v.hist[i]);
     if (v.pass == 0 && tid == 0 && *v.lnan) global_add(v.nan, *v.lnan);
@@ -257,20 +252,20 @@ struct LView {
     int* isfirst;      // [MAX_RANKS]
 };
 
-static QNT_BOTH inline long long valid_count(const LView& v) { return v.n - *v.nan; }
+static C2W_BOTH inline long long valid_count(const LView& v) { return v.n - *v.nan; }
 // the row is NaN and nothing more is counted: no value, or a NaN where NaNs are not skipped
-static QNT_BOTH inline bool dead_at_first(const LView& v) { return valid_count(v) <= 0 || (!v.skipna && *v.nan > 0); }
+static C2W_BOTH inline bool dead_at_first(const LView& v) { return valid_count(v) <= 0 || (!v.skipna && *v.nan > 0); }
 // before any phase writes: what the previous pass left (dead: no value, a NaN where NaNs are not skipped, or marked so by pass 0)
-static QNT_BOTH inline void l_open(LView& v) {
+static C2W_BOTH inline void l_open(LView& v) {
     const int ns = v.pass == 0 ? 1 : *v.ns;
     v.ns_in = ns < 0 ? 0 : ns > v.R ? v.R : ns;
     v.is_dead = v.pass == 0 ? dead_at_first(v) : v.ns_in == 0;
 }
-static QNT_BOTH inline int slots_in(const LView& v) { return v.ns_in; }
-static QNT_BOTH inline int bins_in(const LView& v) { return v.pass == 0 ? BINS0 : BINS; }
+static C2W_BOTH inline int slots_in(const LView& v) { return v.ns_in; }
+static C2W_BOTH inline int bins_in(const LView& v) { return v.pass == 0 ? BINS0 : BINS; }
 
 // v = (nv - 1) q; rank r is lo = floor(v) (r even) or min(lo + 1, nv - 1) (r odd) of level r / 2
-static QNT_BOTH inline long long rank_of(long long nv, double q, int odd) {
+static C2W_BOTH inline long long rank_of(long long nv, double q, int odd) {
     const double pos = (double)(nv - 1) * q;
     long long lo = (long long)floor(pos);
     lo = lo < 0 ? 0 : lo > nv - 1 ? nv - 1 : lo;
@@ -278,7 +273,7 @@ static QNT_BOTH inline long long rank_of(long long nv, double q, int odd) {
 }
 
 // numpy's _lerp in double, every operation rounded on its own
-static QNT_BOTH inline double lerp_of(long long nv, double q, float fa, float fb) {
+static C2W_BOTH inline double lerp_of(long long nv, double q, float fa, float fb) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -289,7 +284,7 @@ static QNT_BOTH inline double lerp_of(long long nv, double q, float fa, float fb
 }
 
 // pass 0: the ranks; every pass: the sums of every slot's table over LOCATE_THREADS equal chunks, and an empty tab
-static QNT_HD inline void l_sums(const LView& v, int tid) {
+static C2W_HD inline void l_sums(const LView& v, int tid) {
     if (v.pass == 0) {
         if (tid == 0) v.nvalid[v.ds] = valid_count(v);
         if (tid < v.R) v.res[tid] = v.is_dead ? 0 : rank_of(valid_count(v), v.q[tid / 2], tid & 1), v.rslot[tid] = 0;
@@ -305,10 +300,10 @@ static QNT_HD inline void l_sums(const LView& v, int tid) {
         for (int i = tid; i < BINS0; i += LOCATE_THREADS) v.tab[i] = (unsigned char)NONE;
 }
 
-static QNT_BOTH inline bool dead(const LView& v) { return v.is_dead != 0; }
+static C2W_BOTH inline bool dead(const LView& v) { return v.is_dead != 0; }
 
 // rank tid: the bin of its slot's table that holds it, and its rank within that bin
-static QNT_HD inline void l_find(const LView& v, int tid) {
+static C2W_HD inline void l_find(const LView& v, int tid) {
     if (tid >= v.R || dead(v)) return;
     int s = v.rslot[tid];
     s = s < 0 ? 0 : s >= slots_in(v) ? slots_in(v) - 1 : s;
@@ -332,7 +327,7 @@ static QNT_HD inline void l_find(const LView& v, int tid) {
 }
 
 // rank tid is the first of the ranks with its new prefix
-static QNT_HD inline void l_mark(const LView& v, int tid) {
+static C2W_HD inline void l_mark(const LView& v, int tid) {
     if (tid >= v.R || dead(v)) return;
     int first = 1;
     for (int p = 0; p < tid; ++p) first &= v.newpre[p] != v.newpre[tid];
@@ -340,7 +335,7 @@ static QNT_HD inline void l_mark(const LView& v, int tid) {
 }
 
 // the distinct new prefixes, ascending, are the next pass's slots; tab points at the first slot of every top-12 value in use
-static QNT_HD inline void l_slots(const LView& v, int tid) {
+static C2W_HD inline void l_slots(const LView& v, int tid) {
     if (dead(v)) {
         if (tid == 0) *v.ns = 0;
         return;
@@ -363,7 +358,7 @@ static QNT_HD inline void l_slots(const LView& v, int tid) {
 }
 
 // after pass 2 a rank's new prefix is its key: level tid's two order statistics and the interpolation
-static QNT_HD inline void l_final(const LView& v, int tid) {
+static C2W_HD inline void l_final(const LView& v, int tid) {
     if (tid >= v.Q) return;
     const long long at = v.ds * v.Q + tid;
     if (dead(v)) {

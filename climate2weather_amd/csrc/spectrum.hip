@@ -5,9 +5,6 @@
 // takes 16, 8 or 4 fields; at N = 64 and 128 it takes one.  No atomics, no float sum whose order depends on the launch: a field's
 // outputs are the same bits wherever it lies in the batch.
 #include "launch.h"
-
-#define SPEC_HD __device__ __forceinline__
-#define SPEC_TABLE static __device__ const
 #include "spectrum_core.h"
 
 namespace {
@@ -61,7 +58,7 @@ int rapsd_launch(const float* x, float* spec, long long n_fields, hipStream_t st
         if (int rc = c2w_lds_optin<rapsd_kernel<N>>((int)lds)) return rc;
     }
     const long long grid = (n_fields + P::FPW - 1) / P::FPW;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     rapsd_kernel<N><<<(unsigned)grid, 256, lds, st>>>(x, spec, n_fields);
     return (int)hipGetLastError();
 }
@@ -74,7 +71,7 @@ extern "C" int c2w_rapsd_supported(int H, int W) {
 
 extern "C" int c2w_rapsd(const float* x, float* spec, long long n_fields, int H, int W, void* stream) {
     if (!c2w_rapsd_supported(H, W)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !spec || ((uintptr_t)x & 15) != 0 || n_fields < 0) return C2W_ERR_BAD_ARG;
+    if (!x || !spec || !c2w_aligned(16, x) || n_fields < 0) return C2W_ERR_BAD_ARG;
     if (n_fields == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     switch (H) {

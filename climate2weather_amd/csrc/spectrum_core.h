@@ -1,6 +1,6 @@
 // Radially averaged power spectrum of one square real field, N in {8, 16, 32, 64, 128}: the arithmetic of spectrum.hip, written as
 // nine barrier-separated phases over "thread tl of the TPF that share a field".  A phase touches the field's LDS image only in ways
-// that need no ordering inside the phase, so the kernel is phase, __syncthreads(), phase, ...; compiled for the host (SPEC_HD empty)
+// that need no ordering inside the phase, so the kernel is phase, __syncthreads(), phase, ...; compiled for the host (core_side.h)
 // the same phases run one thread after the other, which is how the index maps below are checked without a GPU.
 //
 // Definition (a restatement of the radial spectrum the reference takes from its radar library, from memory -- see c2w_hip.h):
@@ -22,9 +22,11 @@
 #ifndef C2W_SPECTRUM_CORE_H
 #define C2W_SPECTRUM_CORE_H
 
-#ifndef SPEC_HD
-#define SPEC_HD
+#include "core_side.h"
+#ifdef C2W_CORE_HOST
 #define SPEC_TABLE static const
+#else
+#define SPEC_TABLE static __device__ const
 #endif
 
 namespace spectrum {
@@ -42,7 +44,7 @@ SPEC_TABLE float QUARTER_TWIDDLE[32][2] = {
         {0.382683426f, -0.923879504f}, {0.336889863f, -0.941544056f}, {0.290284663f, -0.956940353f}, {0.242980182f, -0.970031261f},
         {0.195090324f, -0.980785251f}, {0.146730468f, -0.989176512f}, {0.0980171412f, -0.99518472f}, {0.0490676761f, -0.99879545f}};
 
-static SPEC_HD inline Cplx twiddle128(int j) {  // exp(-2 pi i j / 128), j = 0 .. 127
+static C2W_HD inline Cplx twiddle128(int j) {  // exp(-2 pi i j / 128), j = 0 .. 127
     const Cplx w{QUARTER_TWIDDLE[j & 31][0], QUARTER_TWIDDLE[j & 31][1]};
     switch (j >> 5) {
         case 0: return w;
@@ -66,8 +68,8 @@ struct Plan {
     // a workgroup's LDS: FPW images | N twiddles | per field: TPF doubles (load partials, later bin partials), 16 doubles, TPF ints
     static constexpr int AUX_D = TPF + 16;                      // doubles per field
     static constexpr size_t lds_bytes() { return sizeof(float) * ((size_t)FPW * IMG + 2 * N) + (size_t)FPW * (sizeof(double) * AUX_D + sizeof(int) * TPF); }
-    static SPEC_HD constexpr int pos(int k) { return (k % N1) * N2 + k / N1; }
-    static SPEC_HD constexpr int mirror(int c) { return c ? N - c : N / 2; }
+    static C2W_HD constexpr int pos(int k) { return (k % N1) * N2 + k / N1; }
+    static C2W_HD constexpr int mirror(int c) { return c ? N - c : N / 2; }
 };
 
 // exp(-2 pi i j / 16), j = 0 .. 7: the register transforms' own factors (j = 0 and j = 4 are handled without a multiply)
@@ -78,7 +80,7 @@ struct Plan {
 // Radix-2 decimation-in-time transform of R = 2, 4, 8 or 16 points held in registers (every index below is a compile-time constant
 // once the loops are unrolled).
 template <int R>
-static SPEC_HD inline void fft_reg(float (&re)[R], float (&im)[R]) {
+static C2W_HD inline void fft_reg(float (&re)[R], float (&im)[R]) {
     constexpr float WR[8] = {1.0f, SPEC_C1, SPEC_C2, SPEC_C3, 0.0f, -SPEC_C3, -SPEC_C2, -SPEC_C1};
     constexpr float WI[8] = {0.0f, -SPEC_C3, -SPEC_C2, -SPEC_C1, -1.0f, -SPEC_C1, -SPEC_C2, -SPEC_C3};
     constexpr int LOG = R == 16 ? 4 : R == 8 ? 3 : R == 4 ? 2 : 1;
@@ -113,7 +115,7 @@ static SPEC_HD inline void fft_reg(float (&re)[R], float (&im)[R]) {
     }
 }
 
-static SPEC_HD inline int isqrt_small(int v) {  // floor(sqrt(v)), 0 <= v < 2^15
+static C2W_HD inline int isqrt_small(int v) {  // floor(sqrt(v)), 0 <= v < 2^15
     int s = (int)sqrtf((float)v);
     while (s * s > v) --s;
     while ((s + 1) * (s + 1) <= v) ++s;
@@ -133,7 +135,7 @@ struct FieldView {
 };
 
 template <int N>
-static SPEC_HD inline double field_sum(const FieldView& v) {  // the 16 second-level partials, in order: every thread gets the same bits
+static C2W_HD inline double field_sum(const FieldView& v) {  // the 16 second-level partials, in order: every thread gets the same bits
     double s = 0.0;
     for (int j = 0; j < 16; ++j) s += v.dlev[j];
     return s;
@@ -141,7 +143,7 @@ static SPEC_HD inline double field_sum(const FieldView& v) {  // the 16 second-l
 
 // phase 0: one coalesced read of the field, 16 bytes a lane; thread partial sums in double, in the order of the thread's own loads
 template <int N>
-static SPEC_HD inline void phase_load(const FieldView& v, int tl) {
+static C2W_HD inline void phase_load(const FieldView& v, int tl) {
     using P = Plan<N>;
     double s = 0.0;
     for (int i = tl; i < N * N / 4; i += P::TPF) {
@@ -155,7 +157,7 @@ static SPEC_HD inline void phase_load(const FieldView& v, int tl) {
 
 // phase 1: 16 threads fold TPF / 16 partials each
 template <int N>
-static SPEC_HD inline void phase_fold(const FieldView& v, int tl) {
+static C2W_HD inline void phase_fold(const FieldView& v, int tl) {
     using P = Plan<N>;
     if (tl < 16) {
         double s = 0.0;
@@ -168,7 +170,7 @@ static SPEC_HD inline void phase_fold(const FieldView& v, int tl) {
 // line is at re0[off(e)] -- rows: off(e) = e, columns: see col_off.
 // phase 2: rows, pass A (with the mean taken off as the values are read)
 template <int N>
-static SPEC_HD inline void phase_rows_a(const FieldView& v, int tl) {
+static C2W_HD inline void phase_rows_a(const FieldView& v, int tl) {
     using P = Plan<N>;
     const float mean = (float)(field_sum<N>(v) / (double)(N * N));
     for (int it = tl; it < P::R * P::N2; it += P::TPF) {
@@ -189,7 +191,7 @@ static SPEC_HD inline void phase_rows_a(const FieldView& v, int tl) {
 
 // phase 3: rows, pass B
 template <int N>
-static SPEC_HD inline void phase_rows_b(const FieldView& v, int tl) {
+static C2W_HD inline void phase_rows_b(const FieldView& v, int tl) {
     using P = Plan<N>;
     for (int it = tl; it < P::R * P::N1; it += P::TPF) {
         const int k1 = it % P::N1, p = it / P::N1;
@@ -205,7 +207,7 @@ static SPEC_HD inline void phase_rows_b(const FieldView& v, int tl) {
 
 // phase 4: untangle the packed pair, in place on the four floats of slots pos(k) and pos(N - k)
 template <int N>
-static SPEC_HD inline void phase_untangle(const FieldView& v, int tl) {
+static C2W_HD inline void phase_untangle(const FieldView& v, int tl) {
     using P = Plan<N>;
     for (int it = tl; it < P::R * P::R; it += P::TPF) {
         const int k = it % P::R, p = it / P::R;
@@ -225,20 +227,20 @@ static SPEC_HD inline void phase_untangle(const FieldView& v, int tl) {
 
 // H[r][c]'s real float (the imaginary one is LD further): even rows keep column c in slot pos(c), odd rows in slot pos(N - c)
 template <int N>
-static SPEC_HD inline int cell(int r, int se, int so) {
+static C2W_HD inline int cell(int r, int se, int so) {
     return (r & ~1) * Plan<N>::LD + ((r & 1) ? so : se);
 }
 
 // lane j of a column pass -> column c, ordered so that the even-row slots pos(c) of consecutive lanes are consecutive floats
 template <int N>
-static SPEC_HD inline int lane_column(int j) {
+static C2W_HD inline int lane_column(int j) {
     using P = Plan<N>;
     return (j % (P::N2 / 2)) * P::N1 + j / (P::N2 / 2);
 }
 
 // phase 5: columns, pass A
 template <int N>
-static SPEC_HD inline void phase_cols_a(const FieldView& v, int tl) {
+static C2W_HD inline void phase_cols_a(const FieldView& v, int tl) {
     using P = Plan<N>;
     for (int it = tl; it < P::R * P::N2; it += P::TPF) {
         const int c = lane_column<N>(it % P::R), n2 = it / P::R;
@@ -262,7 +264,7 @@ static SPEC_HD inline void phase_cols_a(const FieldView& v, int tl) {
 
 // phase 6: columns, pass B, and the power |.|^2 (unscaled) into the real float of row-slot k1 N2 + k2 = pos(u), u = k1 + N1 k2
 template <int N>
-static SPEC_HD inline void phase_cols_b(const FieldView& v, int tl) {
+static C2W_HD inline void phase_cols_b(const FieldView& v, int tl) {
     using P = Plan<N>;
     for (int it = tl; it < P::R * P::N1; it += P::TPF) {
         const int c = lane_column<N>(it % P::R), k1 = it / P::R;
@@ -281,7 +283,7 @@ static SPEC_HD inline void phase_cols_b(const FieldView& v, int tl) {
 
 // phase 7: thread (k, q) sums bin k's cells of rows u = q, q + NQ, ... in double (kv = 0 once, kv >= 1 twice) and counts them
 template <int N>
-static SPEC_HD inline void phase_bins(const FieldView& v, int tl) {
+static C2W_HD inline void phase_bins(const FieldView& v, int tl) {
     using P = Plan<N>;
     const int k = tl % P::R, q = tl / P::R;
     double acc = 0.0;
@@ -307,7 +309,7 @@ static SPEC_HD inline void phase_bins(const FieldView& v, int tl) {
 
 // phase 8: the NQ partials in order, the scale 1 / (4 N^2) (the untangle kept its factor 2), bin 0 from the field's own sum
 template <int N>
-static SPEC_HD inline void phase_store(const FieldView& v, int tl) {
+static C2W_HD inline void phase_store(const FieldView& v, int tl) {
     using P = Plan<N>;
     if (tl >= P::R) return;
     if (tl == 0) {

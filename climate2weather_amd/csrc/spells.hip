@@ -3,11 +3,6 @@
 // table.  Everything is integers: the workgroups add to the caller's accumulators with 64-bit integer adds, which commute, so the bits
 // do not depend on any order.  spells_core.h has the index maps and the arithmetic; this file is the workgroup around them.
 #include "launch.h"
-
-#define EV_HD __device__ __attribute__((always_inline))
-#define EV_BOTH __host__ __device__ __attribute__((always_inline))
-#define SP_HD __device__ __attribute__((always_inline))
-#define SP_BOTH __host__ __device__ __attribute__((always_inline))
 #include "spells_core.h"
 
 namespace {
@@ -33,8 +28,6 @@ __global__ __launch_bounds__(THREADS) void spell_update_kernel(const float* __re
     s_flush(v, tid);
 }
 
-bool misaligned(const void* a, const void* b, uintptr_t mask) { return (((uintptr_t)a | (uintptr_t)b) & mask) != 0; }
-
 }  // namespace
 
 extern "C" int c2w_spell_supported(int hw, int K, int max_duration, int period) { return spells::supported(hw, K, max_duration, period) ? 1 : 0; }
@@ -43,12 +36,11 @@ extern "C" int c2w_spell_update(const float* x, const float* y, const float* thr
                                 long long* invalid, int M, int T, int F, int hw, int K, int max_duration, int period, long long t0, void* stream) {
     if (!spells::supported(hw, K, max_duration, period) || M < 1) return C2W_ERR_UNSUPPORTED;
     if (!x || !thr || !dir || !state || !hist || !invalid || (period > 0 && !onsets) || T < 0 || F < 1 || t0 < 0) return C2W_ERR_BAD_ARG;
-    if (misaligned(x, y, 15) || misaligned(state, nullptr, 15) || misaligned(hist, onsets, 7) || misaligned(invalid, nullptr, 7) || misaligned(thr, dir, 3))
-        return C2W_ERR_BAD_ARG;
+    if (!c2w_aligned(16, x, y, state) || !c2w_aligned(8, hist, onsets, invalid) || !c2w_aligned(4, thr, dir)) return C2W_ERR_BAD_ARG;
     if (T == 0) return 0;
     const int nc = spells::chunks(hw), D = M + (y ? 1 : 0);
     const long long grid = (long long)D * F * nc;
-    if (T > MAX_T || grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (T > MAX_T || !c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     const int phase0 = period > 0 ? (int)(t0 % period) : 0;
     hipStream_t st = (hipStream_t)stream;
     for (int g = 0; g < spells::groups(K); ++g) {  // the groups touch disjoint entries of the state and of the tables

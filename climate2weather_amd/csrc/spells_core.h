@@ -1,5 +1,5 @@
 // Event spells of an ensemble: the index maps and the integer arithmetic of spells.hip, written as barrier-separated phases over
-// "thread tid of a workgroup", as events_core.h and temporal_core.h are.  Compiled for the host (SP_HD empty) the same phases run one
+// "thread tid of a workgroup", as events_core.h and temporal_core.h are.  Compiled for the host (core_side.h) the same phases run one
 // thread after the other: tests/host_spells_main.cpp walks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_spell_update).  The rows are d = 0 the truth when one is given, then the M members; D rows in all.  The
@@ -20,10 +20,7 @@
 #ifndef C2W_SPELLS_CORE_H
 #define C2W_SPELLS_CORE_H
 
-#ifndef SP_HD
-#define SP_HD
-#define SP_BOTH
-#endif
+#include "core_side.h"
 
 #ifndef SP_VISIT_READ  // the host driver counts here: a cell-hour read by a threshold group; a state entry loaded; a state entry stored
 #define SP_VISIT_READ(d, f, k0, t, cell)
@@ -55,13 +52,13 @@ static_assert(GROUP * CELLS * COUNTERS == 64, "the state registers of a thread")
 typedef float F4 __attribute__((vector_size(16)));  // 16 bytes a load
 typedef int I4 __attribute__((vector_size(16)));
 
-static SP_BOTH inline bool supported(int hw, int K, int lmax, int period) {
+static C2W_BOTH inline bool supported(int hw, int K, int lmax, int period) {
     return hw >= 4 && hw % 4 == 0 && K >= 1 && K <= MAX_K && lmax >= 1 && lmax <= MAX_LMAX && period >= 0 && period <= MAX_PERIOD;
 }
-static SP_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
-static SP_BOTH inline int cell_of(int chunk, int tid) { return chunk * CHUNK + tid * CELLS; }
-static SP_BOTH inline int groups(int K) { return (K + GROUP - 1) / GROUP; }
-static SP_BOTH inline int group_size(int K, int g) { return K - g * GROUP < GROUP ? K - g * GROUP : GROUP; }
+static C2W_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
+static C2W_BOTH inline int cell_of(int chunk, int tid) { return chunk * CHUNK + tid * CELLS; }
+static C2W_BOTH inline int groups(int K) { return (K + GROUP - 1) / GROUP; }
+static C2W_BOTH inline int group_size(int K, int g) { return K - g * GROUP < GROUP ? K - g * GROUP : GROUP; }
 
 struct View {
     const float* x;      // [M][T][F][hw]
@@ -81,34 +78,34 @@ struct View {
 // event_of with the direction folded into a sign: x <= thr is -x >= -thr for every pair of IEEE numbers, the infinities and both
 // zeros included, and a NaN stays no event under either sign -- so one compare serves both directions.  flip is 0 (above) or the sign
 // bit (below), sthr the threshold with the same bit flipped.  tests/host_spells_main.cpp holds it against event_of on the special values.
-static SP_BOTH inline unsigned flip_of(int above) { return above ? 0u : 0x80000000u; }
-static SP_BOTH inline float flipped(float v, unsigned flip) {
+static C2W_BOTH inline unsigned flip_of(int above) { return above ? 0u : 0x80000000u; }
+static C2W_BOTH inline float flipped(float v, unsigned flip) {
     unsigned u;
     __builtin_memcpy(&u, &v, 4);
     u ^= flip;
     __builtin_memcpy(&v, &u, 4);
     return v;
 }
-static SP_BOTH inline int event_flipped(float v, float sthr, unsigned flip) { return flipped(v, flip) >= sthr ? 1 : 0; }
+static C2W_BOTH inline int event_flipped(float v, float sthr, unsigned flip) { return flipped(v, flip) >= sthr ? 1 : 0; }
 
 // entry (counter s, threshold k0 + k, cell) of state
-static SP_HD inline long long state_at(const View& v, int s, int k, int cell) {
+static C2W_HD inline long long state_at(const View& v, int s, int k, int cell) {
     return ((((long long)s * v.D + v.d) * v.F + v.f) * v.K + v.k0 + k) * v.hw + cell;
 }
 // plane (t = 0, f) of the row this workgroup owns
-static SP_HD inline const float* row_of(const View& v) {
+static C2W_HD inline const float* row_of(const View& v) {
     const long long member = (long long)v.T * v.F * v.hw;
     const float* row = v.y ? (v.d == 0 ? v.y : v.x + (v.d - 1) * member) : v.x + v.d * member;
     return row + (long long)v.f * v.hw;
 }
-static SP_HD inline long long table_row(const View& v, int k) { return ((long long)v.d * v.F + v.f) * v.K + v.k0 + k; }
+static C2W_HD inline long long table_row(const View& v, int k) { return ((long long)v.d * v.F + v.f) * v.K + v.k0 + k; }
 
-static SP_HD inline void s_zero(const View& v, int tid) {
+static C2W_HD inline void s_zero(const View& v, int tid) {
     for (int i = tid; i < LDS_INTS; i += THREADS) v.lds[i] = 0;
 }
 
 // one cell-hour of one threshold: the counters are references into the thread's registers
-static SP_HD inline void s_step(const View& v, int k, int e, int phase, int& open, int& longest, int& count, int& hours) {
+static C2W_HD inline void s_step(const View& v, int k, int e, int phase, int& open, int& longest, int& count, int& hours) {
     const int was = open;
     const bool ending = !e && was > 0, starting = e && was == 0;
     open = e ? was + 1 : 0;  // the counters move without a branch; only the two LDS adds, which are rare, are under one
@@ -119,7 +116,7 @@ static SP_HD inline void s_step(const View& v, int k, int e, int phase, int& ope
     if (starting && v.period) lds_inc(v.lds + LDS_ONSETS + k * MAX_PERIOD + phase);
 }
 
-static SP_HD inline void s_walk(const View& v, int tid) {
+static C2W_HD inline void s_walk(const View& v, int tid) {
     const int cell = cell_of(v.chunk, tid);
     if (cell >= v.hw) return;  // hw is a multiple of 4: a thread has its four cells or none
     float sthr[GROUP];
@@ -181,7 +178,7 @@ static SP_HD inline void s_walk(const View& v, int tid) {
 }
 
 // one 64-bit add per non-zero entry of the workgroup's bins
-static SP_HD inline void s_flush(const View& v, int tid) {
+static C2W_HD inline void s_flush(const View& v, int tid) {
     for (int i = tid; i < v.kn * v.lmax; i += THREADS) {
         const int k = i / v.lmax, b = i % v.lmax, n = v.lds[LDS_HIST + k * MAX_LMAX + b];
         if (n) global_add(v.hist + table_row(v, k) * v.lmax + b, (long long)n);

@@ -3,11 +3,7 @@
 // four when W <= 32; rows stream through a ring of LDS rows in strips of 8 output rows, the next strip's 16 bytes per thread in flight
 // while this one is summed (ssim_core.h has the arithmetic and the index maps; this file is the workgroup around them).  No atomics, no
 // sum whose order depends on the launch: a pair's score is the same bits wherever it lies in the batch.
-#include "common.h"
-#include "c2w_hip.h"
-
-#define SSIM_HD __device__ __forceinline__
-#define SSIM_BOTH __host__ __device__ __forceinline__
+#include "launch.h"
 #include "ssim_core.h"
 
 namespace {
@@ -55,7 +51,7 @@ int ssim_launch(const float* x, const float* y, const float* range, double* out,
                 hipStream_t st) {
     const int fpw = make_shape(H, W, WIN).FPW;
     const long long grid = (n_pairs + fpw - 1) / fpw;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     ssim_kernel<WIN><<<(unsigned)grid, THREADS, 0, st>>>(x, y, range, out, n_pairs, n_truth, H, W);
     return (int)hipGetLastError();
 }
@@ -69,7 +65,7 @@ extern "C" int c2w_ssim_supported(int H, int W, int win) {
 extern "C" int c2w_ssim(const float* x, const float* y, const float* data_range, double* out, long long n_pairs, long long n_truth, int H, int W,
                         int win, void* stream) {
     if (!c2w_ssim_supported(H, W, win)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !y || !data_range || !out || (((uintptr_t)x | (uintptr_t)y) & 15) != 0 || ((uintptr_t)out & 7) != 0 || n_pairs < 0 || n_truth < 1)
+    if (!x || !y || !data_range || !out || !c2w_aligned(16, x, y) || !c2w_aligned(8, out) || n_pairs < 0 || n_truth < 1)
         return C2W_ERR_BAD_ARG;
     if (n_pairs == 0) return 0;
     hipStream_t st = (hipStream_t)stream;

@@ -1,6 +1,6 @@
 // Mean structural similarity of pairs of fp32 fields under a uniform WIN x WIN window: the arithmetic of ssim.hip, written as
 // barrier-separated phases over "thread tid of the 256 of a workgroup".  A phase touches LDS only in ways that need no ordering inside
-// the phase, so the kernel is phase, __syncthreads(), phase, ...; compiled for the host (SSIM_HD empty) the same phases run one thread
+// the phase, so the kernel is phase, __syncthreads(), phase, ...; compiled for the host (core_side.h) the same phases run one thread
 // after the other over a Thread record each, which is how the index maps below are checked without a GPU.
 //
 // Definition (c2w_hip.h: c2w_ssim).  For a pair x, y of H x W, NP = WIN^2, cn = NP / (NP - 1), data range R:
@@ -24,10 +24,7 @@
 #ifndef C2W_SSIM_CORE_H
 #define C2W_SSIM_CORE_H
 
-#ifndef SSIM_HD
-#define SSIM_HD
-#define SSIM_BOTH  // the two shape functions, which the launcher calls on the host as well
-#endif
+#include "core_side.h"
 
 namespace ssim {
 
@@ -58,7 +55,7 @@ struct Shape {
     int NS;      // strips
 };
 
-static SSIM_BOTH inline Shape make_shape(int H, int W, int win) {
+static C2W_BOTH inline Shape make_shape(int H, int W, int win) {
     Shape s;
     s.H = H, s.W = W;
     s.FPW = W <= 32 ? 4 : 1;
@@ -70,7 +67,7 @@ static SSIM_BOTH inline Shape make_shape(int H, int W, int win) {
     return s;
 }
 
-static SSIM_BOTH inline bool supported(int H, int W, int win) {
+static C2W_BOTH inline bool supported(int H, int W, int win) {
     return H % 8 == 0 && W % 8 == 0 && H >= 16 && H <= 128 && W >= 16 && W <= 128 && (win == 7 || win == 11 || win == 15);
 }
 
@@ -97,14 +94,14 @@ struct Thread {
     double acc;        // sum of S over its windows so far
 };
 
-static SSIM_HD inline double sum16(const double* d) {  // in order: every thread gets the same bits
+static C2W_HD inline double sum16(const double* d) {  // in order: every thread gets the same bits
     double s = 0.0;
     for (int j = 0; j < 16; ++j) s += d[j];
     return s;
 }
 
 // four neighbouring window sums from the shared middle `core` (terms 3 .. WIN-1), terms 0, 1, 2 and terms WIN, WIN+1, WIN+2
-static SSIM_HD inline void edge(float (&out)[4], float core, float l0, float l1, float l2, float r0, float r1, float r2) {
+static C2W_HD inline void edge(float (&out)[4], float core, float l0, float l1, float l2, float r0, float r1, float r2) {
     const float t2 = core + l2, t21 = t2 + l1;
     out[0] = t21 + l0;
     out[1] = t21 + r0;
@@ -113,7 +110,7 @@ static SSIM_HD inline void edge(float (&out)[4], float core, float l0, float l1,
 }
 
 // phase 0: the truth field's sum, thread partials in double in the order of the thread's own loads
-static SSIM_HD inline void phase_pivot_partial(const View& v, const Shape& sh, int tid) {
+static C2W_HD inline void phase_pivot_partial(const View& v, const Shape& sh, int tid) {
     const int slot = tid / sh.TPF, tl = tid % sh.TPF;
     const long long pair = v.first + slot;
     double s = 0.0;
@@ -128,7 +125,7 @@ static SSIM_HD inline void phase_pivot_partial(const View& v, const Shape& sh, i
 }
 
 // phase 1: 16 threads of a slot fold TPF / 16 partials each
-static SSIM_HD inline void phase_pivot_fold(const View& v, const Shape& sh, int tid) {
+static C2W_HD inline void phase_pivot_fold(const View& v, const Shape& sh, int tid) {
     const int slot = tid / sh.TPF, tl = tid % sh.TPF;
     if (tl < 16) {
         const int n = sh.TPF / 16;
@@ -140,7 +137,7 @@ static SSIM_HD inline void phase_pivot_fold(const View& v, const Shape& sh, int 
 
 // phase 2: the thread's pivots and constants, and rows 0 .. WIN-2 of a and b into the ring
 template <int WIN>
-static SSIM_HD inline void phase_prologue(const View& v, const Shape& sh, Thread& th, int tid) {
+static C2W_HD inline void phase_prologue(const View& v, const Shape& sh, Thread& th, int tid) {
     const int slot = tid / sh.TPF, tl = tid % sh.TPF, W4 = sh.W / 4;
     const long long pair = v.first + slot, HW = (long long)(sh.H * sh.W);
     th.acc = 0.0, th.has = 0;
@@ -163,7 +160,7 @@ static SSIM_HD inline void phase_prologue(const View& v, const Shape& sh, Thread
 
 // the 16 bytes of x and of y this thread brings in for strip s: rows s SR + WIN - 1 .. + SR - 1, as far as the field goes
 template <int WIN>
-static SSIM_HD inline void fetch(const View& v, const Shape& sh, Thread& th, int tid, int s) {
+static C2W_HD inline void fetch(const View& v, const Shape& sh, Thread& th, int tid, int s) {
     const int slot = tid / sh.TPF, tl = tid % sh.TPF, W4 = sh.W / 4;
     const long long pair = v.first + slot, HW = (long long)(sh.H * sh.W);
     const int ri = tl / W4, q = tl % W4, row = s * SR + WIN - 1 + ri;
@@ -176,7 +173,7 @@ static SSIM_HD inline void fetch(const View& v, const Shape& sh, Thread& th, int
 
 // phase 3 (per strip): what fetch brought, pivoted, into the ring slots of the rows the last strip was the last to use
 template <int WIN>
-static SSIM_HD inline void phase_stash(const View& v, const Shape& sh, const Thread& th, int tid, int s) {
+static C2W_HD inline void phase_stash(const View& v, const Shape& sh, const Thread& th, int tid, int s) {
     if (!th.has) return;
     const int slot = tid / sh.TPF, tl = tid % sh.TPF, W4 = sh.W / 4;
     const int ri = tl / W4, q = tl % W4, row = s * SR + WIN - 1 + ri;
@@ -187,7 +184,7 @@ static SSIM_HD inline void phase_stash(const View& v, const Shape& sh, const Thr
 
 // phase 4 (per strip): column sums of a, b, aa, bb, ab over WIN rows, for 4 output rows of one column
 template <int WIN>
-static SSIM_HD inline void phase_vertical(const View& v, const Shape& sh, int tid, int s) {
+static C2W_HD inline void phase_vertical(const View& v, const Shape& sh, int tid, int s) {
     constexpr int RING = Plan<WIN>::RING, N = WIN + RB - 1;
     const int WT = sh.FPW * sh.SW, c = tid % WT, rb = tid / WT;
     if (rb >= SR / RB || c % sh.SW >= sh.W) return;
@@ -218,7 +215,7 @@ static SSIM_HD inline void phase_vertical(const View& v, const Shape& sh, int ti
 
 // S of one window from its five sums over NP = WIN^2 pivoted values
 template <int WIN>
-static SSIM_HD inline float window_score(float sa, float sb, float saa, float sbb, float sab, float p, float c1, float c2) {
+static C2W_HD inline float window_score(float sa, float sb, float saa, float sbb, float sab, float p, float c1, float c2) {
     constexpr float inv = 1.0f / (float)(WIN * WIN), cn = (float)(WIN * WIN) / (float)(WIN * WIN - 1);
     const float ua = sa * inv, ub = sb * inv;
     const float va = cn * fmaf(-ua, ua, saa * inv), vb = cn * fmaf(-ub, ub, sbb * inv), vab = cn * fmaf(-ua, ub, sab * inv);
@@ -229,7 +226,7 @@ static SSIM_HD inline float window_score(float sa, float sb, float saa, float sb
 
 // phase 5 (per strip): the row sums of the column sums, S, and the thread's running double
 template <int WIN>
-static SSIM_HD inline void phase_horizontal(const View& v, const Shape& sh, Thread& th, int tid, int s) {
+static C2W_HD inline void phase_horizontal(const View& v, const Shape& sh, Thread& th, int tid, int s) {
     constexpr int NV4 = Plan<WIN>::NV4;
     if (tid >= SR * sh.G) return;
     const int rr = tid / sh.G, col = (tid % sh.G) * 4, lc = col % sh.SW;
@@ -257,12 +254,12 @@ static SSIM_HD inline void phase_horizontal(const View& v, const Shape& sh, Thre
 }
 
 // phase 6: every thread's sum
-static SSIM_HD inline void phase_partial(const View& v, const Thread& th, int tid) {
+static C2W_HD inline void phase_partial(const View& v, const Thread& th, int tid) {
     v.dpart[tid] = th.acc;
 }
 
 // phase 7: 16 threads per slot fold the slot's partials, in the order (row of the strip, group of four columns)
-static SSIM_HD inline void phase_fold(const View& v, const Shape& sh, int tid) {
+static C2W_HD inline void phase_fold(const View& v, const Shape& sh, int tid) {
     if (tid >= sh.FPW * 16) return;
     const int slot = tid / 16, j = tid % 16, n = sh.TPF / 16;
     double s = 0.0;
@@ -271,7 +268,7 @@ static SSIM_HD inline void phase_fold(const View& v, const Shape& sh, int tid) {
 }
 
 // phase 8: the mean over the windows, one double per live pair
-static SSIM_HD inline void phase_store(const View& v, const Shape& sh, int tid) {
+static C2W_HD inline void phase_store(const View& v, const Shape& sh, int tid) {
     if (tid >= sh.FPW || v.first + tid >= v.n_pairs) return;
     v.out[v.first + tid] = sum16(v.dlev + tid * 16) / ((double)sh.OH * (double)sh.OW);
 }

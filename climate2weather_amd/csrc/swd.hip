@@ -4,9 +4,6 @@
 // writes one double.  swd_core.h has the index maps and the arithmetic; this file is the workgroups around them.  No atomics, no
 // scratch, no sum whose order depends on the launch.
 #include "launch.h"
-
-#define SWD_HD __device__ __attribute__((always_inline))
-#define SWD_BOTH __host__ __device__ __attribute__((always_inline))
 #include "swd_core.h"
 
 namespace {
@@ -78,13 +75,13 @@ extern "C" int c2w_swd_supported(int d, int P, int T) {
 extern "C" int c2w_swd_project_pair(const float* x, const float* y, const float* theta, const float* shift, const float* scale, float* proj_x,
                                     float* proj_y, long long n_rep, int T, int F, int d, int P, void* stream) {
     if (!swd::project_supported(d, P)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !theta || !shift || !scale || !proj_x || (y && !proj_y) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)theta) & 15) != 0 ||
-        (((uintptr_t)proj_x | (uintptr_t)proj_y) & 3) != 0 || n_rep < 0 || T < 1 || F < 1)
+    if (!x || !theta || !shift || !scale || !proj_x || (y && !proj_y) || !c2w_aligned(16, x, y, theta) || !c2w_aligned(4, proj_x, proj_y) ||
+        n_rep < 0 || T < 1 || F < 1)
         return C2W_ERR_BAD_ARG;
     const long long n_x = n_rep * T * F, n_y = y ? (long long)T * F : 0;
     const long long tiles_x = (n_x + BM - 1) / BM, grid = tiles_x + (n_y + BM - 1) / BM;
     if (grid == 0) return 0;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     swd_project_kernel<<<(unsigned)grid, THREADS, 0, (hipStream_t)stream>>>(x, y, theta, shift, scale, proj_x, proj_y, n_x, n_y, tiles_x, T, F, d, P);
     return (int)hipGetLastError();
 }
@@ -96,10 +93,10 @@ extern "C" int c2w_swd_project(const float* x, const float* theta, const float* 
 
 extern "C" int c2w_swd_distance(const float* proj_x, const float* proj_y, double* out, long long n_rep, int F, int P, int T, void* stream) {
     if (!swd::distance_supported(T)) return C2W_ERR_UNSUPPORTED;
-    if (!proj_x || !proj_y || !out || ((uintptr_t)out & 7) != 0 || n_rep < 0 || F < 1 || P < 1) return C2W_ERR_BAD_ARG;
+    if (!proj_x || !proj_y || !out || !c2w_aligned(8, out) || n_rep < 0 || F < 1 || P < 1) return C2W_ERR_BAD_ARG;
     const long long grid = n_rep * F * P;
     if (grid == 0) return 0;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     const int N = swd::padded(T), lds = 2 * N * (int)sizeof(float);
     if (int rc = c2w_lds_optin<swd_distance_kernel>(2 * MAX_T * (int)sizeof(float))) return rc;  // above the static limit at the largest T
     swd_distance_kernel<<<(unsigned)grid, swd::sort_threads(N), lds, (hipStream_t)stream>>>(proj_x, proj_y, out, F, P, T, N);

@@ -1,5 +1,5 @@
 // Sliced Wasserstein distance of an ensemble to the truth: the index maps and the arithmetic of swd.hip, written as barrier-separated
-// phases over "thread tid of a workgroup", as ssim_core.h is.  Compiled for the host (SWD_HD empty) the same phases run one thread after
+// phases over "thread tid of a workgroup", as ssim_core.h is.  Compiled for the host (core_side.h) the same phases run one thread after
 // the other over a record per thread, and the matrix-core step is replaced by mfma_32x32x2_host, which restates the lane maps and the
 // k order of v_mfma_f32_32x32x2_f32 in plain C++: tests/host_swd_main.cpp checks every map below without a GPU.
 //
@@ -27,11 +27,7 @@
 #ifndef C2W_SWD_CORE_H
 #define C2W_SWD_CORE_H
 
-#ifndef SWD_HD
-#define SWD_HD
-#define SWD_BOTH
-#define SWD_HOST 1
-#endif
+#include "core_side.h"
 
 namespace swd {
 
@@ -49,16 +45,16 @@ static_assert(BM * BK / 4 == THREADS, "one 16-byte load of x per thread and step
 constexpr int MAX_D = 65536, MAX_P = BN, MAX_T = 16384;
 constexpr int SORT_DOUBLES = 1024 + 16;  // one partial per thread | 16 second-level sums
 
-static SWD_BOTH inline bool project_supported(int d, int P) { return d >= 64 && d <= MAX_D && d % 64 == 0 && P >= 1 && P <= MAX_P; }
-static SWD_BOTH inline bool distance_supported(int T) { return T >= 1 && T <= MAX_T; }
-static SWD_BOTH inline int padded(int T) {
+static C2W_BOTH inline bool project_supported(int d, int P) { return d >= 64 && d <= MAX_D && d % 64 == 0 && P >= 1 && P <= MAX_P; }
+static C2W_BOTH inline bool distance_supported(int T) { return T >= 1 && T <= MAX_T; }
+static C2W_BOTH inline int padded(int T) {
     int n = 1;
     while (n < T) n <<= 1;
     return n;
 }
-static SWD_BOTH inline int sort_threads(int N) { return N <= 2048 ? 256 : 1024; }
+static C2W_BOTH inline int sort_threads(int N) { return N <= 2048 ? 256 : 1024; }
 
-#ifdef SWD_HOST
+#ifdef C2W_CORE_HOST
 struct V16 {
     float v[16];
     float& operator[](int i) { return v[i]; }
@@ -68,23 +64,23 @@ struct V16 {
 typedef __attribute__((ext_vector_type(16))) float V16;
 #endif
 
-static SWD_HD inline float comp(const float4& q, int s) { return s == 0 ? q.x : s == 1 ? q.y : s == 2 ? q.z : q.w; }
+static C2W_HD inline float comp(const float4& q, int s) { return s == 0 ? q.x : s == 1 ? q.y : s == 2 ? q.z : q.w; }
 
 // ---------------------------------------------------------------------------------------------------------------- projection: maps
 
 // load j of thread tid brings 16 bytes of row stage_row, floats 4 stage_c4 .. + 3 of the step's 32 (x: j = 0 only)
-static SWD_HD inline int stage_row(int tid, int j) { return (tid + THREADS * j) >> 3; }
-static SWD_HD inline int stage_c4(int tid, int j) { return (tid + THREADS * j) & 7; }
+static C2W_HD inline int stage_row(int tid, int j) { return (tid + THREADS * j) >> 3; }
+static C2W_HD inline int stage_c4(int tid, int j) { return (tid + THREADS * j) & 7; }
 // the 16 bytes lane `lane` of wave `wave` reads of its fields / its projections for k group g of a step: offsets into a buffer
-static SWD_HD inline int frag_a(int wave, int lane, int g) { return ((wave >> 2) * 32 + (lane & 31)) * LDK + 8 * g + 4 * (lane >> 5); }
-static SWD_HD inline int frag_b(int wave, int lane, int g) { return XT_FLOATS + ((wave & 3) * 32 + (lane & 31)) * LDK + 8 * g + 4 * (lane >> 5); }
+static C2W_HD inline int frag_a(int wave, int lane, int g) { return ((wave >> 2) * 32 + (lane & 31)) * LDK + 8 * g + 4 * (lane >> 5); }
+static C2W_HD inline int frag_b(int wave, int lane, int g) { return XT_FLOATS + ((wave & 3) * 32 + (lane & 31)) * LDK + 8 * g + 4 * (lane >> 5); }
 // where register r of lane `lane` of a 32 x 32 result tile lies (the matrix core's C/D map)
-static SWD_HD inline int acc_row(int lane, int r) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-static SWD_HD inline int acc_col(int lane) { return lane & 31; }
+static C2W_HD inline int acc_row(int lane, int r) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+static C2W_HD inline int acc_col(int lane) { return lane & 31; }
 // whether wave `wave` has to multiply at all (else its 32 columns lie past P)
-static SWD_HD inline bool active(int wave, int P) { return (wave & 3) * 32 < P; }
+static C2W_HD inline bool active(int wave, int P) { return (wave & 3) * 32 < P; }
 // proj[rep][f][p][t] of field i = (rep T + t) F + f
-static SWD_HD inline long long out_index(long long i, int p, int T, int F, int P) {
+static C2W_HD inline long long out_index(long long i, int p, int T, int F, int P) {
     const long long rep = i / ((long long)T * F);
     const int t = (int)((i / F) % T), f = (int)(i % F);
     return ((rep * F + f) * P + p) * (long long)T + t;
@@ -108,7 +104,7 @@ struct PThread {
     V16 acc, tot;
 };
 
-static SWD_HD inline void p_init(const PView& v, PThread& th, int tid) {
+static C2W_HD inline void p_init(const PView& v, PThread& th, int tid) {
     long long i = v.first + stage_row(tid, 0);
     if (i > v.n_fields - 1) i = v.n_fields - 1;  // a row past the end reads the last field again and is dropped in the epilogue
     th.xo = i * v.d + 4 * stage_c4(tid, 0);
@@ -122,14 +118,14 @@ static SWD_HD inline void p_init(const PView& v, PThread& th, int tid) {
     for (int r = 0; r < 16; ++r) th.acc[r] = 0.f, th.tot[r] = 0.f;
 }
 
-static SWD_HD inline void p_fetch(const PView& v, PThread& th, int kt) {
+static C2W_HD inline void p_fetch(const PView& v, PThread& th, int kt) {
     th.rx = *(const float4*)(v.x + th.xo + (long long)kt * BK);
 #pragma unroll
     for (int j = 0; j < LOADS; ++j) th.rt[j] = *(const float4*)(v.theta + th.to[j] + (long long)kt * BK);
 }
 
 // x^ = (x - shift) * scale: two roundings, on the loaded value
-static SWD_HD inline void p_stash(const PView& v, const PThread& th, int tid, int buf) {
+static C2W_HD inline void p_stash(const PView& v, const PThread& th, int tid, int buf) {
     float* base = v.lds + buf * BUF_FLOATS;
     const float4 q = th.rx;
     const float s = th.sh, c = th.sc;
@@ -138,7 +134,7 @@ static SWD_HD inline void p_stash(const PView& v, const PThread& th, int tid, in
     for (int j = 0; j < LOADS; ++j) *(float4*)(base + XT_FLOATS + stage_row(tid, j) * LDK + 4 * stage_c4(tid, j)) = th.rt[j];
 }
 
-#ifdef SWD_HOST
+#ifdef C2W_CORE_HOST
 // v_mfma_f32_32x32x2_f32 restated: lane l holds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]; D[i][j] is register
 // (i & 3) + 4 (i >> 3) of lane j + 32 ((i >> 2) & 1); D = fma(A[i][1], B[1][j], fma(A[i][0], B[0][j], C)).
 static inline void mfma_32x32x2_host(const float (&a)[64], const float (&b)[64], V16* (&c)[64]) {
@@ -164,7 +160,7 @@ static inline void p_compute_wave(const PView& v, PThread* th, int wave, int buf
         }
 }
 #else
-static SWD_HD inline void p_compute(const PView& v, PThread& th, int tid, int buf) {
+static C2W_HD inline void p_compute(const PView& v, PThread& th, int tid, int buf) {
     const float* base = v.lds + buf * BUF_FLOATS;
     const int wave = tid >> 6, lane = tid & 63;
     if (!active(wave, v.P)) return;
@@ -178,13 +174,13 @@ static SWD_HD inline void p_compute(const PView& v, PThread& th, int tid, int bu
 #endif
 
 // the chunk's sums join the running sums, in ascending chunk order
-static SWD_HD inline void p_fold(PThread& th) {
+static C2W_HD inline void p_fold(PThread& th) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) th.tot[r] += th.acc[r], th.acc[r] = 0.f;
 }
 
 // epilogue 1: the sums into LDS as [projection][field]
-static SWD_HD inline void p_epi_stash(const PView& v, const PThread& th, int tid) {
+static C2W_HD inline void p_epi_stash(const PView& v, const PThread& th, int tid) {
     const int wave = tid >> 6, lane = tid & 63;
     if (!active(wave, v.P)) return;
     const int n = (wave & 3) * 32 + acc_col(lane);
@@ -193,7 +189,7 @@ static SWD_HD inline void p_epi_stash(const PView& v, const PThread& th, int tid
 }
 
 // epilogue 2: element e = (p, a, b) is field first + b F + a: for one p and a, neighbouring threads write neighbouring t
-static SWD_HD inline void p_epi_write(const PView& v, int tid) {
+static C2W_HD inline void p_epi_write(const PView& v, int tid) {
     const int q = v.F >= BM ? 1 : (BM + v.F - 1) / v.F, per_p = q * v.F;  // F > BM: b = 0 and a = the row, rows past BM skipped
     const long long total = (long long)v.P * per_p;
     for (long long e = tid; e < total; e += THREADS) {
@@ -217,7 +213,7 @@ struct DView {
 };
 
 // phase 0: both columns into LDS, +inf past T; -> whether this thread saw a NaN
-static SWD_HD inline int d_load(const DView& v, int tid) {
+static C2W_HD inline int d_load(const DView& v, int tid) {
     const float* cx = v.px + v.block * v.T;
     const float* cy = v.py + (v.block % ((long long)v.F * v.P)) * v.T;
     int nan = 0;
@@ -230,10 +226,10 @@ static SWD_HD inline int d_load(const DView& v, int tid) {
 }
 
 // the pair compare-exchange `idx` of a stage touches: elements i and i + j of a column, ascending where (i & k) == 0
-static SWD_HD inline int pair_low(int idx, int j) { return ((idx & ~(j - 1)) << 1) | (idx & (j - 1)); }
+static C2W_HD inline int pair_low(int idx, int j) { return ((idx & ~(j - 1)) << 1) | (idx & (j - 1)); }
 
 // phase (k, j): N / 2 compare-exchanges in each of the two columns
-static SWD_HD inline void d_stage(const DView& v, int tid, int k, int j) {
+static C2W_HD inline void d_stage(const DView& v, int tid, int k, int j) {
     const int half = v.N >> 1;
     for (int e = tid; e < v.N; e += v.nthr) {
         const int col = e >= half, i = pair_low(e - col * half, j), l = i + j;
@@ -243,7 +239,7 @@ static SWD_HD inline void d_stage(const DView& v, int tid, int k, int j) {
     }
 }
 
-static SWD_HD inline void d_partial(const DView& v, int tid) {
+static C2W_HD inline void d_partial(const DView& v, int tid) {
     double s = 0.0;
     for (int i = tid; i < v.T; i += v.nthr) {
         const double dd = (double)v.keys[i] - (double)v.keys[v.N + i];
@@ -252,7 +248,7 @@ static SWD_HD inline void d_partial(const DView& v, int tid) {
     v.dpart[tid] = s;
 }
 
-static SWD_HD inline void d_fold(const DView& v, int tid) {
+static C2W_HD inline void d_fold(const DView& v, int tid) {
     if (tid >= 16) return;
     const int n = v.nthr / 16;
     double s = 0.0;
@@ -260,7 +256,7 @@ static SWD_HD inline void d_fold(const DView& v, int tid) {
     v.dpart[1024 + tid] = s;
 }
 
-static SWD_HD inline void d_store(const DView& v, int tid, int nan) {
+static C2W_HD inline void d_store(const DView& v, int tid, int nan) {
     if (tid != 0) return;
     double s = 0.0;
     for (int q = 0; q < 16; ++q) s += v.dpart[1024 + q];

@@ -4,9 +4,6 @@
 // (ordered_sum_launch.h) adds the chunks of a plane in index order when there are several.  temporal_core.h has the index maps and the
 // arithmetic; this file is the workgroup around them.  No float atomics, no sum whose order depends on the launch.
 #include "ordered_sum_launch.h"
-
-#define TINCR_HD __device__ __attribute__((always_inline))
-#define TINCR_BOTH __host__ __device__ __attribute__((always_inline))
 #include "temporal_core.h"
 
 namespace {
@@ -51,12 +48,11 @@ extern "C" long long c2w_tincr_scratch_bytes(long long rows, int T, int F, int h
 extern "C" int c2w_tincr_terms(const float* x, const float* y, double* S, double* scratch, unsigned long long scratch_bytes, int n_rep, int T, int F,
                                int hw, int L, void* stream) {
     if (!tincr::supported(hw, L)) return C2W_ERR_UNSUPPORTED;
-    if (!x || !S || n_rep < 1 || T < 1 || F < 1 || (((uintptr_t)x | (uintptr_t)y) & 15) != 0 || (((uintptr_t)S | (uintptr_t)scratch) & 7) != 0)
-        return C2W_ERR_BAD_ARG;
+    if (!x || !S || n_rep < 1 || T < 1 || F < 1 || !c2w_aligned(16, x, y) || !c2w_aligned(8, S, scratch)) return C2W_ERR_BAD_ARG;
     const int nc = tincr::chunks(hw);
     const long long rows = (long long)n_rep + (y ? 1 : 0), planes = rows * T * F, grid = planes * nc, need = tincr::scratch_bytes(rows, T, F, hw, L);
     if (need > 0 && (!scratch || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     double* out = nc > 1 ? scratch : S;
     if (y)

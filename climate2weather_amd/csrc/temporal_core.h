@@ -1,5 +1,5 @@
 // Temporal increments of an ensemble: the index maps and the arithmetic of temporal.hip, written as barrier-separated phases over
-// "thread tid of a workgroup", as crps_core.h and escore_core.h are.  Compiled for the host (TINCR_HD empty) the same phases run one
+// "thread tid of a workgroup", as crps_core.h and escore_core.h are.  Compiled for the host (core_side.h) the same phases run one
 // thread after the other over a record per thread: tests/host_temporal_main.cpp checks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_tincr_terms).  The rows are r_0 = y when a truth is given, then r_1 .. r_n = x, each [T][F][hw] fp32 read
@@ -24,12 +24,7 @@
 #ifndef C2W_TEMPORAL_CORE_H
 #define C2W_TEMPORAL_CORE_H
 
-#ifndef TINCR_HD
-#define TINCR_HD
-#define TINCR_BOTH
-#define TINCR_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 
 #if defined(__clang__)
 #define TINCR_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -57,21 +52,21 @@ using ordered_sum::nan_if_not_finite;  // the write policy: the kernel finds a n
 
 typedef float F4 __attribute__((vector_size(16)));  // 16 bytes a load
 
-static TINCR_BOTH inline bool supported(int hw, int L) { return hw >= 4 && hw % 4 == 0 && L >= 1 && L <= MAX_L; }
+static C2W_BOTH inline bool supported(int hw, int L) { return hw >= 4 && hw % 4 == 0 && L >= 1 && L <= MAX_L; }
 
 // ---------------------------------------------------------------------------------------------------------------- maps
 
-static TINCR_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
-static TINCR_BOTH inline int chunk_begin(int c) { return c * CHUNK; }
-static TINCR_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
+static C2W_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
+static C2W_BOTH inline int chunk_begin(int c) { return c * CHUNK; }
+static C2W_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
 // rounds of the workgroup over chunk c, and the first of the 4 cells thread tid owns in round `it`
-static TINCR_BOTH inline int rounds(int hw, int c) { return (chunk_end(hw, c) - chunk_begin(c) + 4 * THREADS - 1) / (4 * THREADS); }
-static TINCR_BOTH inline int cell_of(int c, int it, int tid) { return chunk_begin(c) + (it * THREADS + tid) * 4; }
-static TINCR_BOTH inline int passes(int L) { return (L + BATCH - 1) / BATCH; }
+static C2W_BOTH inline int rounds(int hw, int c) { return (chunk_end(hw, c) - chunk_begin(c) + 4 * THREADS - 1) / (4 * THREADS); }
+static C2W_BOTH inline int cell_of(int c, int it, int tid) { return chunk_begin(c) + (it * THREADS + tid) * 4; }
+static C2W_BOTH inline int passes(int L) { return (L + BATCH - 1) / BATCH; }
 // lags of anchor t that have a pair
-static TINCR_BOTH inline int lags_of(int T, int t, int L) { return T - 1 - t < L ? T - 1 - t : L; }
+static C2W_BOTH inline int lags_of(int T, int t, int L) { return T - 1 - t < L ? T - 1 - t : L; }
 // bytes of partial sums: none while a plane is one chunk
-static TINCR_BOTH inline long long scratch_bytes(long long rows, long long T, long long F, int hw, int L) {
+static C2W_BOTH inline long long scratch_bytes(long long rows, long long T, long long F, int hw, int L) {
     return chunks(hw) > 1 ? rows * T * F * chunks(hw) * 3 * L * (long long)sizeof(double) : 0;
 }
 
@@ -91,23 +86,23 @@ struct Thread {
     double acc[SUMS];  // [lag of the pass][column]
 };
 
-static TINCR_HD inline int anchor_of(const View& v) { return (int)((v.plane / v.F) % v.T); }
+static C2W_HD inline int anchor_of(const View& v) { return (int)((v.plane / v.F) % v.T); }
 // plane (t, f) of the row this workgroup owns, and of the truth
-static TINCR_HD inline const float* own_plane(const View& v, int t) {
+static C2W_HD inline const float* own_plane(const View& v, int t) {
     const long long d = v.plane / ((long long)v.T * v.F), f = v.plane % v.F;
     const float* row = v.y ? (d == 0 ? v.y : v.x + (d - 1) * v.T * v.F * v.hw) : v.x + d * v.T * v.F * v.hw;
     return row + ((long long)t * v.F + f) * v.hw;
 }
-static TINCR_HD inline const float* truth_plane(const View& v, int t) { return v.y + ((long long)t * v.F + v.plane % v.F) * v.hw; }
+static C2W_HD inline const float* truth_plane(const View& v, int t) { return v.y + ((long long)t * v.F + v.plane % v.F) * v.hw; }
 
-static TINCR_HD inline void t_init(Thread& th) {
+static C2W_HD inline void t_init(Thread& th) {
 #pragma unroll
     for (int s = 0; s < SUMS; ++s) th.acc[s] = 0.0;
 }
 
 // round `it` of pass `pass`: the lags pass BATCH + 1 .. pass BATCH + BATCH of the thread's 4 cells
 template <bool HAS_Y>
-static TINCR_HD inline void t_round(const View& v, Thread& th, int tid, int pass, int it) {
+static C2W_HD inline void t_round(const View& v, Thread& th, int tid, int pass, int it) {
     TINCR_NO_CONTRACT
     const int cell = cell_of(v.chunk, it, tid);
     if (cell >= chunk_end(v.hw, v.chunk)) return;
@@ -150,9 +145,9 @@ static TINCR_HD inline void t_round(const View& v, Thread& th, int tid, int pass
 
 // the three phases of ordered_sum.h at N = 12: thread s writes sum s of the pass -- lag pass BATCH + s / 3 + 1, column s % 3 -- if the
 // lag is one of the L; +0.0 where the lag has no pair and, without a truth, in the third column
-static TINCR_HD inline void t_stash(const View& v, const Thread& th, int tid) { ordered_sum::stash<SUMS>(v.lds, th.acc, tid); }
-static TINCR_HD inline void t_fold_groups(const View& v, int tid) { ordered_sum::fold_groups<SUMS>(v.lds, tid); }
-static TINCR_HD inline void t_store(const View& v, int tid, int pass, bool folded) {
+static C2W_HD inline void t_stash(const View& v, const Thread& th, int tid) { ordered_sum::stash<SUMS>(v.lds, th.acc, tid); }
+static C2W_HD inline void t_fold_groups(const View& v, int tid) { ordered_sum::fold_groups<SUMS>(v.lds, tid); }
+static C2W_HD inline void t_store(const View& v, int tid, int pass, bool folded) {
     if (tid >= SUMS) return;
     const int tau = pass * BATCH + tid / 3 + 1, col = tid % 3;
     if (tau > v.L) return;
@@ -161,8 +156,8 @@ static TINCR_HD inline void t_store(const View& v, int tid, int pass, bool folde
     v.out[((v.plane * chunks(v.hw) + v.chunk) * v.L + (tau - 1)) * 3 + col] = s;
 }
 // whether pass `pass` of this anchor has a lag with a pair: the same for the whole workgroup
-static TINCR_HD inline bool pass_has_pairs(const View& v, int pass) { return pass * BATCH + 1 <= lags_of(v.T, anchor_of(v), v.L); }
-static TINCR_HD inline void f_fold(const double* partial, double* S, long long entry, int nc, int L) {
+static C2W_HD inline bool pass_has_pairs(const View& v, int pass) { return pass * BATCH + 1 <= lags_of(v.T, anchor_of(v), v.L); }
+static C2W_HD inline void f_fold(const double* partial, double* S, long long entry, int nc, int L) {
     S[entry] = nan_if_not_finite(ordered_sum::fold_parts(partial, entry, nc, 3 * L));
 }
 

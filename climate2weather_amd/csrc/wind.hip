@@ -5,9 +5,6 @@
 // has the table, the lookup, the arithmetic and the index maps; this file is the workgroups around them.  No float atomics, no sum whose
 // order depends on the launch.
 #include "ordered_sum_launch.h"
-
-#define WIND_HD __device__ __attribute__((always_inline))
-#define WIND_BOTH __host__ __device__ __attribute__((always_inline))
 #include "wind_core.h"
 
 namespace {
@@ -55,12 +52,12 @@ extern "C" int c2w_wind_power(const float* fields, int F, int u_index, int v_ind
                               float* derived, double* scratch, unsigned long long scratch_bytes, long long planes, int hw, void* stream) {
     if (!wind::supported(hw, K)) return C2W_ERR_UNSUPPORTED;
     if (!fields || !table || !sums || planes < 1 || F < 1 || u_index < 0 || u_index >= F || v_index < 0 || v_index >= F ||
-        (((uintptr_t)fields | (uintptr_t)table | (uintptr_t)derived) & 15) != 0 || (((uintptr_t)sums | (uintptr_t)scratch) & 7) != 0)
+        !c2w_aligned(16, fields, table, derived) || !c2w_aligned(8, sums, scratch))
         return C2W_ERR_BAD_ARG;
     const int nc = wind::chunks(hw);
     const long long grid = planes * nc, need = wind::scratch_bytes(planes, hw);
     if (need > 0 && (!scratch || scratch_bytes < (unsigned long long)need)) return C2W_ERR_BAD_ARG;
-    if (grid > 0x7fffffffLL) return C2W_ERR_BAD_SHAPE;
+    if (!c2w_grid_fits(grid)) return C2W_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     wind_power_kernel<<<(unsigned)grid, wind::THREADS, 0, st>>>(fields, (const uint4*)table, nc > 1 ? scratch : sums, derived, nc, F, u_index, v_index, K,
                                                                 hub_factor, hw);

@@ -1,5 +1,5 @@
 // Wind power of an ensemble: the table, the interval lookup, the cell arithmetic, the chunk plan and the fold of wind.hip, written as
-// barrier-separated phases over "thread tid of a workgroup", as crps_core.h is.  Compiled for the host (WIND_HD empty) the same phases
+// barrier-separated phases over "thread tid of a workgroup", as crps_core.h is.  Compiled for the host (core_side.h) the same phases
 // run one thread after the other: tests/host_wind_main.cpp checks every map below without a GPU.
 //
 // Definition (c2w_hip.h: c2w_wind_power).  One cell of one (d, t) plane has the fp32 wind components u, v in m/s; with the hub factor
@@ -32,12 +32,7 @@
 #ifndef C2W_WIND_CORE_H
 #define C2W_WIND_CORE_H
 
-#ifndef WIND_HD
-#define WIND_HD
-#define WIND_BOTH
-#define WIND_HOST 1
-#include <cmath>
-#endif
+#include "core_side.h"
 
 #if defined(__clang__)
 #define WIND_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -73,8 +68,8 @@ static_assert(sizeof(Header) == 32 && sizeof(Entry) == 16, "the packed table");
 
 constexpr int MAX_TABLE_BYTES = 32 + 16 * (MAX_K - 1) + 2 * BUCKETS;  // 4624
 
-static WIND_BOTH inline bool supported(int hw, int K) { return hw >= 4 && hw % 4 == 0 && K >= 2 && K <= MAX_K; }
-static WIND_BOTH inline int table_bytes(int K) { return 32 + 16 * (K - 1) + 2 * BUCKETS; }
+static C2W_BOTH inline bool supported(int hw, int K) { return hw >= 4 && hw % 4 == 0 && K >= 2 && K <= MAX_K; }
+static C2W_BOTH inline int table_bytes(int K) { return 32 + 16 * (K - 1) + 2 * BUCKETS; }
 
 struct Table {  // pointers into one packed table
     const Header* h;
@@ -82,7 +77,7 @@ struct Table {  // pointers into one packed table
     const unsigned short* start;
     int K;
 };
-static WIND_BOTH inline Table view_table(const void* bytes, int K) {
+static C2W_BOTH inline Table view_table(const void* bytes, int K) {
     Table t;
     t.h = (const Header*)bytes, t.e = (const Entry*)((const char*)bytes + 32), t.start = (const unsigned short*)((const char*)bytes + 32 + 16 * (K - 1));
     t.K = K;
@@ -92,7 +87,7 @@ static WIND_BOTH inline Table view_table(const void* bytes, int K) {
 // ---------------------------------------------------------------------------------------------------------------- lookup, arithmetic
 
 // s in [x0, xl): monotone in s; (s - x0) inv < BUCKETS (1 + 2^-22), so the conversion is in range
-static WIND_BOTH inline int bucket_of(float s, float x0, float inv) {
+static C2W_BOTH inline int bucket_of(float s, float x0, float inv) {
     WIND_NO_CONTRACT
     const float d = s - x0;
     const int b = (int)(d * inv);
@@ -103,7 +98,7 @@ struct Curve {  // the header's values in registers
     float x0, xl, pl, inv;
     int mode;
 };
-static WIND_BOTH inline Curve curve_of(const Table& t) {
+static C2W_BOTH inline Curve curve_of(const Table& t) {
     Curve c;
     c.x0 = t.h->x0, c.xl = t.h->xl, c.pl = t.h->pl, c.inv = t.h->inv, c.mode = t.h->mode;
     return c;
@@ -112,7 +107,7 @@ static WIND_BOTH inline Curve curve_of(const Table& t) {
 // The powers of four speeds.  Written without a branch that depends on a speed, the four cells side by side: their LDS reads are in
 // flight together, and a lane outside the curve (below the first knot, at or above the last, NaN) looks up the first knot instead and
 // has its value replaced at the end.  The interval of s, x^_0 <= s < x^_{K - 1}, is the largest j <= K - 2 with x^_j <= s.
-static WIND_BOTH inline void powers_of(const Table& t, const Curve& c, const float (&s)[4], float (&p)[4]) {
+static C2W_BOTH inline void powers_of(const Table& t, const Curve& c, const float (&s)[4], float (&p)[4]) {
     WIND_NO_CONTRACT
     const int last = t.K - 2;
     float in[4];
@@ -157,7 +152,7 @@ static WIND_BOTH inline void powers_of(const Table& t, const Curve& c, const flo
     }
 }
 
-static WIND_BOTH inline float speed_of(float u, float v, float hub) {
+static C2W_BOTH inline float speed_of(float u, float v, float hub) {
     WIND_NO_CONTRACT
     const float uu = u * u, vv = v * v;
     const float q = uu + vv;
@@ -204,12 +199,12 @@ static inline int build_table(const double* xs, const double* ps, int K, void* b
 
 // ---------------------------------------------------------------------------------------------------------------- maps
 
-static WIND_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
-static WIND_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
+static C2W_BOTH inline int chunks(int hw) { return (hw + CHUNK - 1) / CHUNK; }
+static C2W_BOTH inline int chunk_end(int hw, int c) { return (c + 1) * CHUNK < hw ? (c + 1) * CHUNK : hw; }
 // the first of the 4 cells thread tid owns in round `it` of chunk c
-static WIND_BOTH inline int cell_of(int c, int it, int tid) { return c * CHUNK + (it * THREADS + tid) * 4; }
+static C2W_BOTH inline int cell_of(int c, int it, int tid) { return c * CHUNK + (it * THREADS + tid) * 4; }
 // bytes of partial sums: none while a plane is one chunk
-static WIND_BOTH inline long long scratch_bytes(long long planes, int hw) {
+static C2W_BOTH inline long long scratch_bytes(long long planes, int hw) {
     return chunks(hw) > 1 ? planes * chunks(hw) * 2 * (long long)sizeof(double) : 0;
 }
 
@@ -234,7 +229,7 @@ struct Thread {
 };
 
 // all the thread's loads of the chunk, 16 bytes each, none used before all are asked for
-static WIND_HD inline void t_fetch(const View& w, Thread& th, int tid) {
+static C2W_HD inline void t_fetch(const View& w, Thread& th, int tid) {
     const float* pu = w.fields + (w.plane * w.F + w.u_index) * w.hw;
     const float* pv = w.fields + (w.plane * w.F + w.v_index) * w.hw;
     const int end = chunk_end(w.hw, w.chunk);
@@ -247,7 +242,7 @@ static WIND_HD inline void t_fetch(const View& w, Thread& th, int tid) {
     th.acc[0] = th.acc[1] = 0.0;
 }
 
-static WIND_HD inline void t_cells(const View& w, Thread& th, int tid) {
+static C2W_HD inline void t_cells(const View& w, Thread& th, int tid) {
     const Curve c = curve_of(w.table);
 #pragma unroll
     for (int it = 0; it < ROUNDS; ++it) {
@@ -267,14 +262,14 @@ static WIND_HD inline void t_cells(const View& w, Thread& th, int tid) {
 
 // the three phases of ordered_sum.h at N = 2: thread s writes the workgroup's entry of sum s, an infinite sum stays; f_fold then
 // writes sums[entry], entry = plane 2 + s, from the chunks in index order
-static WIND_HD inline void t_stash(const View& w, const Thread& th, int tid) { ordered_sum::stash<2>(w.lds, th.acc, tid); }
-static WIND_HD inline void t_fold_groups(const View& w, int tid) { ordered_sum::fold_groups<2>(w.lds, tid); }
-static WIND_HD inline void t_fold_store(const View& w, int tid) {
+static C2W_HD inline void t_stash(const View& w, const Thread& th, int tid) { ordered_sum::stash<2>(w.lds, th.acc, tid); }
+static C2W_HD inline void t_fold_groups(const View& w, int tid) { ordered_sum::fold_groups<2>(w.lds, tid); }
+static C2W_HD inline void t_fold_store(const View& w, int tid) {
     if (tid >= 2) return;
     const double t = ordered_sum::fold_total<2>(w.lds, tid);
     w.out[(w.plane * chunks(w.hw) + w.chunk) * 2 + tid] = ordered_sum::nan_if_nan(t);
 }
-static WIND_HD inline void f_fold(const double* partial, double* sums, long long entry, int nc) {
+static C2W_HD inline void f_fold(const double* partial, double* sums, long long entry, int nc) {
     sums[entry] = ordered_sum::nan_if_nan(ordered_sum::fold_parts(partial, entry, nc, 2));
 }
 

@@ -6,39 +6,15 @@
 // fetched value k (-1: nobody, -2: fetched more than once); it also checks that row i of a thread's registers holds member i of the
 // thread's own cells and that the rows from M on hold +inf.  It has its own main, so it is built with -fsanitize=address,undefined
 // and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 #include "crps_core.h"
 using namespace crps;
-
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static int write_out(const char* path, const std::vector<T>& out) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || (!out.empty() && fwrite(out.data(), sizeof(T), out.size(), fo) != out.size())) return 4;
-    fclose(fo);
-    return 0;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
 
 // one workgroup of crps_terms_kernel<K, V>; owner (if given) collects who fetched what; returns 0 or the number of a failed check
 template <int K, int V>
 static int group(View& v, std::vector<int>* owner, size_t nx) {
     std::vector<Thread<K, V>> th(THREADS);
-    for (int i = 0; i < LDS_DOUBLES; ++i) v.lds[i] = NAN;  // a slot nobody stashed that reaches a sum shows
+    poison(v.lds, LDS_DOUBLES, NAN);  // a slot nobody stashed that reaches a sum shows
     PHASE(t_init(v, th[t]))
     const long long member = (long long)v.T * v.F * v.hw;
     const int n = rounds(v.hw, v.chunk, V);
@@ -88,7 +64,7 @@ static int run(char** a, bool visit) {
     if (visit && nx + ny >= (1u << 24)) return 3;  // an index must be an fp32
     float *x, *y;
     if (visit) {
-        x = (float*)aligned_alloc(16, nx * 4 + 16), y = (float*)aligned_alloc(16, ny * 4 + 16);
+        x = alloc16<float>(nx), y = alloc16<float>(ny);
         for (size_t k = 0; k < nx; ++k) x[k] = (float)k;
         for (size_t k = 0; k < ny; ++k) y[k] = (float)(nx + k);
     } else {
@@ -111,9 +87,9 @@ static int run(char** a, bool visit) {
         for (double p : partial)
             if (p != p) rc = 6;  // a partial nobody wrote (the indices are finite, so no workgroup wrote NaN on purpose)
         std::vector<int> ox(owner.begin(), owner.begin() + nx), oy(owner.begin() + nx, owner.end());
-        if (!rc) rc = write_out(a[4], ox) | write_out(a[5], oy);
+        if (!rc) rc = write_file(a[4], ox) | write_file(a[5], oy);
     } else if (!rc) {
-        rc = write_out(a[7], sums) | write_out(a[8], cells);
+        rc = write_file(a[7], sums) | write_file(a[8], cells);
     }
     free(x), free(y);
     return rc;

@@ -9,12 +9,7 @@
 // exactly once.  `visit_vario` counts the (cell, offset) pairs the threads take up and asserts that every pair with both cells inside
 // the field is visited exactly once and no other, and that the halo holds the field's values where it lies inside.  Both exit with the
 // number of the failed check.  The program has its own main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 
 static std::vector<int>* g_visits = nullptr;  // [plane][offset][cell]
 static long long g_cells = 0, g_offsets = 0;
@@ -23,31 +18,12 @@ static long long g_cells = 0, g_offsets = 0;
 #include "escore_core.h"
 using namespace escore;
 
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static int write_out(const char* path, const std::vector<T>& out) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || (!out.empty() && fwrite(out.data(), sizeof(T), out.size(), fo) != out.size())) return 4;
-    fclose(fo);
-    return 0;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
-
 // -------------------------------------------------------------------------------------------------------------------- pairs
 
 // one workgroup of escore_pairs_kernel; fetched (if given) counts who staged what
 static int pairs_group(PView& v, std::vector<int>* fetched, size_t nx) {
     std::vector<PThread> th(THREADS);
-    memset(v.lds, 0xff, p_lds_bytes(v.M));  // NaNs: a slot nobody wrote that reaches a sum shows
+    poison(v.lds, p_lds_bytes(v.M), 0xff);  // NaNs: a slot nobody wrote that reaches a sum shows
     PHASE(p_stage(v, t))
     if (fetched) {
         const float* rows = (const float*)v.lds;
@@ -78,7 +54,7 @@ static int run_pairs(char** a, bool visit) {
     if (visit && nx + ny >= (1u << 24)) return 3;  // an index must be an fp32
     float *x, *y;
     if (visit) {
-        x = (float*)aligned_alloc(16, nx * 4 + 16), y = (float*)aligned_alloc(16, ny * 4 + 16);
+        x = alloc16<float>(nx), y = alloc16<float>(ny);
         for (size_t k = 0; k < nx; ++k) x[k] = (float)k;
         for (size_t k = 0; k < ny; ++k) y[k] = (float)(nx + k);
     } else {
@@ -105,7 +81,7 @@ static int run_pairs(char** a, bool visit) {
     }
     if (nc > 1)
         for (long long e = 0; e < planes * P; ++e) p_fold(partial.data(), d2.data(), e, nc, P);
-    if (!rc && !visit) rc = write_out(a[5], d2);
+    if (!rc && !visit) rc = write_file(a[5], d2);
     free(x), free(y);
     return rc;
 }
@@ -114,7 +90,7 @@ static int run_pairs(char** a, bool visit) {
 
 template <int ORDER2>
 static int vario_group(VView& v, bool visit, size_t nx) {
-    memset(v.lds, 0xff, v_lds_bytes(v.R, v.M));
+    poison(v.lds, v_lds_bytes(v.R, v.M), 0xff);
     PHASE(v_stage(v, t))
     if (visit) {  // the patch holds the field's own indices inside the field and zeros outside
         const float* patch = (const float*)v.lds;
@@ -148,7 +124,7 @@ static int run_vario(char** a, bool visit) {
     if (visit && nx + ny >= (1u << 24)) return 3;
     float *x, *y;
     if (visit) {
-        x = (float*)aligned_alloc(16, nx * 4 + 16), y = (float*)aligned_alloc(16, ny * 4 + 16);
+        x = alloc16<float>(nx), y = alloc16<float>(ny);
         for (size_t k = 0; k < nx; ++k) x[k] = (float)k;
         for (size_t k = 0; k < ny; ++k) y[k] = (float)(nx + k);
     } else {
@@ -184,7 +160,7 @@ static int run_vario(char** a, bool visit) {
     }
     if (nt > 1)
         for (long long e = 0; e < planes * O * 3; ++e) v_fold(partial.data(), V.data(), e, nt, O * 3);
-    if (!rc && !visit) rc = write_out(a[8], V);
+    if (!rc && !visit) rc = write_file(a[8], V);
     free(x), free(y);
     return rc;
 }

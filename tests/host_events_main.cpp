@@ -9,11 +9,7 @@
 // cumulative table read (as often as the windows clipped to the DOMAIN say), and compare the tables with a direct count.  LDS is
 // filled with a pattern before every workgroup, so a slot nobody zeroed shows.  It has its own main, so it is built with
 // -fsanitize=address,undefined and run directly.
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 
 static int g_H = 0, g_W = 0, g_hw = 0, g_K = 0, g_S = 0, g_M = 0, g_bad = 0;
 static std::vector<long long> g_cells, g_loads, g_sums, g_corners;  // [plane][k][cell]; [d][cell]; [d][s][cell]; [s][(H + 1) (W + 1)]
@@ -43,26 +39,6 @@ static void visit_corner(int d, int s, int gy, int gx) {
 #include "events_core.h"
 using namespace events;
 
-template <typename T>
-static T* alloc16(size_t n) { return (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16); }
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = alloc16<T>(n);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-template <typename T>
-static int write_file(const char* path, const std::vector<T>& v) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || fwrite(v.data(), sizeof(T), v.size(), fo) != v.size()) return 4;
-    fclose(fo);
-    return 0;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
-
 struct Inputs {
     float *x, *y, *thr;
     int* dir;
@@ -80,7 +56,7 @@ static Inputs synthetic(int M, int T, int F, int hw, int K) {
 static void release(Inputs& in) { free(in.x), free(in.y), free(in.thr), free(in.dir); }
 
 static void counts_group(CView& v) {
-    for (int i = 0; i < COUNT_LDS_INTS; ++i) v.lds[i] = 0x55555555;
+    poison(v.lds, COUNT_LDS_INTS, 0x55555555);
     PHASE(c_zero(v, t))
     PHASE(c_count(v, t))
     PHASE(c_derive(v, t))
@@ -127,7 +103,7 @@ static int run_counts(char** a, bool visit) {
 }
 
 static void fss_group(FView& v) {
-    memset(v.lds, 0xA5, FSS_LDS_BYTES);
+    poison(v.lds, FSS_LDS_BYTES, 0xA5);
     const Geo g = geo_of(v.H, v.W, v.R, v.tile);
     PHASE(f_zero(v, t))
     for (int d = 0; d <= v.M; ++d) {

@@ -6,40 +6,15 @@
 // `visit` fills x and y with their own indices, so what a workgroup fetched says where it read: owner[k] is the one data set that
 // fetched value k (-1: nobody, -2: fetched more than once); it also checks that every grid point belongs to exactly one (thread,
 // register).  It has its own main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-struct alignas(16) float4 { float x, y, z, w; };
+#include "host_main.h"
 #include "kde_core.h"
 using namespace kde;
-
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static int write_out(const char* path, const std::vector<T>& out) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || fwrite(out.data(), sizeof(T), out.size(), fo) != out.size()) return 4;
-    fclose(fo);
-    return 0;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
 
 // one workgroup of kde_partial_kernel<P>; seen (if given) collects the floats every thread fetched
 template <int P>
 static void partial_group(KView& v, std::vector<float>* seen) {
     std::vector<KThread<P>> th(THREADS);
-    for (int i = 0; i < THREADS; ++i) v.lds[i] = float4{NAN, NAN, NAN, NAN};  // a value nothing staged that reaches a sum shows
+    poison(v.lds, THREADS, float4{NAN, NAN, NAN, NAN});  // a value nothing staged that reaches a sum shows
     PHASE(k_init(v, th[t], t))
     const long long tiles = k_tiles(th[0]);
     auto fetch = [&](long long tile) {
@@ -81,10 +56,10 @@ static int density(char** a, bool visit) {
     float *x, *y = nullptr, *off, *pivot;
     double* h;
     if (visit) {
-        x = (float*)aligned_alloc(16, nx * 4 + 16), y = (float*)aligned_alloc(16, ny * 4 + 16);
+        x = alloc16<float>(nx), y = alloc16<float>(ny);
         for (size_t k = 0; k < nx; ++k) x[k] = (float)k;
         for (size_t k = 0; k < ny; ++k) y[k] = (float)(nx + k);
-        off = (float*)calloc((size_t)F * N, 4), pivot = (float*)calloc(F, 4), h = (double*)aligned_alloc(16, (D * 8 + 15) / 16 * 16 + 16);
+        off = (float*)calloc((size_t)F * N, 4), pivot = (float*)calloc(F, 4), h = alloc16<double>((size_t)D);
         for (long long i = 0; i < D; ++i) h[i] = 1.0;
     } else {
         x = read_file<float>(a[6], nx);
@@ -117,9 +92,9 @@ static int density(char** a, bool visit) {
         for (double p : partial)
             if (p != p) rc = 6;  // a partial nobody wrote (the indices are finite, so no workgroup wrote NaN on purpose)
         std::vector<int> ox(owner.begin(), owner.begin() + nx), oy(owner.begin() + nx, owner.end());
-        if (!rc) rc = write_out(a[5], ox) | write_out(a[6], oy);
+        if (!rc) rc = write_file(a[5], ox) | write_file(a[6], oy);
     } else {
-        rc = write_out(a[11], dens);
+        rc = write_file(a[11], dens);
     }
     free(lds), free(x), free(y), free(off), free(pivot), free(h);
     return rc;
@@ -135,13 +110,13 @@ static int pit(char** a) {
     PView v{};
     v.x = x, v.y = y, v.counts = counts.data(), v.grid = grid, v.M = M, v.T = T, v.F = F, v.hw = hw, v.hist = hist.data();
     for (v.block = 0; v.block < grid; ++v.block) {
-        for (auto& q : hist) q = -1000000;  // a bin nobody zeroed shows
+        poison(hist.data(), hist.size(), -1000000);  // a bin nobody zeroed shows
         PHASE(pit_zero(v, t))
         PHASE(pit_count(v, t))
         PHASE(pit_flush(v, t))
     }
     free(x), free(y);
-    return write_out(a[7], counts);
+    return write_file(a[7], counts);
 }
 
 int main(int argc, char** argv) {

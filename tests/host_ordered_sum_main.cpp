@@ -4,54 +4,35 @@
 //   host_ordered_sum parts outer parts inner policy partial.f64 out.f64   partial [outer][parts][inner] -> out [outer][inner]
 // policy: 0 nan_if_nan, 1 nan_if_not_finite; N: 1, 2, 4 or 12.  The LDS starts as NaNs, so a slot nobody wrote that reaches a sum shows.
 // It has its own main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 #include "ordered_sum.h"
 using namespace ordered_sum;
 
-static std::vector<double> read_file(const char* path, size_t n) {
-    std::vector<double> v(n);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(v.data(), sizeof(double), n, fi) != n) exit(2);
-    fclose(fi);
-    return v;
-}
-
-static int write_out(const char* path, const std::vector<double>& out) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || (!out.empty() && fwrite(out.data(), sizeof(double), out.size(), fo) != out.size())) return 4;
-    fclose(fo);
-    return 0;
-}
-
 static double written(int policy, double t) { return policy ? nan_if_not_finite(t) : nan_if_nan(t); }
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
 
 template <int N>
 static int workgroup(int policy, const char* in, const char* out_path) {
-    const std::vector<double> acc = read_file(in, (size_t)N * THREADS);
+    double* acc = read_file<double>(in, (size_t)N * THREADS, 0);
     std::vector<double> lds(lds_doubles<N>(), NAN), out(N, -7.25);
     double mine[THREADS][N];
     for (int t = 0; t < THREADS; ++t)
         for (int s = 0; s < N; ++s) mine[t][s] = acc[(size_t)s * THREADS + t];
+    free(acc);
     PHASE(stash<N>(lds.data(), mine[t], t))
     PHASE(fold_groups<N>(lds.data(), t))
     PHASE(if (t < N) out[t] = written(policy, fold_total<N>(lds.data(), t)))
-    return write_out(out_path, out);
+    return write_file(out_path, out);
 }
 
 static int parts(char** a) {
     const long long outer = atoll(a[0]), np = atoll(a[1]), inner = atoll(a[2]);
     const int policy = atoi(a[3]);
     if (outer < 1 || np < 1 || inner < 1) return 3;
-    const std::vector<double> partial = read_file(a[4], (size_t)(outer * np * inner));
+    double* partial = read_file<double>(a[4], (size_t)(outer * np * inner), 0);
     std::vector<double> out((size_t)(outer * inner), -7.25);
-    for (long long e = 0; e < outer * inner; ++e) out[(size_t)e] = written(policy, fold_parts(partial.data(), e, np, inner));
-    return write_out(a[5], out);
+    for (long long e = 0; e < outer * inner; ++e) out[(size_t)e] = written(policy, fold_parts(partial, e, np, inner));
+    free(partial);
+    return write_file(a[5], out);
 }
 
 int main(int argc, char** argv) {

@@ -24,6 +24,6 @@ def build(tmp_path_factory, stem, *, sanitize, fp_contract_off=False, debug=None
     flags = ["-O1"] + (["-g"] if (sanitize if debug is None else debug) else []) + ["-std=c++17"]
     flags += ["-ffp-contract=off"] if fp_contract_off else []
     flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-    subprocess.run(cxx() + flags + ["-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), os.path.join(ROOT, "tests", f"host_{stem}_main.cpp"),
-                                    "-o", str(exe)], check=True, timeout=timeout)
+    includes = ["-I" + os.path.join(ROOT, "climate2weather_amd", "csrc"), "-I" + os.path.join(ROOT, "tests")]  # the cores; host_main.h
+    subprocess.run(cxx() + flags + includes + [os.path.join(ROOT, "tests", f"host_{stem}_main.cpp"), "-o", str(exe)], check=True, timeout=timeout)
     return exe

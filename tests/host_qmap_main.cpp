@@ -5,12 +5,7 @@
 // `nodes` walks the cells in blocks of `block`, as the host layer does; it fails if the network leaves a series unsorted or an output
 // is left unwritten.  `apply` works in place and counts, through QMAP_VISIT, how often every element is taken up: exactly once.  It
 // has its own main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 
 static std::vector<int>* g_visits = nullptr;
 static void visit4(long long at) {
@@ -19,25 +14,6 @@ static void visit4(long long at) {
 #define QMAP_VISIT(index) visit4(index)
 #include "qmap_core.h"
 using namespace qmap;
-
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || (n && fread(p, sizeof(T), n, fi) != n)) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static bool write_file(const char* path, const T* p, size_t n) {
-    FILE* fo = fopen(path, "wb");
-    const bool ok = fo && fwrite(p, sizeof(T), n, fo) == n;
-    if (fo) fclose(fo);
-    return ok;
-}
-
-#define PHASE(n, call) for (int t = 0; t < (n); ++t) { call; }
 
 static int run_nodes(char** a) {
     const int n_rep = atoi(a[0]), T = atoi(a[1]), F = atoi(a[2]), hw = atoi(a[3]), G = atoi(a[4]), K = atoi(a[5]), skipna = atoi(a[6]), block = atoi(a[7]);
@@ -65,9 +41,9 @@ static int run_nodes(char** a) {
         for (gv.row = 0; gv.row < rows; ++gv.row)
             for (gv.ctile = 0; gv.ctile < tiles(c1 - c0); ++gv.ctile)
                 for (gv.ptile = 0; gv.ptile < tiles(Tu); ++gv.ptile) {
-                    for (float& v : tile) v = -12345.0f;
-                    PHASE(THREADS, g_load(gv, t))
-                    PHASE(THREADS, g_store(gv, t))
+                    poison(tile.data(), tile.size(), -12345.0f);
+                    PHASE(g_load(gv, t))
+                    PHASE(g_store(gv, t))
                 }
         SView sv{};
         sv.scratch = scratch.data(), sv.goff = goff, sv.levels = levels, sv.q = q.data(), sv.nvalid = nvalid.data();
@@ -75,21 +51,22 @@ static int run_nodes(char** a) {
         sv.nthr = sort_threads(padded(max_len)), sv.keys = keys.data();
         const long long series = rows * (c1 - c0) * G;
         for (sv.series = 0; sv.series < series; ++sv.series) {
-            for (unsigned& k : keys) k = 12345u;
-            PHASE(sv.nthr, s_load(sv, t))
+            poison(keys.data(), keys.size(), 12345u);
+            PHASE_N(sv.nthr, s_load(sv, t))
             const int N = padded(length_of(sv));
             for (int k = 2; k <= N; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) PHASE(sv.nthr, s_stage(sv, t, k, j))
+                for (int j = k >> 1; j > 0; j >>= 1) PHASE_N(sv.nthr, s_stage(sv, t, k, j))
             for (int i = 1; i < N; ++i)
                 if (keys[i - 1] > keys[i]) return 6;  // the network sorts
-            PHASE(sv.nthr, s_nodes(sv, t))
+            PHASE_N(sv.nthr, s_nodes(sv, t))
         }
     }
     for (long long n : nvalid)
         if (n < 0) return 7;  // an entry nobody wrote
     for (double v : q)
         if (!memcmp(&v, &unwritten, 8)) return 7;
-    const int rc = write_file(a[12], q.data(), q.size()) && write_file(a[13], nvalid.data(), nvalid.size()) ? 0 : 4;
+    int rc = write_file(a[12], q);
+    if (!rc) rc = write_file(a[13], nvalid);
     free(x), free(tidx), free(goff), free(levels);
     return rc;
 }
@@ -114,16 +91,16 @@ static int run_apply(char** a) {
         for (v.f = 0; v.f < F; ++v.f)
             for (v.cblock = 0; v.cblock < cell_blocks(hw, K); ++v.cblock)
                 for (v.slab = 0; v.slab < slabs; ++v.slab) {
-                    for (double& d : lds) d = NAN;
-                    PHASE(APPLY_THREADS, a_stage(v, t))
-                    PHASE(APPLY_THREADS, a_walk(v, t))
+                    poison(lds.data(), lds.size(), NAN);
+                    PHASE_N(APPLY_THREADS, a_stage(v, t))
+                    PHASE_N(APPLY_THREADS, a_walk(v, t))
                 }
     int rc = 0;
     std::vector<char> listed(T, 0);
     for (int p = 0; p < goff[G]; ++p) listed[tidx[p]] = 1;
     for (size_t i = 0; i < n && !rc; ++i)
         if (visits[i] != listed[(i / ((size_t)F * hw)) % T]) rc = 5;
-    if (!rc && !write_file(a[12], x, n)) rc = 4;
+    if (!rc) rc = write_file(a[12], x, n);
     free(x), free(xq), free(yq), free(tidx), free(goff);
     return rc;
 }

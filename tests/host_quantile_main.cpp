@@ -5,31 +5,9 @@
 // `visit` fills x and y with their own indices, so what a workgroup loaded says where it read: owner[k] is the one data set that
 // loaded value k (-1: nobody, -2: loaded more than once), in every one of the three passes; it also checks that the pass-0 table of
 // every data set sums to n.  It has its own main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 #include "quantile_core.h"
 using namespace qnt;
-
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static int write_out(const char* path, const std::vector<T>& out) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || fwrite(out.data(), sizeof(T), out.size(), fo) != out.size()) return 4;
-    fclose(fo);
-    return 0;
-}
 
 struct Run {
     const float *x, *y;
@@ -56,7 +34,7 @@ static void select(Run& r, std::vector<double>& out, std::vector<float>& stats, 
     for (int pass = 0; pass < 3; ++pass) {
         if (r.owner) std::fill(r.owner->begin(), r.owner->end(), -1);
         for (long long b = 0; b < D * r.slabs; ++b) {
-            memset(lds, 0x5A, (size_t)count_lds_bytes(pass, r.Q));  // a counter nobody zeroed shows
+            poison(lds, (size_t)count_lds_bytes(pass, r.Q), 0x5A);  // a counter nobody zeroed shows
             CView v{};
             v.x = r.x, v.y = r.y, v.n_x = n_x, v.ds = b / r.slabs, v.slab = (int)(b % r.slabs), v.slabs = r.slabs, v.T = r.T, v.F = r.F, v.hw = r.hw;
             v.pass = pass, v.R = R, v.owner = r.owner ? r.owner->data() : nullptr;
@@ -124,7 +102,7 @@ static int visit(char** a) {
     if (!supported(r.hw, r.Q) || r.n_rep < 1 || r.T < 1 || r.F < 1 || r.slabs < 1) return 3;
     const size_t nx = (size_t)r.n_rep * r.T * r.F * r.hw, ny = (size_t)r.T * r.F * r.hw;
     if (nx + ny >= (1u << 24)) return 3;  // an index must be an fp32
-    float *x = (float*)aligned_alloc(16, nx * 4 + 16), *y = (float*)aligned_alloc(16, ny * 4 + 16);
+    float *x = alloc16<float>(nx), *y = alloc16<float>(ny);
     for (size_t k = 0; k < nx; ++k) x[k] = (float)k;
     for (size_t k = 0; k < ny; ++k) y[k] = (float)(nx + k);
     const long long D = (r.n_rep + 1) * r.F;
@@ -145,7 +123,7 @@ static int visit(char** a) {
     }
     owner = r.owner0;
     std::vector<int> ox(owner.begin(), owner.begin() + nx), oy(owner.begin() + nx, owner.end());
-    const int rc = write_out(a[5], ox) | write_out(a[6], oy);
+    const int rc = write_file(a[5], ox) | write_file(a[6], oy);
     free(x), free(y);
     return rc;
 }
@@ -165,7 +143,7 @@ static int select_mode(char** a) {
     std::vector<long long> nvalid((size_t)D, -7);
     r.x = x, r.y = y, r.q = q;
     select(r, out, stats, nvalid);
-    const int rc = r.rc | write_out(a[11], out) | write_out(a[12], stats) | write_out(a[13], nvalid);
+    const int rc = r.rc | write_file(a[11], out) | write_file(a[12], stats) | write_file(a[13], nvalid);
     free(x), free(y), free(q);
     return rc;
 }

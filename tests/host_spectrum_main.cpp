@@ -1,12 +1,7 @@
 // Host driver for csrc/spectrum_core.h: runs the kernel's nine phases one thread after the other over the fields of a file
 // (tests/test_spectra_cpu.py: the index maps and the arithmetic of csrc/spectrum.hip without a GPU).
 //   host_spectrum N n_fields in.f32 out.f32
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-struct alignas(16) float4 { float x, y, z, w; };
+#include "host_main.h"
 #include "spectrum_core.h"
 using namespace spectrum;
 
@@ -20,11 +15,11 @@ void run(const float* x, float* spec, long long nf) {
     for (int j = 0; j < N; ++j) tw[j] = twiddle128(j * (128 / N));
     for (long long f = 0; f < nf; ++f) {
         FieldView v{x + f * N * N, spec + f * P::R, img.data(), tw.data(), d.data(), d.data() + P::TPF, c.data()};
-        for (auto& e : img) e = NAN;  // a read of the row padding, or of a slot nothing wrote, shows in the output
-#define PHASE(fn) for (int t = 0; t < P::TPF; ++t) fn<N>(v, t);
-        PHASE(phase_load) PHASE(phase_fold) PHASE(phase_rows_a) PHASE(phase_rows_b) PHASE(phase_untangle)
-        PHASE(phase_cols_a) PHASE(phase_cols_b) PHASE(phase_bins) PHASE(phase_store)
-#undef PHASE
+        poison(img.data(), img.size(), NAN);  // a read of the row padding, or of a slot nothing wrote, shows in the output
+#define FIELD_PHASE(fn) PHASE_N(P::TPF, fn<N>(v, t))
+        FIELD_PHASE(phase_load) FIELD_PHASE(phase_fold) FIELD_PHASE(phase_rows_a) FIELD_PHASE(phase_rows_b) FIELD_PHASE(phase_untangle)
+        FIELD_PHASE(phase_cols_a) FIELD_PHASE(phase_cols_b) FIELD_PHASE(phase_bins) FIELD_PHASE(phase_store)
+#undef FIELD_PHASE
     }
 }
 
@@ -32,11 +27,8 @@ int main(int argc, char** argv) {
     if (argc != 5) return 1;
     const int N = atoi(argv[1]);
     const long long nf = atoll(argv[2]);
-    float* x = (float*)aligned_alloc(16, (size_t)nf * N * N * 4);
+    float* x = read_file<float>(argv[3], (size_t)nf * N * N, 0);  // no slack: a read past the last field shows
     std::vector<float> s((size_t)nf * N / 2);
-    FILE* fi = fopen(argv[3], "rb");
-    if (!fi || fread(x, 4, (size_t)nf * N * N, fi) != (size_t)(nf * N * N)) return 2;
-    fclose(fi);
     switch (N) {
         case 8: run<8>(x, s.data(), nf); break;
         case 16: run<16>(x, s.data(), nf); break;
@@ -45,9 +37,6 @@ int main(int argc, char** argv) {
         case 128: run<128>(x, s.data(), nf); break;
         default: return 3;
     }
-    FILE* fo = fopen(argv[4], "wb");
-    if (!fo || fwrite(s.data(), 4, s.size(), fo) != s.size()) return 4;
-    fclose(fo);
     free(x);
-    return 0;
+    return write_file(argv[4], s);
 }

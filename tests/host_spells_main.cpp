@@ -9,11 +9,7 @@
 // is read exactly once per threshold group and every state entry loaded and stored exactly once, nothing out of range.  LDS is filled
 // with a pattern before every workgroup, so a slot nobody zeroed shows.  It has its own main, so it is built with
 // -fsanitize=address,undefined and run directly.
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 
 static bool g_visit = false;
 static int g_bad = 0, g_D = 0, g_T = 0, g_F = 0, g_hw = 0, g_groups = 0;
@@ -35,26 +31,6 @@ static void visit_state(std::vector<int>& seen, long long at) {
 #include "spells_core.h"
 using namespace spells;
 
-template <typename T>
-static T* alloc16(size_t n) { return (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16); }
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = alloc16<T>(n);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-template <typename T>
-static int write_file(const char* path, const T* p, size_t n) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || fwrite(p, sizeof(T), n, fo) != n) return 4;
-    fclose(fo);
-    return 0;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
-
 struct Tables {
     int* state;
     long long *hist, *onsets, *invalid;
@@ -74,7 +50,7 @@ static void update(const float* x, const float* y, const float* thr, const int* 
         for (v.d = 0; v.d < v.D; ++v.d)
             for (v.f = 0; v.f < F; ++v.f)
                 for (v.chunk = 0; v.chunk < chunks(hw); ++v.chunk) {
-                    for (int i = 0; i < LDS_INTS; ++i) lds[i] = 0x55555555;
+                    poison(v.lds, LDS_INTS, 0x55555555);
                     PHASE(s_zero(v, t))
                     PHASE(s_walk(v, t))
                     PHASE(s_flush(v, t))

@@ -1,12 +1,7 @@
 // Host driver for csrc/ssim_core.h: runs the kernel's phases one thread after the other, workgroup by workgroup, over the pairs of two
 // files (tests/test_ssim_cpu.py: the index maps and the arithmetic of csrc/ssim.hip without a GPU).
 //   host_ssim H W win n_pairs n_truth x.f32 y.f32 range.f32 out.f64
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-struct alignas(16) float4 { float x, y, z, w; };
+#include "host_main.h"
 #include "ssim_core.h"
 using namespace ssim;
 
@@ -20,8 +15,7 @@ void run(View v, int H, int W) {
     v.ringA = f, v.ringB = f + P::RING_FLOATS, v.V = f + 2 * P::RING_FLOATS;
     v.dpart = d.data(), v.dlev = d.data() + THREADS;
     for (v.first = 0; v.first < v.n_pairs; v.first += sh.FPW) {
-        for (int i = 0; i < P::FLOATS; ++i) f[i] = NAN;  // a value nothing wrote that reaches a kept sum shows in the output
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
+        poison(f, P::FLOATS, NAN);  // a value nothing wrote that reaches a kept sum shows in the output
         PHASE(phase_pivot_partial(v, sh, t))
         PHASE(phase_pivot_fold(v, sh, t))
         PHASE(phase_prologue<WIN>(v, sh, th[t], t))
@@ -35,17 +29,8 @@ void run(View v, int H, int W) {
         PHASE(phase_partial(v, th[t], t))
         PHASE(phase_fold(v, sh, t))
         PHASE(phase_store(v, sh, t))
-#undef PHASE
     }
     free(f);
-}
-
-static float* read_f32(const char* path, size_t n) {
-    float* p = (float*)aligned_alloc(16, (n * 4 + 15) / 16 * 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, 4, n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
 }
 
 int main(int argc, char** argv) {
@@ -54,9 +39,9 @@ int main(int argc, char** argv) {
     const long long np = atoll(argv[4]), nt = atoll(argv[5]);
     if (!supported(H, W, win) || np < 0 || nt < 1) return 3;
     View v{};
-    float* x = read_f32(argv[6], (size_t)np * H * W);
-    float* y = read_f32(argv[7], (size_t)nt * H * W);
-    float* r = read_f32(argv[8], (size_t)nt);
+    float* x = read_file<float>(argv[6], (size_t)np * H * W, 0);  // no slack: a read past an input shows
+    float* y = read_file<float>(argv[7], (size_t)nt * H * W, 0);
+    float* r = read_file<float>(argv[8], (size_t)nt, 0);
     std::vector<double> out((size_t)np, -7.25);
     v.x = x, v.y = y, v.range = r, v.out = out.data(), v.n_pairs = np, v.n_truth = nt;
     switch (win) {
@@ -64,9 +49,6 @@ int main(int argc, char** argv) {
         case 11: run<11>(v, H, W); break;
         default: run<15>(v, H, W); break;
     }
-    FILE* fo = fopen(argv[9], "wb");
-    if (!fo || fwrite(out.data(), 8, out.size(), fo) != out.size()) return 4;
-    fclose(fo);
     free(x), free(y), free(r);
-    return 0;
+    return write_file(argv[9], out);
 }

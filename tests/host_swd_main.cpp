@@ -3,38 +3,16 @@
 //   host_swd project  n_rep T F d P x.f32 theta.f32 shift.f32 scale.f32 proj.f32
 //   host_swd distance n_rep F P T proj_x.f32 proj_y.f32 out.f64
 // It has its own main, so it may be built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-struct alignas(16) float4 { float x, y, z, w; };
+#include "host_main.h"
 #include "swd_core.h"
 using namespace swd;
-
-static float* read_f32(const char* path, size_t n) {
-    float* p = (float*)aligned_alloc(16, (n * 4 + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, 4, n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static int write_out(const char* path, const std::vector<T>& out) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || fwrite(out.data(), sizeof(T), out.size(), fo) != out.size()) return 4;
-    fclose(fo);
-    return 0;
-}
 
 static int project(char** a) {
     const long long n_rep = atoll(a[0]);
     const int T = atoi(a[1]), F = atoi(a[2]), d = atoi(a[3]), P = atoi(a[4]);
     if (!project_supported(d, P) || n_rep < 1 || T < 1 || F < 1) return 3;
     const long long n_fields = n_rep * T * F;
-    float *x = read_f32(a[5], (size_t)n_fields * d), *theta = read_f32(a[6], (size_t)P * d), *shift = read_f32(a[7], F), *scale = read_f32(a[8], F);
+    float *x = read_file<float>(a[5], (size_t)n_fields * d), *theta = read_file<float>(a[6], (size_t)P * d), *shift = read_file<float>(a[7], F), *scale = read_file<float>(a[8], F);
     std::vector<float> out((size_t)n_fields * P, -7.25f);
     float* lds = (float*)aligned_alloc(16, sizeof(float) * LDS_FLOATS);
     std::vector<PThread> th(THREADS);
@@ -43,8 +21,7 @@ static int project(char** a) {
     v.n_fields = n_fields, v.T = T, v.F = F, v.d = d, v.P = P, v.lds = lds;
     const int steps = d / BK;
     for (v.first = 0; v.first < n_fields; v.first += BM) {
-        for (int i = 0; i < LDS_FLOATS; ++i) lds[i] = NAN;  // a value nothing wrote that reaches a kept sum shows in the output
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
+        poison(lds, LDS_FLOATS, NAN);  // a value nothing wrote that reaches a kept sum shows in the output
         PHASE(p_init(v, th[t], t))
         PHASE(p_fetch(v, th[t], 0))
         PHASE(p_stash(v, th[t], t, 0))
@@ -54,12 +31,12 @@ static int project(char** a) {
             if ((kt + 1) % FOLD == 0 || kt + 1 == steps) PHASE(p_fold(th[t]))
             if (kt + 1 < steps) PHASE(p_stash(v, th[t], t, (kt + 1) & 1))
         }
-        for (int i = 0; i < LDS_FLOATS; ++i) lds[i] = NAN;
+        poison(lds, LDS_FLOATS, NAN);
         PHASE(p_epi_stash(v, th[t], t))
         PHASE(p_epi_write(v, t))
     }
     free(lds), free(x), free(theta), free(shift), free(scale);
-    return write_out(a[9], out);
+    return write_file(a[9], out);
 }
 
 static int distance(char** a) {
@@ -67,15 +44,14 @@ static int distance(char** a) {
     const int F = atoi(a[1]), P = atoi(a[2]), T = atoi(a[3]);
     if (!distance_supported(T) || n_rep < 1 || F < 1 || P < 1) return 3;
     const long long n = n_rep * F * P;
-    float *px = read_f32(a[4], (size_t)n * T), *py = read_f32(a[5], (size_t)F * P * T);
+    float *px = read_file<float>(a[4], (size_t)n * T), *py = read_file<float>(a[5], (size_t)F * P * T);
     std::vector<double> out((size_t)n, -7.25), dpart(SORT_DOUBLES);
     DView v{};
     v.px = px, v.py = py, v.out = out.data(), v.F = F, v.P = P, v.T = T, v.N = padded(T), v.nthr = sort_threads(v.N);
     std::vector<float> keys(2 * (size_t)v.N);
     v.keys = keys.data(), v.dpart = dpart.data();
     for (v.block = 0; v.block < n; ++v.block) {
-        for (auto& k : keys) k = NAN;
-        for (auto& p : dpart) p = NAN;
+        poison(keys.data(), keys.size(), NAN), poison(dpart.data(), dpart.size(), NAN);
         int nan = 0;
         for (int t = 0; t < v.nthr; ++t) nan |= d_load(v, t);
         if (!nan) {
@@ -88,7 +64,7 @@ static int distance(char** a) {
         for (int t = 0; t < v.nthr; ++t) d_store(v, t, nan);
     }
     free(px), free(py);
-    return write_out(a[6], out);
+    return write_file(a[6], out);
 }
 
 int main(int argc, char** argv) {

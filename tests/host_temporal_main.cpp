@@ -5,12 +5,7 @@
 // `visit` counts, through TINCR_VISIT, how often every (cell, lag) of every anchor plane is taken up: exactly once where the lag has a
 // pair, never where it has none; it also checks that every entry of the output and of the partial sums was written.  It has its own
 // main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 
 static std::vector<int>* g_visits = nullptr;  // [plane][lag - 1][cell]
 static int g_hw = 0, g_L = 0;
@@ -22,21 +17,10 @@ static void visit4(long long plane, int cell, int tau) {
 #include "temporal_core.h"
 using namespace tincr;
 
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
-
 // one workgroup of tincr_terms_kernel<HAS_Y>
 template <bool HAS_Y>
 static void group(View& v) {
-    for (int i = 0; i < LDS_DOUBLES; ++i) v.lds[i] = NAN;  // a slot nobody stashed that reaches a sum shows
+    poison(v.lds, LDS_DOUBLES, NAN);  // a slot nobody stashed that reaches a sum shows
     const int n = rounds(v.hw, v.chunk), np = passes(v.L);
     for (int pass = 0; pass < np; ++pass) {
         if (!pass_has_pairs(v, pass)) {
@@ -58,7 +42,7 @@ static int run(char** a, bool visit) {
     const size_t ny = (size_t)T * F * hw, nx = (size_t)n_rep * ny;
     float *x, *y = nullptr;
     if (visit) {
-        x = (float*)aligned_alloc(16, nx * 4 + 16), y = (float*)aligned_alloc(16, ny * 4 + 16);
+        x = alloc16<float>(nx), y = alloc16<float>(ny);
         for (size_t k = 0; k < nx; ++k) x[k] = (float)(k % 1021) * 0.25f;
         for (size_t k = 0; k < ny; ++k) y[k] = (float)(k % 1019) * 0.5f;
     } else {
@@ -94,9 +78,7 @@ static int run(char** a, bool visit) {
                     }
         }
     } else if (!rc) {
-        FILE* fo = fopen(a[8], "wb");
-        if (!fo || fwrite(S.data(), sizeof(double), S.size(), fo) != S.size()) return 4;
-        fclose(fo);
+        rc = write_file(a[8], S);
     }
     free(x), free(y);
     return rc;

@@ -7,38 +7,14 @@
 // `visit` fills the fields with their own indices, so what a thread fetched says where it read: owner[k] is the one plane whose
 // workgroups fetched value k (-1: nobody, -2: fetched more than once); it also checks that the thread holds the u value and the v value
 // of the same cell.  It has its own main, so it is built with -fsanitize=address,undefined and run directly.
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "host_main.h"
 #include "wind_core.h"
 using namespace wind;
-
-template <typename T>
-static T* read_file(const char* path, size_t n) {
-    T* p = (T*)aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16 + 16);
-    FILE* fi = fopen(path, "rb");
-    if (!fi || fread(p, sizeof(T), n, fi) != n) exit(2);
-    fclose(fi);
-    return p;
-}
-
-template <typename T>
-static int write_out(const char* path, const T* data, size_t n) {
-    FILE* fo = fopen(path, "wb");
-    if (!fo || (n && fwrite(data, sizeof(T), n, fo) != n)) return 4;
-    fclose(fo);
-    return 0;
-}
-
-#define PHASE(call) for (int t = 0; t < THREADS; ++t) { call; }
 
 // one workgroup of wind_power_kernel; owner (if given) collects who fetched what; returns 0 or the number of a failed check
 static int group(View& w, std::vector<int>* owner) {
     std::vector<Thread> th(THREADS);
-    for (int i = 0; i < LDS_DOUBLES; ++i) w.lds[i] = NAN;  // a slot nobody stashed that reaches a sum shows
+    poison(w.lds, LDS_DOUBLES, NAN);  // a slot nobody stashed that reaches a sum shows
     PHASE(t_fetch(w, th[t], t))
     if (owner) {
         for (int t = 0; t < THREADS; ++t)
@@ -71,7 +47,7 @@ static int table(char** a) {
     const size_t n = K >= 2 && K <= MAX_K ? (size_t)table_bytes(K) : 16;
     unsigned char* bytes = (unsigned char*)aligned_alloc(16, n);
     memset(bytes, 0, n);
-    int rc = build_table(xs, ps, K, bytes) ? 5 : write_out(a[3], bytes, n);
+    int rc = build_table(xs, ps, K, bytes) ? 5 : write_file(a[3], bytes, n);
     free(xs), free(ps), free(bytes);
     return rc;
 }
@@ -87,7 +63,7 @@ static int run(char** a, bool visit) {
     double xs2[2] = {1.0, 2.0}, ps2[2] = {0.0, 1.0}, *xs = xs2, *ps = ps2;
     if (visit) {
         if (n >= (1u << 24)) return 3;  // an index must be an fp32
-        x = (float*)aligned_alloc(16, n * 4 + 16);
+        x = alloc16<float>(n);
         for (size_t k = 0; k < n; ++k) x[k] = (float)k;
     } else {
         K = atoi(a[7]);
@@ -108,11 +84,11 @@ static int run(char** a, bool visit) {
     for (w.plane = 0; w.plane < planes && !rc; ++w.plane)
         for (w.chunk = 0; w.chunk < nc && !rc; ++w.chunk) rc = group(w, visit ? &owner : nullptr);
     if (!rc && visit) {
-        rc = write_out(a[5], owner.data(), owner.size());
+        rc = write_file(a[5], owner.data(), owner.size());
     } else if (!rc) {
         if (nc > 1)
             for (long long e = 0; e < planes * 2; ++e) f_fold(partial.data(), sums.data(), e, nc);
-        rc = write_out(a[11], sums.data(), sums.size()) | write_out(a[12], derived.data(), derived.size());
+        rc = write_file(a[11], sums.data(), sums.size()) | write_file(a[12], derived.data(), derived.size());
     }
     free(x), free(bytes);
     if (!visit) free(xs), free(ps);
