@@ -27,6 +27,22 @@ __device__ __forceinline__ bool src_pixel(const A& p, int oh, int ow, int kh, in
 }
 
 
+// the output grid as the mode's function of the input grid (c2w_hip.h, next to C2wConvArgs): the only grids src_pixel has a definition
+// for -- on any other the gather walks into the next image (C2W_CONV_UP with Hout > 2 * Hin).  An unknown mode is the callers' business.
+inline bool c2w_conv_grid_defined(const C2wConvArgs& a) {
+    auto ok = [&](int in, int out) {
+        switch (a.mode) {
+            case C2W_CONV_1X1:
+            case C2W_CONV_S1: return out == in;
+            case C2W_CONV_S2: return out == (in + 1) / 2 || out == in / 2;
+            case C2W_CONV_UP: return out == 2 * in;
+            case C2W_CONV_TS2: return out == 2 * in - 1 || out == 2 * in;
+        }
+        return true;
+    };
+    return ok(a.Hin, a.Hout) && ok(a.Win, a.Wout);
+}
+
 // exact n / d for n < 2^31 with a host-precomputed (magic, shift): q = umulhi(n, magic) >> shift; magic == 0 means d == 1
 struct FastDiv {
     uint32_t magic, shift;

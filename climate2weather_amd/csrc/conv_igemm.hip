@@ -455,6 +455,8 @@ extern "C" int c2w_conv_forward(const C2wConvArgs* a, int dtype, int naive, void
     if (a->Cout <= 0 || a->Cout % (16 / esz) != 0 || a->ldy % (16 / esz) != 0) return C2W_ERR_BAD_SHAPE;
     if (a->B <= 0 || a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0) return C2W_ERR_BAD_SHAPE;
     if (a->Hout >= 65536 || a->Wout >= 65536) return C2W_ERR_BAD_SHAPE;
+    if (a->Cout > a->ldy) return C2W_ERR_BAD_SHAPE;                            // a row of y holds Cout channels (c2w_hip.h)
+    if (!c2w_conv_grid_defined(*a)) return C2W_ERR_BAD_SHAPE;                  // the output grid is the mode's function of the input grid
     if (a->act < C2W_ACT_NONE || a->act > C2W_ACT_RELU_PAIR) return C2W_ERR_BAD_ARG;
     if ((a->act == C2W_ACT_SILU_PAIR || a->act == C2W_ACT_RELU_PAIR) && a->y2 == nullptr) return C2W_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;

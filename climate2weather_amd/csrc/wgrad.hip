@@ -587,6 +587,7 @@ static int wgrad_check(const C2wConvArgs* a, int dtype) {
     if (a->B <= 0 || a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0) return C2W_ERR_BAD_SHAPE;
     if ((long long)a->B * a->Hout * a->Wout >= (1ll << 31)) return C2W_ERR_BAD_SHAPE;
     if (a->mode != C2W_CONV_1X1 && a->mode != C2W_CONV_S1 && a->mode != C2W_CONV_S2 && a->mode != C2W_CONV_UP) return C2W_ERR_BAD_ARG;
+    if (!c2w_conv_grid_defined(*a)) return C2W_ERR_BAD_SHAPE;  // the output grid is the mode's function of the input grid (c2w_hip.h)
     return 0;
 }
 

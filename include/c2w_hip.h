@@ -55,7 +55,18 @@ enum { C2W_CONV_POOL2 = 1, C2W_CONV_WPACKED = 2, C2W_CONV_NO_Y = 4, C2W_CONV_DET
  * and after a call), like c2w_conv_wgrad's workspace. */
 
 /* y[q][co] = act( sum_{tap,ci} w[co][tap][ci] * x[src(q,tap)][ci] + bias[co] ) (* mul' ) (+ res)
- * q runs over the B*Hout*Wout output pixels in NHWC raster order. */
+ * q runs over the B*Hout*Wout output pixels in NHWC raster order.
+ *
+ * Geometry the launchers take (c2w_conv_forward, c2w_conv_wgrad and its siblings; anything else is C2W_ERR_BAD_SHAPE, before a launch):
+ *   - Cout <= ldy.  A row of y, y2, res, mul (and of dY) holds ldy channels of which the first Cout are live: the columns [Cout, ldy) of
+ *     every output are left untouched, and what the inputs hold there is never used.
+ *   - The output grid is the mode's function of the input grid, per axis: Hout == Hin for C2W_CONV_1X1 and C2W_CONV_S1; (Hin + 1) / 2 or
+ *     Hin / 2 for C2W_CONV_S2; 2 * Hin for C2W_CONV_UP; 2 * Hin - 1 or 2 * Hin for C2W_CONV_TS2 (the two input sizes a stride-2 conv
+ *     maps to Hin) -- and the same for Wout from Win.  No other grid has a definition: the gather would walk into the next image.
+ * The kernels take every zero they need (halos, weight rows >= wrows, the bias tail, the missing partner of an odd batch) from the range
+ * check of buffer descriptors built from exactly these sizes: nothing outside an operand is ever read into a result.
+ * Alignment is a precondition the launchers do NOT verify: every operand pointer (x, w, res, mul, y, y2, dY, dw, the workspaces) must be
+ * 16-byte aligned -- nothing stronger is asked for; bias and dbias are read and written as single floats. */
 typedef struct C2wConvArgs {
     const void* x;     /* [B][Hin][Win][Cin]  (Cin = channel stride; multiple of 32 (f32) / 64 (bf16)) */
     const void* w;     /* [wrows][taps][Cin], taps = 1 or 9 (kh*3+kw); rows >= wrows read as zero */

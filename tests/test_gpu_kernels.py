@@ -76,6 +76,14 @@ CONV_CASES = [
 ]
 
 
+# rows wider than the channels written (ldy > Cout > wrows): the padding columns of y and y2 keep what they held.  Here only, not in CONV_CASES
+# (the weight-gradient and determinism tests import that list); tests/test_gpu_conv_geometry.py runs every route at such rows.
+PADDED_ROW_CASES = [
+    (ops.CONV_1X1, 8, 1, 1, 64, 200, 199, 256),     # the Linear layers' transposed operand (engine.py: ld = the padded row)
+    (ops.CONV_S1, 2, 8, 16, 64, 72, 71, 80),        # halo-patch kernel, one partial channel tile
+]
+
+
 def _out_hw(mode, Hin, Win):
     if mode == ops.CONV_S2:
         return Hin // 2, Win // 2
@@ -85,7 +93,7 @@ def _out_hw(mode, Hin, Win):
 
 
 @pytest.mark.parametrize("dt", [F32, BF16, F16])
-@pytest.mark.parametrize("case", CONV_CASES)
+@pytest.mark.parametrize("case", CONV_CASES + PADDED_ROW_CASES)
 @pytest.mark.parametrize("naive", [0, 1, 2])
 def test_conv_forward(case, dt, naive):
     mode, B, Hin, Win, Cin, Cout, wrows, ldy = case

@@ -6,7 +6,12 @@ arguments can reach that), an unsupported shape.  Every row returns a negative C
 device addresses are made-up multiples of 4096 and nothing dereferences them.  Pointers the library reads ON THE HOST (the quantile
 levels, the FSS radii, the wind curve) are real arrays.  The expected codes were recorded from the launchers as they were when the
 checks were still written out in every entry point; c2w_aligned and c2w_grid_fits (csrc/launch.h) must not change one of them, nor
-the order unsupported -> bad argument -> bad shape.  Skipped where a GPU is visible: no row may ever be in a position to launch."""
+the order unsupported -> bad argument -> bad shape.  Skipped where a GPU is visible: no row may ever be in a position to launch.
+
+c2w_conv_forward and the weight-gradient entry points take their geometry in a C2wConvArgs block (ConvBlock below: a change that names
+one of its fields lands in the block).  Their rows pin the geometry no definition covers (include/c2w_hip.h next to C2wConvArgs): more
+channels than a row of y holds, and an output grid that is not the mode's function of the input grid -- C2W_ERR_BAD_SHAPE, before any
+launch."""
 import ctypes
 
 import pytest
@@ -26,8 +31,29 @@ class Dev:
 
 DEV = Dev()
 
+
+class ConvBlock:
+    """A C2wConvArgs passed by reference: the fields given (DEV: a made-up device address), every other one zero."""
+
+    def __init__(self, **fields):
+        self.fields = fields
+
+    def build(self, change):
+        f = dict(self.fields, **{k: v for k, v in change.items() if k in self.fields})
+        block = _lib.ConvArgs()
+        for j, (k, v) in enumerate(f.items()):
+            setattr(block, k, 4096 * (64 + j) if v is DEV else v)
+        return block
+
+
+X1, S1, S2, UP, TS2 = _lib.CONV_1X1, _lib.CONV_S1, _lib.CONV_S2, _lib.CONV_UP, _lib.CONV_TS2
+CONV = dict(x=DEV, w=DEV, y=DEV, B=2, Hin=8, Win=8, Cin=64, Hout=8, Wout=8, Cout=64, ldy=64, wrows=64, mode=S1)  # bf16: 3x3 stride 1 on 8x8
+
 # name -> the base call, in the order of the C signature (DEV: a device pointer)
 BASE = {
+    "c2w_conv_forward": dict(args=ConvBlock(**CONV), dtype=_lib.DTYPE_BF16, naive=0, stream=None),
+    "c2w_conv_wgrad": dict(args=ConvBlock(**CONV), dw=DEV, dbias=DEV, workspace=None, workspace_bytes=0, dtype=_lib.DTYPE_BF16, stream=None),
+    "c2w_conv_wgrad_dispatch": dict(args=ConvBlock(**CONV), dtype=_lib.DTYPE_BF16),
     "c2w_rapsd": dict(x=DEV, spec=DEV, n_fields=4, H=8, W=8, stream=None),
     "c2w_ssim": dict(x=DEV, y=DEV, data_range=DEV, out=DEV, n_pairs=4, n_truth=2, H=16, W=16, win=7, stream=None),
     "c2w_swd_project": dict(x=DEV, theta=DEV, shift=DEV, scale=DEV, proj=DEV, n_rep=2, T=2, F=2, d=64, P=4, stream=None),
@@ -71,8 +97,21 @@ def off(by, *names):  # a pointer of the 16-, 8- (by 4 bytes) or 4-byte class (b
 
 M20 = 1 << 20  # T = F = 2^20: 2^40 planes, over any grid while a plane is one chunk (hw = 16 needs no scratch)
 
+# an output grid that is not the mode's function of the input grid (8x8 in): 1x1 and stride 1 keep it, stride 2 halves it (rounding either
+# way), the up-conv doubles it, the stride-2 input gradient gives 2 n - 1 or 2 n
+GRID = [("stride 1, a row more", dict(Hout=9)), ("stride 1, a column less", dict(Wout=7)), ("1x1, a column less", dict(mode=X1, Wout=7)),
+        ("stride 2, Hout under Hin / 2", dict(mode=S2, Hout=3, Wout=4)), ("stride 2, Wout over (Win + 1) / 2", dict(mode=S2, Hout=4, Wout=5)),
+        ("up-conv, Hout over 2 Hin", dict(mode=UP, Hout=17, Wout=16)), ("up-conv, Wout under 2 Win", dict(mode=UP, Hout=16, Wout=15))]
+GRID_TS2 = [("stride-2 input gradient, Hout over 2 Hin", dict(mode=TS2, Hout=17, Wout=16)),
+            ("stride-2 input gradient, Wout under 2 Win - 1", dict(mode=TS2, Hout=16, Wout=14))]
+
 # (entry point, [(what is broken, {argument: None | a byte offset for a device pointer | a value})], the codes in that order)
 TABLE_ROWS = [
+    ("c2w_conv_forward", null("x", "w", "y") + [("Cout over ldy", dict(ldy=56)), ("Cout over ldy, 1x1", dict(mode=X1, ldy=8))] + GRID + GRID_TS2,
+     [BAD_ARG] * 3 + [BAD_SHAPE] * (2 + len(GRID) + len(GRID_TS2))),
+    ("c2w_conv_wgrad", [("Cout over ldy", dict(ldy=56))] + GRID + [("the stride-2 input gradient has no weight gradient", dict(mode=TS2, Hout=16, Wout=16))],
+     [BAD_SHAPE] * (1 + len(GRID)) + [BAD_ARG]),
+    ("c2w_conv_wgrad_dispatch", [("Cout over ldy", dict(ldy=56))] + GRID, [BAD_SHAPE] * (1 + len(GRID))),
     ("c2w_rapsd", null("x", "spec") + off(4, "x") + [("grid", dict(n_fields=1 << 35)), ("unsupported", dict(H=12, W=12))],
      [BAD_ARG, BAD_ARG, BAD_ARG, BAD_SHAPE, UNSUPPORTED]),
     ("c2w_ssim", null("x", "y", "data_range", "out") + off(4, "x", "y", "out") + [("grid", dict(n_pairs=1 << 40)), ("unsupported", dict(win=9))],
@@ -129,13 +168,16 @@ def arguments(name, change):
     out = []
     for i, (arg, value) in enumerate(BASE[name].items()):
         address = 4096 * (16 + i)
-        if arg in change:
+        if isinstance(value, ConvBlock):
+            value = ctypes.byref(value.build(change))
+        elif arg in change:
             c = change[arg]
             value = address + c if value is DEV and isinstance(c, int) else c
         elif value is DEV:
             value = address
         out.append(value)
-    assert set(change) <= set(BASE[name]), (name, change)
+    blocks = [f for v in BASE[name].values() if isinstance(v, ConvBlock) for f in v.fields]
+    assert set(change) <= set(BASE[name]) | set(blocks), (name, change)
     return out
 
 
