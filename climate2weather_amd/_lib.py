@@ -147,6 +147,9 @@ _PROTOS = {
     "c2w_spell_supported": [c_int, c_int, c_int, c_int],
     "c2w_spell_update": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_longlong, c_void_p],
+    "c2w_objects_supported": [c_int, c_int, c_int, c_int, c_int],
+    "c2w_object_tables": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                          c_int, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

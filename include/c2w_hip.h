@@ -762,6 +762,37 @@ int c2w_fss_sums(const float* x, const float* y, const float* thr, const int* di
 int c2w_spell_supported(int hw, int K, int max_duration, int period); /* 1 or 0 */
 int c2w_spell_update(const float* x, const float* y, const float* thr, const int* dir, int* state, long long* hist, long long* onsets,
                      long long* invalid, int M, int T, int F, int hw, int K, int max_duration, int period, long long t0, void* stream);
+/* Event objects of an ensemble (climate2weather_amd.objects): how many events are there, how big are they and where?  The tables above
+ * take a plane as a bag of cells (c2w_event_counts), a box of cells (c2w_fss_sums) or a series per cell (c2w_spell_update); none knows
+ * which event cells belong together.  The definitions are elementary and verified by known answers; the centroid displacement is the
+ * binary-mass form of the L1 of Wernli's SAL, recalled (README, statement 15).
+ *
+ * The event and the rows are those of c2w_spell_update: x is [M][T][F][H W], y is [T][F][H W] or NULL, thr[F][K] fp32 and dir[F][K]
+ * int, x >= thr (dir != 0) or x <= thr (dir == 0), IEEE comparisons, a NaN is no event; d = 0 is the truth if y is given, then the M
+ * members; D = M + 1, or M without a truth.  An OBJECT is a maximal connected set of event cells of one (d, t, f, k) plane of H x W
+ * cells; connectivity 4 joins edge neighbours, 8 edge and corner neighbours; nothing wraps around.  Its LABEL is the smallest linear
+ * index i W + j of its cells: it depends on nothing but the plane.
+ *   plane[D][T][F][K][6] long long: the number of objects, the event cells, the largest area, the objects that touch the domain's
+ *     border (they are cut by it: censored), sum i and sum j over the event cells.  Written, not added to.
+ *   area_hist[D][F][K][B] long long, B = floor(log2(H W)) + 1: += the objects of all T planes with area in [2^b, 2^(b + 1)).  An
+ *     ACCUMULATOR: the caller zeroes it once and the call adds; planes are independent in time, so a year may arrive in blocks.
+ *   objects[D][T][F][K][max_objects][8] int (NULL at max_objects = 0): the first max_objects objects of the plane in label order as
+ *     (label, area, sum_i, sum_j, i_min, i_max, j_min, j_max); the unused slots are WRITTEN as label -1 and the rest 0.  Objects past
+ *     the cap are not listed but are in every other table: plane[..][0] - max_objects says how many are missing.
+ *   invalid[D][T][F] long long: the NaN cells.  Written, not added to.
+ * object_tables_kernel: a workgroup of 512 owns one (d, t, f, k) plane -- the thresholds run over the grid, the plane is re-read from
+ * the caches.  The indicator is staged once with 16-byte loads as a bit mask and labelled entirely in LDS: 16-bit labels, the runs
+ * along a row take the index of their first cell, the runs of adjacent rows (and diagonals at connectivity 8) are united by a
+ * label-equivalence union-find that links the larger root to the smaller with a compare-and-swap, then one flattening pass; the
+ * minimum labels make the result independent of any order.  A run adds its length once to its root's area; the roots are ranked by a
+ * scan in index order, which is the label order of the list.  No global atomics but the one 64-bit add per non-zero area bin, no
+ * scratch memory, no host read-back, everything on the caller's stream; every data-dependent loop has a trip bound derived from H W.
+ * 80128 bytes of LDS, two workgroups a CU (csrc/objects_maps.h has the budget).  Supported: W a multiple of 4, H W <= 16384,
+ * 1 <= K <= 8, connectivity 4 or 8, 0 <= max_objects <= 256, M >= 1 (x, y 16-byte aligned); everything else returns
+ * C2W_ERR_UNSUPPORTED and writes nothing.  T = 0 does nothing. */
+int c2w_objects_supported(int H, int W, int K, int connectivity, int max_objects); /* 1 or 0 */
+int c2w_object_tables(const float* x, const float* y, const float* thr, const int* dir, long long* plane, long long* area_hist, int* objects,
+                      long long* invalid, int M, int T, int F, int H, int W, int K, int connectivity, int max_objects, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
