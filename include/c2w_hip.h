@@ -793,6 +793,46 @@ int c2w_spell_update(const float* x, const float* y, const float* thr, const int
 int c2w_objects_supported(int H, int W, int K, int connectivity, int max_objects); /* 1 or 0 */
 int c2w_object_tables(const float* x, const float* y, const float* thr, const int* dir, long long* plane, long long* area_hist, int* objects,
                       long long* invalid, int M, int T, int F, int H, int W, int K, int connectivity, int max_objects, void* stream);
+/* Extremes of an ensemble (climate2weather_amd.extremes): what does the tail do?  Every score above averages over the whole
+ * distribution or needs a threshold chosen in advance; none sees the largest gust of a day or the 20-block return level.  The sample
+ * L-moments are those of scipy.stats.lmoment(standardize=False); the GEV fit by L-moments is recalled from Hosking & Wallis and lives
+ * in extremes.py as float64 tensor algebra (README, statement 16).
+ *
+ * Rows: d = 0 is the truth if y is given, then the M members; D = M + 1, or M without a truth.  x is [M][T][F][hw], y is [T][F][hw]
+ * or NULL, dense fp32.  A SERIES is one (d, f, cell) over time; dir[F] int is 1 for maxima and 0 for minima of variable f; block b holds
+ * the absolute hours [b block, (b + 1) block).  The EXTREME of a block is taken in the total order of the key of c2w_quantiles on the
+ * fp32 bits: -0.0 < +0.0, the infinities are ordinary values, NaN hours are skipped and counted per (d, f) in invalid; a block whose
+ * hours are all NaN has the extreme NaN, stored as the one pattern 0x7FC00000.
+ *
+ * c2w_block_extremes_update takes T >= 0 consecutive hours whose first plane is the absolute hour t0 >= 0 (T = 0 does nothing).
+ *   open[D][F][hw] unsigned: the running key of the open block, read at the start and written at the end.  The key of a value is
+ *     key ^ (dir ? 0 : ~0), so that both directions are an unsigned maximum; 0 is "no value yet" and the caller's initial value.
+ *   table[D][F][B][hw] float, B = max_blocks: the extreme of every block whose LAST hour lies in this call is stored at index
+ *     t / block, with plain 16-byte stores, exactly once.  Nothing else of table is touched.
+ *   invalid[D][F] long long: += the NaN cell-hours; an ACCUMULATOR the caller zeroes once.
+ * block_extremes_kernel: a workgroup of 256 owns (row, variable, chunk of 1024 cells); a thread owns 4 adjacent cells and walks the T
+ * planes in order with 16-byte loads, 8 in flight, two integer compares a value; 4 bytes of LDS for the NaN count, one 64-bit integer
+ * add per workgroup, no scratch, no host read-back, everything on the caller's stream.  Integer maxima commute: the table equals the
+ * definition bit for bit for every cut of the time axis into calls.  Time is not split over workgroups.  Supported: hw a multiple of
+ * 4, 1 <= block <= 2^20, 1 <= max_blocks <= 4096, M >= 1 (x, y, open, table 16-byte aligned); everything else returns
+ * C2W_ERR_UNSUPPORTED and writes nothing.  T beyond 2^20, or a block that would end at or beyond index max_blocks, is
+ * C2W_ERR_BAD_SHAPE.
+ *
+ * c2w_lmoments: table[R][n][hw] float (R = D F rows of n block extremes) -> lmom[R][4][hw] double, the sample L-moments l1 .. l4 of
+ * each cell's n' <= n non-NaN extremes x_(0) <= .. <= x_(n' - 1), and n_valid[R][hw] int = n'.  With p = x_(n' / 2) the pivot and
+ * e_j = x_(j) - p:  S_r = sum_j N_r(j) e_j in ascending j with N_0 = 1, N_1 = j, N_2 = j (j - 1), N_3 = j (j - 1)(j - 2);
+ * b_r = S_r / (n' (n' - 1) .. (n' - r)), one division by an exact integer;  l1 = p + b_0, l2 = 2 b_1 - b_0, l3 = (6 b_2 - 6 b_1) + b_0,
+ * l4 = ((20 b_3 - 30 b_2) + 12 b_1) - b_0; all in double on exactly converted fp32 values, no multiply fused with an add; l_r is NaN
+ * where n' < r.  csrc/extremes_maps.h derives the error bound c_r(n') 2^-53 sum_j |e_j| (+ 2^-53 |l1| at r = 1).
+ * lmoments_kernel: a thread holds the K x V extremes of V adjacent cells in registers (K = n rounded up to 8 / 16 / 32 / 64, V = 4, 4,
+ * 2, 1), sorts them with the static Batcher network of c2w_crps_terms -- pads and NaNs are +inf and sort to the top -- and forms the
+ * four moments; plain 8-byte stores, no LDS, no atomics, no scratch: the bits are the same at every position of the launch.
+ * Supported: hw a multiple of 4, 1 <= n <= 64 (table 16-byte aligned); else C2W_ERR_UNSUPPORTED, nothing written.  R = 0 does nothing. */
+int c2w_block_extremes_supported(int hw, int block, int max_blocks); /* 1 or 0 */
+int c2w_block_extremes_update(const float* x, const float* y, const int* dir, unsigned* open, float* table, long long* invalid, int M, int T,
+                              int F, int hw, int block, int max_blocks, long long t0, void* stream);
+int c2w_lmoments_supported(int hw, int n); /* 1 or 0 */
+int c2w_lmoments(const float* table, double* lmom, int* n_valid, long long R, int n, int hw, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
