@@ -833,6 +833,37 @@ int c2w_block_extremes_update(const float* x, const float* y, const int* dir, un
                               int F, int hw, int block, int max_blocks, long long t0, void* stream);
 int c2w_lmoments_supported(int hw, int n); /* 1 or 0 */
 int c2w_lmoments(const float* table, double* lmom, int* n_valid, long long R, int n, int hw, void* stream);
+/* Co-moments of an ensemble (climate2weather_amd.dependence): do the variables still belong together, and does each member co-vary in
+ * time with the truth?  Every score above judges a variable on its own.  Pearson correlation and the Taylor-diagram identity are the
+ * textbook definitions (README, statement 17); they live in dependence.py as float64 tensor algebra on the tables below.
+ *
+ * Rows: d = 0 is the truth if y is given, then the M members; D = M + 1, or M without a truth.  x is [M][T][F][hw], y is [T][F][hw]
+ * or NULL, dense fp32.  Hour t is VALID for (d, cell) iff all F values of row d at the cell and, with a truth, all F truth values at
+ * the cell have an exponent field that is not all ones (infinities are invalid, not values).  An invalid hour adds nothing to
+ * (d, cell) and is counted in invalid[d].
+ *
+ * c2w_comoments_update takes T >= 0 consecutive hours (T = 0 does nothing) and reads and writes the state, which the caller zeroed
+ * when it made it:
+ *   n[D][hw] int: the valid hours so far; 0 is "no pivot yet".
+ *   pivot[D][F][hw], truth_pivot[D][F][hw] float: the row's and the truth's values at the first valid hour of (d, cell), never
+ *     changed afterwards.  truth_pivot is not touched (and may be NULL) without a truth.
+ *   sums[D][NS][hw] double: with e_f = (double)x_f - (double)P_f and eT_f = (double)y_f - (double)PT_f, per valid hour in hour order,
+ *     each a plain s = s + term, no multiply fused with an add:  S[f] += e_f (F entries);  C[f,g] += e_f e_g for f <= g (F (F + 1) / 2
+ *     entries in the order (0,0), (0,1) .. (0,F-1), (1,1) ..);  with a truth also ST[f] += eT_f, QT[f] += eT_f eT_f, X[f] += e_f eT_f
+ *     (F entries each).  NS = 4 F + F (F + 1) / 2 with a truth, F + F (F + 1) / 2 without.  Row 0 has eT = e.
+ *   invalid[D] long long: += the invalid cell-hours; an ACCUMULATOR the caller zeroes once.
+ * comoments_update_kernel<F, TRUTH>: a workgroup of 256 owns (row, chunk of 256 V cells), V = 4 for F = 1, 2 for F = 2, 1 above; a
+ * thread keeps the state of its V adjacent cells in registers, walks the T planes in order, 4 hours loaded in a straight line, and
+ * stores the state where it loaded it; 4 bytes of LDS for the invalid count, one 64-bit integer add per workgroup, no atomics on
+ * floats, no scratch, no host read-back, everything on the caller's stream.  One thread adds a series' terms in hour order, so the
+ * tables are the same bit for bit at every position of a launch and for every cut of the hours into calls; csrc/comoments_maps.h
+ * derives the error bound against exact arithmetic, (n + 1) 2^-53 sum |e| for S and ST, (n + 2) 2^-53 sum |e e| for the products.
+ * Time is not split over workgroups.  Supported: hw a multiple of 4, 1 <= F <= 8, M >= 1 (x, y, n, pivot, truth_pivot, sums 16-byte
+ * aligned); everything else returns C2W_ERR_UNSUPPORTED and writes nothing.  T beyond 2^20 is C2W_ERR_BAD_SHAPE: the host walks a
+ * longer update in parts. */
+int c2w_comoments_supported(int hw, int F); /* 1 or 0 */
+int c2w_comoments_update(const float* x, const float* y, int* n, float* pivot, float* truth_pivot, double* sums, long long* invalid, int M, int T,
+                         int F, int hw, void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
