@@ -157,6 +157,8 @@ _PROTOS = {
     "c2w_lmoments": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p],
     "c2w_comoments_supported": [c_int, c_int],
     "c2w_comoments_update": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "c2w_block_moments_supported": [c_int, c_int, c_int],
+    "c2w_block_moments": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "c2w_timestep_embedding": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "c2w_mu_sigma": [c_void_p, c_void_p, c_int, c_float, c_void_p],
     "c2w_publish_scalar": [c_void_p, c_void_p, c_int, c_void_p],

@@ -15,7 +15,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"]
 SOURCES = ["conv_igemm.hip", "conv_patch.hip", "conv_patch3.hip", "wgrad.hip", "wgrad_patch.hip", "pointwise.hip", "attention.hip", "attention_mfma.hip",
            "sampler.hip", "conv_center.hip", "evaluation.hip", "spectrum.hip", "ssim.hip", "swd.hip", "kde.hip", "quantile.hip",
            "crps.hip", "wind.hip", "escore.hip", "temporal.hip", "qmap.hip", "events.hip", "spells.hip", "objects.hip", "extremes.hip",
-           "comoments.hip"]
+           "comoments.hip", "blockmoments.hip"]
 
 
 STAMP = os.path.join(HERE, "build", "sources.sha256")

@@ -1,5 +1,5 @@
 """The host side the ensemble metrics share (``crps``, ``ssim``, ``spectra``, ``wasserstein``, ``marginals``, ``quantiles``,
-``windpower``, ``multivariate``, ``temporal``, ``biascorrect``, ``events``, ``spells``, ``objects``, ``extremes``, ``dependence``): how an input becomes what the kernels read, how the float64 routes are chunked, how scratch is
+``windpower``, ``multivariate``, ``temporal``, ``biascorrect``, ``events``, ``spells``, ``objects``, ``extremes``, ``dependence``, ``scalesplit``): how an input becomes what the kernels read, how the float64 routes are chunked, how scratch is
 allocated, what the argument checks say and what a per-variable report is.  Plain functions; no metric imports another metric for any of
 it.
 

@@ -864,6 +864,31 @@ int c2w_lmoments(const float* table, double* lmom, int* n_valid, long long R, in
 int c2w_comoments_supported(int hw, int F); /* 1 or 0 */
 int c2w_comoments_update(const float* x, const float* y, int* n, float* pivot, float* truth_pivot, double* sums, long long* invalid, int M, int T,
                          int F, int hw, void* stream);
+/* Block moments at the observation grid (climate2weather_amd.scalesplit): averaged back to the coarse grid, does a member still
+ * reproduce what it was conditioned on, and how much variability does it add below that grid?  For blocks of s x s cells with block
+ * means m, sum (x - y)^2 = s^2 (m_x - m_y)^2 + sum ((x - m_x) - (y - m_y))^2 (README, statement 18); the scores live in scalesplit.py
+ * as float64 tensor algebra on the tables below.
+ *
+ * Rows: d = 0 is the truth if y is given, then the M members; D = M + 1, or M without a truth.  x is [M][T][F][H][W], y is
+ * [T][F][H][W] or NULL, dense fp32; h = H / s, w = W / s.  For each block of each (d, t, f) plane, cells x[r][c], r, c in 0 .. s-1:
+ *   pivot[D][T][F][h][w] float: x[0][0], the fp32 value kept as its bits.
+ *   n[D][T][F][h][w] int: the cells whose exponent field is not all ones (infinities are invalid, not values).
+ *   sums[D][T][F][NS][h][w] double, NS = 3 with a truth and 2 without: with e = (double)x - (double)pivot and, from the truth's block
+ *     and the truth's pivot, eT: the column sums A_c = sum_r e, Q_c = sum_r e e, X_c = sum_r e eT, each sequential from +0.0 in row
+ *     order, then S1 = sum_c A_c, S2 = sum_c Q_c, X = sum_c X_c, each sequential from +0.0 in column order; every product rounded on
+ *     its own, no multiply fused with an add.  A block with n < s^2 holds the canonical NaN 0x7ff8000000000000 in S1 and S2; X is that
+ *     NaN if the block or the truth's block is invalid.  Row 0 carries the truth against itself (X == S2).
+ * block_moments_kernel<S, TRUTH>: an item is (plane, block row, quad of 4 adjacent columns), the items of a row's planes numbered
+ * flat; a workgroup of 256 takes 256 consecutive items, a thread walks its item's S rows with 16-byte loads, 8 rows in flight, and
+ * keeps the 4 x NS column sums in registers; 26 KiB of LDS, one barrier, and the first thread of each block adds the S columns in
+ * order and stores with plain stores.  No atomics, no scratch, no host read-back, everything on the caller's stream.  The order
+ * fixes the bits: they are the same at every position of a launch; csrc/blockmoments_maps.h derives the error bound against exact
+ * arithmetic, 2 s 2^-53 sum |e| for S1 and (2 s + 2) 2^-53 sum |e e| for S2 and X.  Supported: s in {4, 8, 16, 32}, H and W
+ * multiples of s, M >= 1, F >= 1, the items of a row within an int and the grid within a launch (x, y 16-byte aligned); everything
+ * else returns C2W_ERR_UNSUPPORTED and writes nothing.  T = 0 does nothing. */
+int c2w_block_moments_supported(int H, int W, int s); /* 1 or 0 */
+int c2w_block_moments(const float* x, const float* y, int* n, float* pivot, double* sums, int M, int T, int F, int H, int W, int s,
+                      void* stream);
 /* The network's output convolution (model/nn.py:194: 3x3, stride 1, zero padding) restricted to what the sampler's fold keeps
  * (src/thor/score.py:76-88: of a window's w * F output channels only the centre frame's F, all of them only for the first / last
  * window of a trajectory): rows r0 .. r0 + nr - 1 (nr <= 16) of the [wrows][9][Cin] weight matrix `w` over the NHWC rows `x`
